@@ -16,14 +16,20 @@ round-2 definition (the step cut at train_nn_area.py:287) beside it.  Secondary 
 (Phase-B-only rate at the same batch: the per-image unit of SURVEY.md §8d) and `configs1_b512` (BASELINE configs[1]: B = 512,
 Phase B).  `--phase-b-only` makes the Phase-B rate the `value` instead.
 
-Inputs are resident in HBM, random-init weights, fp32 storage.  One JSON line on rank 0 (contract in the task statement), plus
+Inputs are resident in HBM, random-init weights, fp32 storage.  One JSON line on rank 0 (contract in the task statement).  A plain
+run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` = milliseconds per timed step).  Everything
+else is measured with `--full` only: the `phase_b` leg, the round-2 and select-before-clean full steps, `configs1_b512`,
+`small_batch`, and
   "roofline":     the implicit-GEMM MFMA conv class (dominant): algorithmic flops / HIP-event time over the same K steps
                   re-run single-stream; and the SAME class with every product forced onto the fp32 MFMA instruction
                   (`native_fp32`), against the 157.3 TFLOP/s fp32 matrix peak
   "cpu_baseline": the CPU oracle (oracle/, a torch-CPU restatement pinned to the reference) timed on the host cores on a
                   bounded sample at B = 32 and B = 128 — N = 1 only.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--phase-b-only]
+`--dump-outputs DIR` writes what the last timed step computed on rank 0 as DIR/<name>.npy (see dump_outputs()); inputs and
+weights are seeded, so two builds run with the same arguments can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--phase-b-only] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -187,6 +193,24 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
+DUMP_CAP = 1 << 21                   # elements per dumped array (8 MB in fp32): a larger output is written as a sample of this size
+
+
+def dump_outputs(path, arrays):
+    """arrays: {name: tensor} -> path/<name>.npy, float64 if the tensor is float64, else float32.  An output of more than DUMP_CAP
+    elements is written flattened as the DUMP_CAP elements at fixed positions (a seeded permutation of its size, sorted), so
+    the files of two runs of the same workload line up element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_CAP].sort().values
+            t = t.flatten()[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -205,6 +229,12 @@ def main():
                          "per-kernel averages are then directly comparable with roofline.avg_launch_us)")
     ap.add_argument("--graph", action="store_true",
                     help="record the Phase-B step into a hipGraph and time replays (single GPU, implies --phase-b-only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed on rank 0 as DIR/<name>.npy: loss, log_probs and "
+                         "cleaned (Phase B's CRNN and UNet outputs), unet_params, and for the full step crnn_params and cer")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (phase_b, roofline and kernel figures, other configurations, small_batch, "
+                         "cpu_baseline); a plain run only times the K steps")
     args = ap.parse_args()
     if args.graph:
         args.phase_b_only = True
@@ -318,6 +348,8 @@ def main():
         lp = crnn(img)
         loss = ctc(lp, w.y_s, w.ins_s, w.lens_s) + mse(img, w.ones)
         w.last_lp = lp.detach()
+        if args.dump_outputs:
+            w.last_img = img.detach()
         loss.backward()
         if use_dist:
             timed_allreduce(fs.grad, "unet")         # one RCCL all-reduce of the flat 31 MB UNet gradient
@@ -431,9 +463,17 @@ def main():
             v.clear()
     if rank == 0:
         print(f"[bench] {args.steps} timed steps in {dt:.3f}s", file=sys.stderr, flush=True)
+    if args.dump_outputs and rank == 0:              # before any secondary leg moves the weights on
+        outs = {"loss": loss, "log_probs": W.last_lp, "cleaned": W.last_img,
+                "unet_params": torch.cat([p.detach().flatten() for p in prep.parameters()])}
+        if not args.phase_b_only:
+            outs["crnn_params"] = torch.cat([p.detach().flatten() for p in crnn.parameters()])
+            outs["cer"] = torch.tensor([W.sampler.cers[n] for n in W.names], dtype=torch.float64)
+        dump_outputs(args.dump_outputs, outs)
+    full = args.full
     # ---- Phase B alone at the same batch (the per-image unit of SURVEY.md §8d)
     dt_b = dt
-    if not args.phase_b_only and not args.no_phase_b_leg:
+    if full and not args.phase_b_only and not args.no_phase_b_leg:
         phase_b(W)
         dt_b, _ = timed(lambda: phase_b(W), args.steps)
 
@@ -455,9 +495,12 @@ def main():
         ops.set_overlap(overlap0)
         return prof, d, overlap0
 
-    prof, dt_serial, overlap0 = event_leg(main_step, args.steps)
+    prof, dt_serial, overlap0 = None, None, ops.overlap_enabled()
+    if full:
+        prof, dt_serial, overlap0 = event_leg(main_step, args.steps)
+    secondary = full and not args.no_secondary
     native = None
-    if not args.no_secondary:
+    if secondary:
         # the same steps with every product on v_mfma_f32_32x32x2_f32: the class against the fp32 matrix peak
         prev = ops.set_mfma_mode("f32")
         try:
@@ -467,7 +510,7 @@ def main():
         finally:
             ops.set_mfma_mode(prev)
     bf16_leg = None
-    if not args.no_secondary and ops.mfma_mode() == "split_f16":
+    if secondary and ops.mfma_mode() == "split_f16":
         # the same steps in the round-2 form (three-way bf16 split, six MFMAs per product): the two forms on the same box
         prev = ops.set_mfma_mode("split_bf16")
         try:
@@ -478,13 +521,13 @@ def main():
         finally:
             ops.set_mfma_mode(prev)
     no_cer = None
-    if not args.no_secondary and not args.phase_b_only:
+    if secondary and not args.phase_b_only:
         full_step_r2()
         dnc, _ = timed(full_step_r2, args.steps)
         no_cer = {"note": "Phase A + Phase B only (the round-2 timed region: the step cut at train_nn_area.py:287, before decode -> CER -> update_cer)",
                   "value": B * world * args.steps / dnc, "unit": "patch-images/s", "ms_per_step": dnc / args.steps * 1e3}
     sel_first = None
-    if not args.no_secondary and not args.phase_b_only:
+    if secondary and not args.phase_b_only:
         def step_sf():
             phase_a(W, select_first=True)
             loss = phase_b(W)
@@ -496,7 +539,7 @@ def main():
                              "cleaner then runs on the k picked images only (same results up to rounding; NOT the reference's order of work)",
                      "value": B * world * args.steps / dsf, "unit": "patch-images/s", "ms_per_step": dsf / args.steps * 1e3}
     c1 = None
-    if not args.no_secondary and B != 512:
+    if secondary and B != 512:
         W1 = Work(512)
         for _ in range(2):
             phase_b(W1)
@@ -506,36 +549,22 @@ def main():
         del W1
 
     traffic, traffic_dom, traffic_note = None, None, "no PMC profile for this build"
-    try:                                             # HBM bytes per launch of the dominant class, from the committed PMC pass of THIS build
-        pm = json.load(open(os.path.join(ROOT, "profiles", "r04_pmc_traffic.json")))
-        if pm.get("source_hash") != source_hash():
-            traffic_note = f"profiles/r04_pmc_traffic.json was taken on sources {pm.get('source_hash')} != this build {source_hash()}: refused"
-        elif pm.get("batch_per_gpu") != B or pm.get("full_step") != (not args.phase_b_only):
-            traffic_note = "profiles/r04_pmc_traffic.json was taken on another workload: refused"
-        else:
-            traffic = pm["conv_igemm"]["hbm_bytes_per_launch"]
-            kt = pm.get("per_kernel_bytes_per_launch", {}).get(DOMINANT_KERNEL)
-            traffic_dom = kt["fetch"] + kt["write"] if kt else None
-            traffic_note = "HBM bytes/launch, rocprofv3 --pmc FETCH_SIZE(x2)+WRITE_SIZE in separate passes, profiles/r04_pmc_traffic.json (same sources)"
-    except (OSError, KeyError, ValueError):
-        pass
+    if full:
+        try:                                             # HBM bytes per launch of the dominant class, from the committed PMC pass of THIS build
+            pm = json.load(open(os.path.join(ROOT, "profiles", "r04_pmc_traffic.json")))
+            if pm.get("source_hash") != source_hash():
+                traffic_note = f"profiles/r04_pmc_traffic.json was taken on sources {pm.get('source_hash')} != this build {source_hash()}: refused"
+            elif pm.get("batch_per_gpu") != B or pm.get("full_step") != (not args.phase_b_only):
+                traffic_note = "profiles/r04_pmc_traffic.json was taken on another workload: refused"
+            else:
+                traffic = pm["conv_igemm"]["hbm_bytes_per_launch"]
+                kt = pm.get("per_kernel_bytes_per_launch", {}).get(DOMINANT_KERNEL)
+                traffic_dom = kt["fetch"] + kt["write"] if kt else None
+                traffic_note = "HBM bytes/launch, rocprofv3 --pmc FETCH_SIZE(x2)+WRITE_SIZE in separate passes, profiles/r04_pmc_traffic.json (same sources)"
+        except (OSError, KeyError, ValueError):
+            pass
 
     if rank == 0:
-        ig, wg, ls = prof[ops.PROF_CONV_IGEMM], prof[ops.PROF_CONV_WGRAD], prof[ops.PROF_LSTM_STEP]
-        tf = lambda q: q["flops"] / (q["ms"] * 1e-3) / 1e12 if q["ms"] > 0 else 0.0
-        ach = tf(ig)
-        dom = prof["dominant"]
-        dom_tf = tf(dom)
-        # the class mixes split-bf16 launches (>= 128-channel layers) and native fp32-MFMA launches: its matrix roofline is
-        # the flop-weighted harmonic blend of the two peaks (time at peak = flops_split / peak_split + flops_f32 / peak_f32)
-        # time at peak = flops_f16 / peak_f16split + flops_bf16 / peak_bf16split + flops_fp32 / peak_fp32
-        blend = lambda q: 1.0 / ((q["flops_split_f16"] / q["flops"]) / SPLIT_F16_PEAK_TFLOPS + (q["flops_split_bf16"] / q["flops"]) / SPLIT_BF16_PEAK_TFLOPS
-                                 + (1.0 - (q["flops_split_bf16"] + q["flops_split_f16"]) / q["flops"]) / FP32_MFMA_PEAK_TFLOPS) if q["flops"] > 0 else FP32_MFMA_PEAK_TFLOPS
-        f_split = ig["flops_split_bf16"] / ig["flops"] if ig["flops"] > 0 else 0.0
-        f_f16 = ig["flops_split_f16"] / ig["flops"] if ig["flops"] > 0 else 0.0
-        f16_mode = ops.mfma_mode() == "split_f16"
-        dom_peak = SPLIT_F16_PEAK_TFLOPS if f16_mode else SPLIT_BF16_PEAK_TFLOPS
-        peak = blend(ig)
         imgs = B * world * args.steps
         workload = ("BASELINE configs[2]: full minibatch step of train_nn_area.py:212-287 — Phase A (UNet eval fwd, TopKCER k = 5 % of the "
                     f"minibatch, inner_limit = {R} jitter replicas fused in the batch dim, CRNN train-BN fwd+bwd, Adam(CRNN)) + Phase B (UNet "
@@ -553,7 +582,7 @@ def main():
             "dtype": {"f32": "f32", "split_bf16": "f32 (GEMMs as 3 x bf16 split products, fp32 accumulate)",
                       "split_f16": "f32 (GEMMs as scaled 2 x fp16 split products — three fp16 MFMAs per fp32 multiply-add — fp32 accumulate)"}[ops.mfma_mode()],
             "data": "synthetic",
-            "overlap": {"wgrad_side_stream": overlap0, "ms_per_step_single_stream": dt_serial / args.steps * 1e3},
+            "overlap": {"wgrad_side_stream": overlap0},
             "config": {"workload": workload, "batch_per_gpu": B, "global_batch": B * world, "full_step": not args.phase_b_only,
                        "phase_a": None if args.phase_b_only else {
                            "selection": "topKCER", "minibatch_subset_prop": 0.95, "k_global": W.k_global, "inner_limit": R,
@@ -565,48 +594,65 @@ def main():
                        "small_collectives_per_step": 0 if (world == 1 or args.phase_b_only) else "CER all-gather (4 B per strip) + winner re-balance (k x 16 KB)",
                        "data_parallel": dp_report,
                        "loss": float(loss.item()), "hipgraph": bool(args.graph)},
-            "phase_b": None if (args.no_phase_b_leg and not args.phase_b_only) else {"value": imgs / dt_b, "unit": "patch-images/s", "ms_per_step": dt_b / args.steps * 1e3,
+            "phase_b": None if (args.no_phase_b_leg or not full) and not args.phase_b_only else {"value": imgs / dt_b, "unit": "patch-images/s", "ms_per_step": dt_b / args.steps * 1e3,
                         "end_to_end_tflops": FLOP_PER_IMG_FAITHFUL * imgs / dt_b / 1e12 if not args.skip_crnn_wgrad else None,
                         "note": "Phase B alone at the same batch: 9.846 GFLOP per image (SURVEY.md §8d unit of work)"},
-            "roofline": {"bound": "mfma",
-                         "kernel": (DOMINANT_KERNEL if f16_mode else DOMINANT_KERNEL_BF16) + " — the LDS-halo 3x3 convolution (conv_igemm.hip): fp32 "
-                                   "operands scaled by the power of two of their abs-max and split into 2 fp16 planes (input halo split once per tile "
-                                   "in LDS, filter fragments pre-split), three v_mfma_f32_32x32x16_f16 per product, fp32 accumulate [split_bf16 mode: "
-                                   "3 bf16 planes, six MFMAs]; forward and input gradient of every 3x3 layer with >= 64 input and >= 128 output "
-                                   "channels and W % 32 == 0",
-                         "achieved": dom_tf, "peak": dom_peak, "unit": "TFLOP/s", "frac": dom_tf / dom_peak,
-                         "frac_of_the_six_mfma_peak": dom_tf / SPLIT_BF16_PEAK_TFLOPS,
-                         "avg_launch_us": dom["ms"] * 1e3 / max(1, dom["launches"]), "launches_per_step": dom["launches"] / args.steps,
-                         "ms_per_step_in_kernel": dom["ms"] / args.steps, "share_of_step": dom["ms"] / args.steps / (dt_serial / args.steps * 1e3),
-                         "algorithmic_flops_per_launch": dom["flops"] / max(1, dom["launches"]),
-                         "algorithmic_bytes_per_launch": dom["bytes"] / max(1, dom["launches"]),
-                         "traffic": traffic_dom, "traffic_note": traffic_note, "source_hash": source_hash(),
-                         "measured": "HIP events around every launch of this kernel over the same K steps re-run with the wgrad side stream "
-                                     f"disabled ({dt_serial / args.steps * 1e3:.2f} ms/step single-stream vs {dt / args.steps * 1e3:.2f} overlapped); "
-                                     "avg_launch_us is comparable with profiles/r03_kernel_stats_b2048_single_stream.csv",
-                         "peak_is": (f"fp16 dense MFMA peak / 3 = {SPLIT_F16_PEAK_TFLOPS:.1f} TFLOP/s fp32-equivalent (three MFMAs per product); rounds 1-2 priced "
-                                     f"the six-MFMA bf16 form against {SPLIT_BF16_PEAK_TFLOPS:.1f} (frac_of_the_six_mfma_peak)") if f16_mode else
-                                    f"bf16 dense MFMA peak / 6 = {SPLIT_BF16_PEAK_TFLOPS:.1f} TFLOP/s fp32-equivalent",
-                         "launch_class": {
-                             "what": "all qea_conv_igemm launches (implicit-GEMM conv fwd/dgrad, convT, LSTM/linear GEMMs): the LDS-halo kernel above, "
-                                     "conv_igemm_bf3w_kernel (other >= 128-channel GEMMs: pre-split filter planes by LDS-DMA), and the native "
-                                     "v_mfma_f32_32x32x2_f32 kernels conv_igemm_kernel / conv3x3_halo_kernel",
-                             "achieved": ach, "peak": peak, "frac": ach / peak, "traffic": traffic,
-                             "algorithmic_bytes_per_launch": ig["bytes"] / max(1, ig["launches"]), "launches_per_step": ig["launches"] / args.steps,
-                             "ms_per_step_in_kernel": ig["ms"] / args.steps, "split_bf16_flop_fraction": f_split, "split_f16_flop_fraction": f_f16,
-                             "frac_of_native_fp32_mfma_peak": ach / FP32_MFMA_PEAK_TFLOPS,
-                             "peak_note": f"fp32-equivalent; flop-weighted blend of fp16 dense peak / 3 = {SPLIT_F16_PEAK_TFLOPS:.1f} ({100 * f_f16:.0f} % of the "
-                                          f"class's flops), bf16 dense peak / 6 = {SPLIT_BF16_PEAK_TFLOPS:.1f} ({100 * f_split:.0f} %) and the fp32 MFMA peak "
-                                          f"{FP32_MFMA_PEAK_TFLOPS}"}},
-            "kernels": {
+        }
+        if full:
+            ig, wg, ls = prof[ops.PROF_CONV_IGEMM], prof[ops.PROF_CONV_WGRAD], prof[ops.PROF_LSTM_STEP]
+            tf = lambda q: q["flops"] / (q["ms"] * 1e-3) / 1e12 if q["ms"] > 0 else 0.0
+            ach = tf(ig)
+            dom = prof["dominant"]
+            dom_tf = tf(dom)
+            # the class mixes split-bf16 launches (>= 128-channel layers) and native fp32-MFMA launches: its matrix roofline is
+            # the flop-weighted harmonic blend of the two peaks (time at peak = flops_split / peak_split + flops_f32 / peak_f32)
+            # time at peak = flops_f16 / peak_f16split + flops_bf16 / peak_bf16split + flops_fp32 / peak_fp32
+            blend = lambda q: 1.0 / ((q["flops_split_f16"] / q["flops"]) / SPLIT_F16_PEAK_TFLOPS + (q["flops_split_bf16"] / q["flops"]) / SPLIT_BF16_PEAK_TFLOPS
+                                     + (1.0 - (q["flops_split_bf16"] + q["flops_split_f16"]) / q["flops"]) / FP32_MFMA_PEAK_TFLOPS) if q["flops"] > 0 else FP32_MFMA_PEAK_TFLOPS
+            f_split = ig["flops_split_bf16"] / ig["flops"] if ig["flops"] > 0 else 0.0
+            f_f16 = ig["flops_split_f16"] / ig["flops"] if ig["flops"] > 0 else 0.0
+            f16_mode = ops.mfma_mode() == "split_f16"
+            dom_peak = SPLIT_F16_PEAK_TFLOPS if f16_mode else SPLIT_BF16_PEAK_TFLOPS
+            peak = blend(ig)
+            out["overlap"]["ms_per_step_single_stream"] = dt_serial / args.steps * 1e3
+            out["roofline"] = {"bound": "mfma",
+                               "kernel": (DOMINANT_KERNEL if f16_mode else DOMINANT_KERNEL_BF16) + " — the LDS-halo 3x3 convolution (conv_igemm.hip): fp32 "
+                                         "operands scaled by the power of two of their abs-max and split into 2 fp16 planes (input halo split once per tile "
+                                         "in LDS, filter fragments pre-split), three v_mfma_f32_32x32x16_f16 per product, fp32 accumulate [split_bf16 mode: "
+                                         "3 bf16 planes, six MFMAs]; forward and input gradient of every 3x3 layer with >= 64 input and >= 128 output "
+                                         "channels and W % 32 == 0",
+                               "achieved": dom_tf, "peak": dom_peak, "unit": "TFLOP/s", "frac": dom_tf / dom_peak,
+                               "frac_of_the_six_mfma_peak": dom_tf / SPLIT_BF16_PEAK_TFLOPS,
+                               "avg_launch_us": dom["ms"] * 1e3 / max(1, dom["launches"]), "launches_per_step": dom["launches"] / args.steps,
+                               "ms_per_step_in_kernel": dom["ms"] / args.steps, "share_of_step": dom["ms"] / args.steps / (dt_serial / args.steps * 1e3),
+                               "algorithmic_flops_per_launch": dom["flops"] / max(1, dom["launches"]),
+                               "algorithmic_bytes_per_launch": dom["bytes"] / max(1, dom["launches"]),
+                               "traffic": traffic_dom, "traffic_note": traffic_note, "source_hash": source_hash(),
+                               "measured": "HIP events around every launch of this kernel over the same K steps re-run with the wgrad side stream "
+                                           f"disabled ({dt_serial / args.steps * 1e3:.2f} ms/step single-stream vs {dt / args.steps * 1e3:.2f} overlapped); "
+                                           "avg_launch_us is comparable with profiles/r03_kernel_stats_b2048_single_stream.csv",
+                               "peak_is": (f"fp16 dense MFMA peak / 3 = {SPLIT_F16_PEAK_TFLOPS:.1f} TFLOP/s fp32-equivalent (three MFMAs per product); rounds 1-2 priced "
+                                           f"the six-MFMA bf16 form against {SPLIT_BF16_PEAK_TFLOPS:.1f} (frac_of_the_six_mfma_peak)") if f16_mode else
+                                          f"bf16 dense MFMA peak / 6 = {SPLIT_BF16_PEAK_TFLOPS:.1f} TFLOP/s fp32-equivalent",
+                               "launch_class": {
+                                   "what": "all qea_conv_igemm launches (implicit-GEMM conv fwd/dgrad, convT, LSTM/linear GEMMs): the LDS-halo kernel above, "
+                                           "conv_igemm_bf3w_kernel (other >= 128-channel GEMMs: pre-split filter planes by LDS-DMA), and the native "
+                                           "v_mfma_f32_32x32x2_f32 kernels conv_igemm_kernel / conv3x3_halo_kernel",
+                                   "achieved": ach, "peak": peak, "frac": ach / peak, "traffic": traffic,
+                                   "algorithmic_bytes_per_launch": ig["bytes"] / max(1, ig["launches"]), "launches_per_step": ig["launches"] / args.steps,
+                                   "ms_per_step_in_kernel": ig["ms"] / args.steps, "split_bf16_flop_fraction": f_split, "split_f16_flop_fraction": f_f16,
+                                   "frac_of_native_fp32_mfma_peak": ach / FP32_MFMA_PEAK_TFLOPS,
+                                   "peak_note": f"fp32-equivalent; flop-weighted blend of fp16 dense peak / 3 = {SPLIT_F16_PEAK_TFLOPS:.1f} ({100 * f_f16:.0f} % of the "
+                                                f"class's flops), bf16 dense peak / 6 = {SPLIT_BF16_PEAK_TFLOPS:.1f} ({100 * f_split:.0f} %) and the fp32 MFMA peak "
+                                                f"{FP32_MFMA_PEAK_TFLOPS}"}}
+            out["kernels"] = {
                 "conv_wgrad": {"tflops": tf(wg), "ms_per_step": wg["ms"] / args.steps, "peak": blend(wg), "frac": tf(wg) / blend(wg),
                                "split_bf16_flop_fraction": wg["flops_split_bf16"] / wg["flops"] if wg["flops"] > 0 else 0.0,
                                "split_f16_flop_fraction": wg["flops_split_f16"] / wg["flops"] if wg["flops"] > 0 else 0.0,
                                "algorithmic_bytes_per_launch": wg["bytes"] / max(1, wg["launches"]),
                                "launches_per_step": wg["launches"] / args.steps},
                 "lstm_step": {"tflops": tf(ls), "ms_per_step": ls["ms"] / args.steps, "launches_per_step": ls["launches"] / args.steps},
-            },
-        }
+            }
         if native is not None:
             nprof, ndt, nsteps = native
             nig, nwg = nprof[ops.PROF_CONV_IGEMM], nprof[ops.PROF_CONV_WGRAD]
@@ -629,9 +675,9 @@ def main():
             out["full_step_select_before_clean"] = sel_first
         if c1 is not None:
             out["configs1_b512"] = c1
-        if world == 1 and not use_dist and not args.no_secondary and not args.phase_b_only and not args.graph and B >= 512:
+        if world == 1 and not use_dist and secondary and not args.phase_b_only and not args.graph and B >= 512:
             out["small_batch"] = small_batch_legs()          # (child processes of this bench: not under torch.distributed.run)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         sys.stdout.flush()
         os.dup2(stdout_fd, 1)

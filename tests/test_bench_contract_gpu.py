@@ -4,19 +4,23 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_prints_one_json_line_with_the_contract_fields():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "64", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-secondary"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+def _bench(*args):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines[:3]
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_bench_prints_one_json_line_with_the_contract_fields():
+    d = _bench("--batch", "64", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline"):
         assert k in d, k
@@ -28,3 +32,33 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert r["bound"] == "mfma" and r["unit"] == "TFLOP/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
     assert r["traffic"] is None                      # the committed PMC profile is for B = 2048: refused for another workload
     assert abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+
+
+def test_plain_bench_times_the_steps_only_and_dumps_the_last_step(tmp_path):
+    """Without --full: the headline fields and none of the secondary legs.  --dump-outputs: the last timed step's outputs as float32 /
+    float64 .npy files (64 MB at most), the same in two runs with the same arguments (seeded inputs and weights)."""
+    names = ("loss", "log_probs", "cleaned", "unet_params", "crnn_params", "cer")
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        d = _bench("--batch", "64", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True
+        assert abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for k in ("roofline", "kernels", "cpu_baseline", "small_batch", "configs1_b512", "full_step_without_cer_update",
+                  "full_step_select_before_clean"):
+            assert k not in d, k
+        assert d["phase_b"] is None and "ms_per_step_single_stream" not in d["overlap"]
+        assert sorted(os.listdir(out)) == sorted(f"{n}.npy" for n in names)
+        a = {n: np.load(out / f"{n}.npy") for n in names}
+        assert sum(v.nbytes for v in a.values()) <= 64 << 20
+        for n, v in a.items():
+            assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), n
+        assert a["log_probs"].shape == (31, 64, 95) and a["cleaned"].shape == (64, 1, 32, 128) and a["cer"].shape == (64,)
+        assert abs(float(a["loss"]) - d["config"]["loss"]) <= 1e-6 * abs(d["config"]["loss"])
+        runs.append(a)
+    a, b = runs
+    for n in names[:-1]:
+        assert np.abs(a[n].astype(np.float64) - b[n]).max() <= 1e-3 * np.abs(a[n]).max() + 1e-6, n
+    assert (a["cer"] != b["cer"]).mean() <= 0.05        # discrete: a near-tie in the greedy decode may go the other way

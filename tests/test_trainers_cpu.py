@@ -22,6 +22,14 @@ def oracle_backend():
     return Backend(OracleUNet, OracleCRNN, torch.nn.CTCLoss, torch.optim.Adam, torch.device("cpu"), gpu_jitter=False)
 
 
+@pytest.fixture
+def float64_default():
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    yield
+    torch.set_default_dtype(prev)
+
+
 def _args(which, tmp, **over):
     from qea.cli_flags import build_parser
     a = build_parser(which, "").parse_args(["--exp_base_path", str(tmp), "--ocr", "stub", "--epoch", "1", "--inner_limit", "1"])
@@ -112,11 +120,13 @@ def test_patch_trainer_plumbing(tmp_path):
     assert ocr.count_calls > 0
 
 
-def test_patch_trainer_docs_per_step_equals_the_sequential_loop(tmp_path, monkeypatch):
+def test_patch_trainer_docs_per_step_equals_the_sequential_loop(tmp_path, monkeypatch, float64_default):
     """[new] --docs_per_step N (SURVEY §8 f2 "multi-document batching"): Phase B runs the N documents through the cleaner as one
     batch with per-document BatchNorm statistics and all their strips through the CRNN as one batch, sums the N per-document
     losses and back-propagates once.  Against the reference's loop written out (train_nn_patch.py:318-329: per document forward,
-    loss, backward — gradients accumulate) on the same models: the gradient Adam(UNet) consumes and the UNet's running statistics."""
+    loss, backward — gradients accumulate) on the same models: the gradient Adam(UNet) consumes and the UNet's running statistics.
+    Both sides run in fp64: in fp32 the two orders of work round apart wherever the BLAS blocks a GEMM by its batch shape (MKL's
+    AVX2 path: 5e-5 on the upconv biases, sums that cancel heavily), which says nothing about the batching itself."""
     import torch.nn.functional as F
     from datasets.synthetic import SyntheticPatches
     from ocr_helper.stub_helper import StubHelper
