@@ -1,0 +1,169 @@
+"""Preprocessor evaluation — MI355X-native drop-in for the reference's eval_prep.py.
+
+`EvalPrep(args).eval()` with the reference's flags (qea/cli_flags.py tag "v"):
+  * --dataset vgg: batches of test strips -> eval-mode UNet (BatchNorm folded into the conv epilogue) -> the OCR engine on the
+    cleaned strips -> exact-match count and CER against the ground truth;
+  * --dataset patch_dataset / wildreceipt: each document [1,1,400,512] -> eval-mode UNet -> word strips cut on the device
+    (utils.get_text_stack) -> the OCR engine (documents are padded, never resized: PatchDataset(pad=True, resize_images=False));
+    for wildreceipt the spaces are stripped from the OCR's labels;
+  * --show_orig also runs the OCR on the uncleaned strips.
+Returns (accuracy, cer) of the cleaned strips, as the reference's patch flow does.  Differences, all deliberate:
+  * [new] the area flow returns the same pair (the reference returns None).
+  * The area flow's --show_orig: the reference adds to `ori_lbl_cer` before assigning it and divides the original strips' CER
+    twice (by the batch, then by the set); here it is summed over the strips and divided once by the set size.
+  * A document whose size is not a multiple of 16 raises the UNet's ValueError with the file's name added (the reference fails
+    on it too); it is not padded silently.
+  * [new] --synthetic_size N evaluates on N synthetic strips / documents (datasets/synthetic.py).
+  * The loaders run in the main process (the reference asks for properties.num_workers workers).
+`backend` / `dataset` / `ocr` are injection seams for tests, as in the trainers; the default backend is the HIP path.
+"""
+import os
+
+import torch
+
+import properties
+from qea.trainer_core import hip_backend
+from utils import compare_labels, get_ocr_helper, get_text_stack, show_img
+
+
+class EvalPrep:
+    def __init__(self, args, backend=None, dataset=None, ocr=None):
+        self.batch_size = args.batch_size
+        self.show_txt = args.show_txt
+        self.show_img = args.show_img
+        self.prep_model_path = args.prep_path
+        self.ocr_name = args.ocr
+        self.dataset_name = args.dataset
+        self.show_orig = args.show_orig
+        self.input_size = properties.input_size
+        if self.dataset_name == "vgg":
+            self.test_set = os.path.join(args.data_base_path, properties.vgg_text_dataset_test)
+        elif self.dataset_name == "patch_dataset":
+            self.test_set = os.path.join(args.data_base_path, properties.patch_dataset_test)
+        elif self.dataset_name == "wildreceipt":
+            self.test_set = os.path.join(args.data_base_path, properties.wr_dataset_test)
+        else:
+            raise ValueError(f"--dataset {self.dataset_name!r}: one of patch_dataset, vgg, wildreceipt")
+
+        self.device = (backend or hip_backend()).device
+        self.prep_model = torch.load(self.prep_model_path, map_location=self.device, weights_only=False).to(self.device)
+        self.ocr = ocr if ocr is not None else get_ocr_helper(self.ocr_name, is_eval=True)
+
+        n = getattr(args, "synthetic_size", None)
+        if dataset is None and n:
+            from datasets.synthetic import SyntheticPatches, SyntheticTextAreas
+            dataset = SyntheticTextAreas(n, seed=3, include_name=True) if self.dataset_name == "vgg" else SyntheticPatches(n, seed=3)
+        elif dataset is None and self.dataset_name in ("patch_dataset", "wildreceipt"):
+            from datasets.patch_dataset import PatchDataset
+            dataset = PatchDataset(self.test_set, pad=True, include_name=True, resize_images=False)
+        elif dataset is None:
+            from datasets._io import to_tensor
+            from datasets.img_dataset import ImgDataset
+            from transform_helper import PadWhite
+            dataset = ImgDataset(self.test_set, transform=lambda img: to_tensor(PadWhite(self.input_size)(img)), include_name=True)
+        self.dataset = dataset
+        if self.dataset_name == "vgg":
+            self.loader_eval = torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size)
+
+    def _print_labels(self, labels, pred, ori):
+        print()
+        print("{:<25}{:<25}{:<25}".format("GT Label", "Label for pred", "Label for original"))
+        for i in range(len(labels)):
+            print("{:<25}{:<25}{:<25}".format(labels[i], pred[i] if i < len(pred) else "*******", ori[i] if i < len(ori) else ""))
+
+    def _ocr(self, crops):
+        labels = self.ocr.get_labels(crops.cpu())
+        if self.dataset_name == "wildreceipt":
+            labels = [lbl.replace(" ", "") for lbl in labels]
+        return labels
+
+    def eval_area(self):
+        print("Eval with ", self.ocr_name)
+        self.prep_model.eval()
+        pred_correct_count, ori_correct_count, ori_cer, pred_cer = 0, 0, 0.0, 0.0
+        with torch.no_grad():
+            for batch in self.loader_eval:
+                images, labels = batch[0], list(batch[1])
+                img_preds = self.prep_model(images.to(self.device))
+                ocr_lbl_pred = self.ocr.get_labels(img_preds.cpu())
+                ocr_lbl_ori = []
+                if self.show_orig:
+                    ocr_lbl_ori = self.ocr.get_labels(images.cpu())
+                    c, e = compare_labels(ocr_lbl_ori, labels)
+                    ori_correct_count += c
+                    ori_cer += e
+                c, e = compare_labels(ocr_lbl_pred, labels)
+                pred_correct_count += c
+                pred_cer += e
+                if self.show_img:
+                    show_img(img_preds.detach().cpu(), "Processed images")
+                if self.show_txt:
+                    self._print_labels(labels, ocr_lbl_pred, ocr_lbl_ori)
+        n = len(self.dataset)
+        print()
+        print("Correct count from predicted images: {:d}/{:d} ({:.5f})".format(pred_correct_count, n, pred_correct_count / n))
+        if self.show_orig:
+            print("Correct count from original images: {:d}/{:d} ({:.5f})".format(ori_correct_count, n, ori_correct_count / n))
+            print("Average CER from original images: {:.5f}".format(ori_cer / n))
+        print("Average CER from predicted images: {:.5f}".format(pred_cer / n))
+        self.orig_result = (ori_correct_count / n, ori_cer / n) if self.show_orig else None
+        return pred_correct_count / n, pred_cer / n
+
+    def eval_patch(self):
+        print("Eval with ", self.ocr_name)
+        self.prep_model.eval()
+        ori_lbl_crt_count, ori_lbl_cer, prd_lbl_crt_count, prd_lbl_cer, lbl_count = 0, 0.0, 0, 0.0, 0
+        with torch.no_grad():
+            for i in range(len(self.dataset)):
+                item = self.dataset[i]
+                image, labels_dict = item[0], item[1]
+                name = item[2] if len(item) > 2 else f"document {i}"
+                image = image.detach().to(self.device)
+                ocr_labels = []
+                if self.show_orig:
+                    text_crops, labels = get_text_stack(image, labels_dict, self.input_size)
+                    ocr_labels = self._ocr(text_crops)
+                    c, e = compare_labels(ocr_labels, labels)
+                    ori_lbl_crt_count += c
+                    ori_lbl_cer += e
+                try:
+                    pred = self.prep_model(image.unsqueeze(0))[0]
+                except ValueError as err:
+                    raise ValueError(f"{name}: {err}") from err
+                pred_crops, labels = get_text_stack(pred, labels_dict, self.input_size)
+                lbl_count += len(labels)
+                pred_labels = self._ocr(pred_crops)
+                c, e = compare_labels(pred_labels, labels)
+                prd_lbl_crt_count += c
+                prd_lbl_cer += e
+                if self.show_img:
+                    show_img(image.cpu())
+                if self.show_txt:
+                    self._print_labels(labels, pred_labels, ocr_labels)
+                if not i % 100:
+                    print(f"{i} samples completed")
+        print()
+        print("Correct count from predicted images: {:d}/{:d} ({:.5f})".format(prd_lbl_crt_count, lbl_count, prd_lbl_crt_count / lbl_count))
+        if self.show_orig:
+            print("Correct count from original images: {:d}/{:d} ({:.5f})".format(ori_lbl_crt_count, lbl_count, ori_lbl_crt_count / lbl_count))
+            print("Average CER from original images: ({:.5f})".format(ori_lbl_cer / lbl_count))
+        print("Average CER from predicted images: ({:.5f})".format(prd_lbl_cer / lbl_count))
+        self.orig_result = (ori_lbl_crt_count / lbl_count, ori_lbl_cer / lbl_count) if self.show_orig else None
+        return prd_lbl_crt_count / lbl_count, prd_lbl_cer / lbl_count
+
+    def eval(self):
+        if self.dataset_name in ("patch_dataset", "wildreceipt"):
+            return self.eval_patch()
+        return self.eval_area()
+
+
+def build_parser():
+    from qea.cli_flags import build_parser as _build
+    return _build("v", "Evaluates a trained preprocessor")
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
+    print(args)
+    evaluator = EvalPrep(args)
+    evaluator.eval()

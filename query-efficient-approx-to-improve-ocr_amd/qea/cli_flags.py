@@ -1,6 +1,8 @@
 """The reference's command-line surface, as data.  Names, defaults, types, choices and the
 `store_false` quirk of --random_std are those of patch_cli.py:11-155 and area_cli.py:11-124
-(SURVEY.md §5.6); the MI355X build only ADDS flags (marked new)."""
+(SURVEY.md §5.6), and of train_crnn.py:217-275, eval_crnn.py and eval_prep.py (tags "c", "e", "v"); the MI355X
+build only ADDS flags (marked new)."""
+import properties as _properties
 
 SUBSETS = ["random", "uniformCER", "uniformCERglobal", "randomglobal", "rangeCER", "uniformEntropy", "topKCER"]
 WEIGHTGEN = ["levenshtein", "self_attention", "decaying"]
@@ -63,6 +65,41 @@ FLAGS = [
     ("--no_rebalance_topk", dict(action="store_true", help="[new] data-parallel runs only: process every global TopKCER winner on the rank "
                                                            "that owns it instead of dealing the winners out in equal slices (one all-reduce of "
                                                            "k x 16 KB images); always so with --inner_limit_skip (label histories stay with the owner)"), "a"),
+]
+
+# the warm-up and evaluation drivers: "c" = train_crnn.py (:217-275), "e" = eval_crnn.py, "v" = eval_prep.py (their __main__ blocks).
+# Kept apart from the trainers' entries above, whose defaults and help differ for several shared names (--ocr, --batch_size, ...).
+FLAGS += [
+    ("--batch_size", dict(type=int, default=32, help="input batch size"), "c"),
+    ("--batch_size", dict(type=int, default=64, help="Inference batch size"), "ev"),
+    ("--lr", dict(type=float, default=0.0001, help="learning rate, not used by adadealta"), "c"),
+    ("--epoch", dict(type=int, default=50, help="number of epochs"), "c"),
+    ("--std", dict(type=int, default=5, help="standard deviation of Gussian noice added to images (this value devided by 100)"), "c"),
+    ("--random_seed", dict(type=int, default=42, help="random seed for shuffles"), "c"),
+    ("--ocr", dict(help="performs training lebels from given OCR [Tesseract,EasyOCR,stub]"), "c"),
+    ("--ocr", dict(default="Tesseract", help="performs training lebels from given OCR [Tesseract,EasyOCR,stub]"), "ev"),
+    ("--train_subset", dict(type=int, help="Specify subset of training samples"), "c"),
+    ("--val_subset", dict(type=int, help="Specify subset of validation samples"), "c"),
+    ("--dataset", dict(default="pos", help="performs training with given dataset [pos, vgg]"), "c"),
+    ("--dataset", dict(default="pos", help="evaluates on the given dataset [pos, vgg, pos_textarea]"), "e"),
+    ("--dataset", dict(default="patch_dataset", help="evaluates on the given dataset [patch_dataset, vgg, wildreceipt]"), "v"),
+    ("--random_std", dict(action="store_false", default=True,
+                          help="randomly selected integers from 0 upto given std value (devided by 100) will be used"), "c"),
+    ("--crnn_model_path", dict(default=_properties.crnn_model_path, help="CRNN model save path. Default picked from properties"), "c"),
+    ("--data_base_path", dict(default=".", help="Base path training, validation and test data"), "cev"),
+    ("--ckpt_path", dict(help="Path to CRNN checkpoint"), "c"),
+    ("--start_epoch", dict(type=int, default=-1, help="Starting epoch. If loading from a ckpt, pass the ckpt epoch here."), "c"),
+    ("--show_txt", dict(action="store_true", help="prints predictions and groud truth"), "ev"),
+    ("--show_img", dict(action="store_true", help="shows each batch of images"), "ev"),
+    ("--crnn_path", dict(default=_properties.crnn_model_path, help="specify non-default CRNN model location"), "e"),
+    ("--crnn_model_name", dict(default="prep_tesseract_pos", help="CRNN model name"), "e"),
+    ("--prep_path", dict(default=_properties.prep_model_path, help="specify non-default prep model location"), "v"),
+    ("--show_orig", dict(action="store_true", help="Show original flow evaluation"), "ev"),
+    # ---- new (additive) ----
+    ("--synthetic_size", dict(type=int, help="[new] use N synthetic samples (datasets/synthetic.py) instead of reading --data_base_path"), "cev"),
+    ("--graph", dict(action="store_true", help="[new] replay the warm-up step (CRNN -> CTC -> backward -> Adam) as ONE hipGraph per (batch size, "
+                                               "width, target-length cap, lr); the first two steps of a shape run eagerly, single-process runs only"),
+     "c"),
 ]
 
 

@@ -1,5 +1,5 @@
 """Helpers of the training loop — drop-in for the hot subset of the reference's utils.py
-(get_char_maps :22-40, pred_to_string :74-92, compare_labels :95-110, set_bn_eval :113-115,
+(get_char_maps :22-40, show_img :49-54, pred_to_string :74-92, compare_labels :95-110, set_bn_eval :113-115,
 padder / get_text_stack :118-141, get_ocr_helper :180-188, create_dirs :191-206, save_json /
 save_all_jsons :209-231, handle_optuna_trial :233-237, set_random_seeds :240-243).
 
@@ -230,6 +230,24 @@ def save_img(images, name, dir, nrow=8):
         r, c = divmod(i, cols)
         grid[pad + r * (h + pad): pad + r * (h + pad) + h, pad + c * (w + pad): pad + c * (w + pad) + w] = imgs[i, 0]
     Image.fromarray((grid.numpy() * 255).round().astype(np.uint8)).save(os.path.join(dir, name + ".png"), "PNG")
+
+
+def show_img(images, title="Figure", nrow=8):
+    """Shows a grid of [N,1,H,W] images (reference :49-54; the eval drivers' --show_img).  matplotlib is imported only here."""
+    import matplotlib.pyplot as plt
+    imgs = images.detach().cpu().float().clamp(0, 1)
+    if imgs.dim() == 3:
+        imgs = imgs[None]
+    n, _, h, w = imgs.shape
+    cols = min(nrow, n)
+    rows = (n + cols - 1) // cols
+    grid = torch.zeros(rows * (h + 2) + 2, cols * (w + 2) + 2)
+    for i in range(n):
+        r, c = divmod(i, cols)
+        grid[2 + r * (h + 2): 2 + r * (h + 2) + h, 2 + c * (w + 2): 2 + c * (w + 2) + w] = imgs[i, 0]
+    plt.figure(num=title)
+    plt.imshow(grid.numpy(), cmap="gray")
+    plt.show()
 
 
 def handle_optuna_trial(trial, accuracy, epoch):
