@@ -489,6 +489,25 @@ int qea_greedy_decode(const float* scores, int32_t ld_t, int32_t ld_n, int32_t T
 int qea_edit_distance(const int32_t* pred_tokens, int32_t ldp, const int32_t* pred_len, const int32_t* gt_tokens,
                       const int64_t* gt_offsets, const int32_t* gt_len, int32_t N, int32_t* out, void* stream);
 
+/* Dataset pruning: greedy facility-location selection (pruning/methods.py:12-23, apricot's FacilityLocationSelection with
+ * optimizer='naive' on squared-euclidean similarities) over n feature rows x[n][d] of fp64, 1 <= d <= 32, 1 <= k <= n:
+ *   S[i][j] = M - sum_dd (x[i][dd] - x[j][dd])^2 (terms added in ascending dd), M = the largest squared distance of any pair;
+ *   cur[j] = 0; pick t takes the unpicked i with the largest gain[i] = sum_j max(S[i][j], cur[j]) (the LOWEST index on an exact
+ *   tie), then cur[j] = max(cur[j], S[i][j]).
+ * ranking_out[t] receives the index and gain_out[t] (may be NULL) the gain of pick t.  S is recomputed from x for every pick (no
+ * n x n buffer); the sum over j has one fixed order for every i, so rows with identical features tie exactly; the k picks (two
+ * launches each) and the computation of M are enqueued on `stream` without a host synchronisation.  `workspace`: 16-byte aligned,
+ * qea_facility_workspace_bytes(n, d) bytes (0 for sizes the call refuses), zeroed by the call itself.  Refused before any launch:
+ * NULL x / ranking_out / workspace, d outside 1..32, k outside 1..n.  Non-finite features (or squared distances that overflow) are
+ * found on the device: the picks then do nothing and ranking_out / gain_out stay unwritten; qea_facility_status — the ONE entry
+ * point here that synchronises `stream`, meant to follow the caller's own read-back of the ranking — reads the workspace's flag
+ * word and returns QEA_ERR_INVALID with the message.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects these three by symbol.) */
+size_t qea_facility_workspace_bytes(int32_t n, int32_t d);
+int qea_facility_select(const double* x, int32_t n, int32_t d, int32_t k, int32_t* ranking_out, double* gain_out, void* workspace,
+                        void* stream);
+int qea_facility_status(const void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

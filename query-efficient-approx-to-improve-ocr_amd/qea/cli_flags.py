@@ -1,6 +1,6 @@
 """The reference's command-line surface, as data.  Names, defaults, types, choices and the
 `store_false` quirk of --random_std are those of patch_cli.py:11-155 and area_cli.py:11-124
-(SURVEY.md §5.6), and of train_crnn.py:217-275, eval_crnn.py and eval_prep.py (tags "c", "e", "v"); the MI355X
+(SURVEY.md §5.6), and of train_crnn.py:217-275, eval_crnn.py and eval_prep.py (tags "c", "e", "v") and pruning/prune_dataset.py:88-106 (tag "r"); the MI355X
 build only ADDS flags (marked new)."""
 import properties as _properties
 
@@ -100,6 +100,21 @@ FLAGS += [
     ("--graph", dict(action="store_true", help="[new] replay the warm-up step (CRNN -> CTC -> backward -> Adam) as ONE hipGraph per (batch size, "
                                                "width, target-length cap, lr); the first two steps of a shape run eagerly, single-process runs only"),
      "c"),
+]
+
+# the dataset pruner: "r" = pruning/prune_dataset.py (its __main__ block, :88-106)
+FLAGS += [
+    ("--prune_method", dict(choices=["topk", "FL"], default="topk", help="Pruning method"), "r"),
+    ("--prune_prop", dict(type=int, default=10, help="Proportion of samples to be pruned"), "r"),
+    ("--dataset", dict(choices=["vgg", "pos"], help="Name of dataset to be pruned"), "r"),
+    ("--cers_tess_path", dict(required=True, help="Path to text strip cers information with respect to Tesseract"), "r"),
+    # ---- new (additive) ----
+    ("--backend", dict(choices=["hip", "cpu"], help="[new] where the FL selection runs: hip = the device kernel (qea_facility_select), cpu = the "
+                                                    "same definition in numpy fp64 (forms the n x n matrix); default: hip when a device is present"), "r"),
+    ("--features", dict(choices=["mean", "history"], default="mean",
+                        help="[new] FL feature of a document: mean = its mean CER (the reference); history = the means of its strips' CERs over "
+                             "the last --history_len epochs of a trainer's all_cers.json (name -> list of per-epoch CERs)"), "r"),
+    ("--history_len", dict(type=int, default=8, help="[new] --features history: epochs per feature row (1..32)"), "r"),
 ]
 
 

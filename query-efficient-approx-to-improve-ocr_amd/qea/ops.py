@@ -836,3 +836,23 @@ def prof_read_launches(klass, capacity=4096):
 def edit_distance(pred_tokens, ldp, pred_len, gt_tokens, gt_offsets, gt_len, N, out):
     _lib.check(_lib.lib().qea_edit_distance(_ptr(pred_tokens), ldp, _ptr(pred_len), _ptr(gt_tokens), _ptr(gt_offsets), _ptr(gt_len), N,
                                             _ptr(out), _stream()), "qea_edit_distance")
+
+
+def facility_select(x, k):
+    """Greedy facility-location ranking (include/qea_hip.h: qea_facility_select) of the rows of x [n][d] (CUDA, float64, 1 <= d <= 32):
+    returns (ranking [k] int32, gains [k] float64) as HOST tensors.  Raises QeaError for k > n, d out of range and non-finite rows."""
+    if x.dim() == 1:
+        x = x[:, None]
+    if not x.is_cuda or x.dtype != torch.float64 or x.dim() != 2:
+        raise _lib.QeaError("facility_select needs a CUDA float64 tensor [n][d] (there is no CPU path here: pruning.methods has one)")
+    x = x.contiguous()
+    n, d = x.shape
+    L = _lib.lib()
+    ranking = torch.empty(max(int(k), 1), dtype=torch.int32, device=x.device)
+    gains = torch.empty(max(int(k), 1), dtype=torch.float64, device=x.device)
+    nbytes = L.qea_facility_workspace_bytes(n, d)
+    ws = workspace(max(nbytes, 16), x.device)
+    _lib.check(L.qea_facility_select(_ptr(x), n, d, int(k), _ptr(ranking), _ptr(gains), ws.data_ptr(), _stream()), "qea_facility_select")
+    out = ranking.cpu(), gains.cpu()                     # the call's one synchronisation; the flag word is read behind it
+    _lib.check(L.qea_facility_status(ws.data_ptr(), _stream()), "qea_facility_select")
+    return out

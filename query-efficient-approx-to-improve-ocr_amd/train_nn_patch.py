@@ -20,7 +20,7 @@ from qea import dist as qdist
 from qea.trainer_core import TrainerCore
 from tracking_utils import add_labels_to_history, call_crnn, generate_ctc_target_batches, weighted_ctc_loss
 from transform_helper import AddGaussianNoice
-from utils import compare_labels, get_text_stack, handle_optuna_trial, pred_to_string, save_img
+from utils import compare_labels, get_pruning_sampler, get_text_stack, handle_optuna_trial, pred_to_string, save_img
 
 
 class TrainNNPrep(TrainerCore):
@@ -45,7 +45,11 @@ class TrainNNPrep(TrainerCore):
             self.train_subset_size = len(train_set)
         if not self.val_subset_size:
             self.val_subset_size = len(val_set)
-        idx = torch.randperm(len(train_set))[: self.train_subset_size]
+        if getattr(args, "pruning_artifact", None):
+            idx = get_pruning_sampler(train_set, args.pruning_artifact).indices      # the kept documents (train_nn_patch.py:119-120)
+        else:
+            idx = torch.randperm(len(train_set))[: self.train_subset_size]
+        print(f"Train Data Size - {len(train_set)}, Train Subset Size - {len(idx)}")
         idx = qdist.equal_shards(idx, self.batch_size)          # data parallel: the same number of steps on every rank
         self._train_idx = idx
         self._collate = collate

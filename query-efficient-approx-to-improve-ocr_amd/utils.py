@@ -258,6 +258,36 @@ def handle_optuna_trial(trial, accuracy, epoch):
             raise optuna.TrialPruned()
 
 
+def get_pruning_sampler(dataset, artifact_name):
+    """SubsetRandomSampler over the documents an artifact of pruning/prune_dataset.py names (reference :246-263): keys are
+    `<folder>_<file stem>` of the dataset's names.  The artifact is read from pruning/<cer_artifacts>/<name>.json below the working
+    directory, or fetched through wandb when a wandb run is active and enabled."""
+    from qea._lib import QeaError
+    wb = _wandb()
+    if wb is not None and not getattr(wb.run, "disabled", False) and "Disabled" not in type(getattr(wb.run, "mode", None)).__name__:
+        data = wb.run.use_artifact(f"{artifact_name}:latest")
+        cers_path = os.path.join(data.download(), f"{artifact_name}.json")
+    else:
+        cers_path = os.path.join("pruning", properties.cer_artifacts_path, f"{artifact_name}.json")
+    if not os.path.exists(cers_path):
+        raise QeaError(f"pruning artifact {cers_path} not found (write it with pruning/prune_dataset.py)")
+    with open(cers_path, "r") as f:
+        pruned_data_info = json.load(f)
+    names = getattr(dataset, "names", None) or getattr(dataset, "files", None)   # a dataset that lists its names spares loading every image
+    if names is None:
+        names = (dataset[i][-1] for i in range(len(dataset)))
+    indices = list()
+    for i, name in enumerate(names):
+        folder_name, file_name = name.split("/")[-2:]
+        file_name = file_name.split(".")[0]
+        if f"{folder_name}_{file_name}" in pruned_data_info:
+            indices.append(i)
+    if not indices:
+        raise QeaError(f"pruning artifact {cers_path} names none of the {len(dataset)} training documents "
+                       f"(keys look like {next(iter(pruned_data_info), None)!r})")
+    return torch.utils.data.SubsetRandomSampler(torch.tensor(indices))
+
+
 def set_random_seeds(random_seed):
     torch.manual_seed(random_seed)
     python_random.seed(random_seed)
