@@ -508,6 +508,40 @@ int qea_facility_select(const double* x, int32_t n, int32_t d, int32_t k, int32_
                         void* stream);
 int qea_facility_status(const void* workspace, void* stream);
 
+/* Label-history loss weights (--inner_limit_skip with --window_size > 1), the whole [n][W+1] table of one minibatch in ONE launch.
+ * Both calls write every element of `out` (fp32 [n][W+1]): column 0 is 1, columns 1..count[r] are the weights of strip r's
+ * remembered labels, most recent first, the rest are 0.  count[r] (clamped to 0..W) = remembered labels inside the window, 0 for
+ * a strip without history.  W <= QEA_HISTORY_MAX_WINDOW.  Nothing synchronises.
+ *
+ * qea_history_lev_weights — LevenshteinWeightGenerator.gen_weights (label_tracking/tracking_methods.py:63-101):
+ *   tokens [n][W][QEA_HISTORY_MAX_LEN] int32 Unicode code points (raw characters, no char_to_index), lens [n][W] (a length
+ *   outside 0..QEA_HISTORY_MAX_LEN is clamped, so nothing is read out of bounds: the caller routes longer words elsewhere);
+ *   out[r][i+1] = 0.5 * (1 - min(mean_i, c_i) / c_i), mean_i = (integer sum of the unit-cost edit distances of word i to the
+ *   other count-1 words) / max(count-1, 1), c_i = max(1, len_i), evaluated in fp64 and rounded once to fp32: bit-identical to the
+ *   reference's Python floats stored into a float32 tensor.  Each of the W(W-1)/2 distances is computed once.
+ *
+ * qea_history_attn_weights — AttentionWeightGenerator.gen_weights (label_tracking/tracking_methods.py:26-59) through
+ *   HistoryAttention.forward (models/model_attention.py:7-38), fp32:
+ *   char_idx [n][W][n_chars] int32 indices into `embedding` [V1][E] as tracking_utils.str_to_tensor builds them (pad index V1-1 for
+ *   missing characters and missing words; an index outside 0..V1-1 is read as V1-1); words = mean over the n_chars rows (always
+ *   / n_chars) + positional_encodings [W][E]; q = words Wq^T + wq_bias (wq_weight [Dq][E]); a = softmax_rows(q q^T / sqrt(Dq));
+ *   z = a coef_weight^T + coef_bias (coef_weight [W], coef_bias [1]); activation 0: sigmoid(z), 1: softmax of z over the W window
+ *   rows, 2: relu(z) / (sum relu(z) + 1e-6).  Strips with count 0 get [1, 0, ...] without evaluating the scorer.
+ *   (V1 + W) * Dq <= QEA_HISTORY_ATTN_MAX_TABLE, E a multiple of 4, all float pointers 16-byte aligned.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects these two by symbol.) */
+#define QEA_HISTORY_MAX_WINDOW 8
+#define QEA_HISTORY_MAX_LEN 128
+#define QEA_HISTORY_ATTN_MAX_TABLE 12288
+#define QEA_HISTORY_ACT_SIGMOID 0
+#define QEA_HISTORY_ACT_SOFTMAX 1
+#define QEA_HISTORY_ACT_RELU 2
+int qea_history_lev_weights(const int32_t* tokens, const int32_t* lens, const int32_t* count, int32_t n, int32_t W, float* out,
+                            void* stream);
+int qea_history_attn_weights(const int32_t* char_idx, const int32_t* count, int32_t n, int32_t W, int32_t n_chars,
+                             const float* embedding, int32_t V1, int32_t E, const float* wq_weight, const float* wq_bias, int32_t Dq,
+                             const float* coef_weight, const float* coef_bias, const float* positional_encodings, int32_t activation,
+                             float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

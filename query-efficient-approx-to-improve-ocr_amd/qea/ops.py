@@ -856,3 +856,27 @@ def facility_select(x, k):
     out = ranking.cpu(), gains.cpu()                     # the call's one synchronisation; the flag word is read behind it
     _lib.check(L.qea_facility_status(ws.data_ptr(), _stream()), "qea_facility_select")
     return out
+
+
+HISTORY_MAX_WINDOW, HISTORY_MAX_LEN, HISTORY_ATTN_MAX_TABLE = 8, 128, 12288      # QEA_HISTORY_* of include/qea_hip.h
+HISTORY_ACTIVATIONS = {"sigmoid": 0, "softmax": 1, "relu": 2}
+HISTORY_LAUNCHES = {"lev": 0, "attn": 0}     # launches of the two label-history kernels issued through this module (tests, tools)
+
+
+def history_lev_weights(tokens, lens, count, n, W, out):
+    """include/qea_hip.h: qea_history_lev_weights — tokens [n][W][128] / lens [n][W] / count [n] int32 -> out [n][W+1] fp32."""
+    _lib.check(_lib.lib().qea_history_lev_weights(_ptr(tokens), _ptr(lens), _ptr(count), n, W, _ptr(out), _stream()), "qea_history_lev_weights")
+    HISTORY_LAUNCHES["lev"] += 1
+
+
+def history_attn_weights(char_idx, count, n, W, n_chars, embedding, wq_weight, wq_bias, coef_weight, coef_bias, pos, activation, out):
+    """include/qea_hip.h: qea_history_attn_weights — char_idx [n][W][n_chars] / count [n] int32 and the HistoryAttention parameters
+    (contiguous fp32) -> out [n][W+1] fp32; `activation` is one of HISTORY_ACTIVATIONS."""
+    if activation not in HISTORY_ACTIVATIONS:
+        raise ValueError(f"unknown attn_activation {activation!r}")
+    V1, E = embedding.shape
+    Dq = wq_weight.shape[0]
+    _lib.check(_lib.lib().qea_history_attn_weights(_ptr(char_idx), _ptr(count), n, W, n_chars, _ptr(embedding), V1, E, _ptr(wq_weight),
+                                                   _ptr(wq_bias), Dq, _ptr(coef_weight), _ptr(coef_bias), _ptr(pos),
+                                                   HISTORY_ACTIVATIONS[activation], _ptr(out), _stream()), "qea_history_attn_weights")
+    HISTORY_LAUNCHES["attn"] += 1
