@@ -542,6 +542,30 @@ int qea_history_attn_weights(const int32_t* char_idx, const int32_t* count, int3
                              const float* coef_weight, const float* coef_bias, const float* positional_encodings, int32_t activation,
                              float* out, void* stream);
 
+/* Label-history weighted CTC loss (tracking_utils.py:59-75: weighted_ctc_loss) of one minibatch in one device pass: every strip n
+ * carries up to W problems, one per history depth i, that share the log-prob rows lp[:, n, :] (element (t,n,c) at
+ * t*ld_t + n*ld_n + c, as qea_ctc_loss).  input_lengths [N]; lens [N][W] int32, -1 = strip n has no label at depth i, 0 = a real,
+ * empty label; offs [N][W] int32 = start of that label in the concatenated int32 `chars`; depth_n [W] = strips present at depth i.
+ * weights element (n,i) at n*w_stride_n + i*w_stride_i (fp32): the sample-wise [N][W+1] table has strides (W+1, 1), the decaying
+ * [W] vector (0, 1).  With
+ *   coef[n,i] = w[n,i] / depth_n[i]                       mean_by_length = 0   (:69-73, mean(w * CTCLoss(reduction="none")) per depth)
+ *   coef[n,i] = w[n,i] / (depth_n[i] * max(len,1))        mean_by_length = 1   (:66-67, w[i] * CTCLoss() per depth)
+ * loss[0] = sum_{n,i present} coef * nll[n,i];  grad (may be NULL; element (t,n,c) at t*gld_t + n*gld_n + c)
+ *   = sum_i coef[n,i] * (exp(lp) - exp(lse_{s: l'_s = c}(alpha+beta) + nll - lp)), rows t >= input_length and strips without any
+ * label are zero; nll [N][W] fp32, 0 where absent.  Recursion, nll, coef and the sums over depths (ascending i) run in fp64, each
+ * output element is written once by one thread and rounded once: bit-reproducible, no atomics.  An infeasible target gives
+ * nll = +inf, a non-finite loss and NaN rows t < input_length of THAT strip only (as qea_ctc_loss does).
+ * At most three launches whatever W and the histories (two when grad is NULL); nothing synchronises and nothing is copied, so the
+ * call can be captured in a hipGraph.  W <= QEA_HISTORY_MAX_WINDOW, S_max >= 2*max(len)+1, <= 256, T <= 65535.  workspace:
+ * qea_ctc_history_workspace_bytes(T, N, W, S_max) = (2*T*S_max + 2) * N*W * 8 bytes (alpha, beta, nll, coef in fp64), 8-byte aligned.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects these two by symbol.) */
+size_t qea_ctc_history_workspace_bytes(int32_t T, int32_t N, int32_t W, int32_t S_max);
+int qea_ctc_history_loss(const float* lp, int32_t ld_t, int32_t ld_n, const int32_t* input_lengths, const int32_t* lens,
+                         const int32_t* offs, const int32_t* chars, const int32_t* depth_n, const float* weights,
+                         int32_t w_stride_n, int32_t w_stride_i, int32_t mean_by_length, int32_t T, int32_t N, int32_t C, int32_t W,
+                         int32_t blank, int32_t S_max, float* loss, float* grad, int32_t gld_t, int32_t gld_n, float* nll,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,3 +78,22 @@ class CTCFn(torch.autograd.Function):
         else:
             g = g * gout.view(1, -1, 1)
         return g, None, None, None, None, None, None, None
+
+
+class HistoryCTCFn(torch.autograd.Function):
+    """The label-history weighted CTC loss (csrc/ctc_history.hip) as one scalar; the weights are constants."""
+
+    @staticmethod
+    def forward(ctx, lp, in_len, lens, offs, chars, depth_n, weights, w_stride_n, w_stride_i, mean_by_length, S_max, blank):
+        if lp.stride(2) != 1:
+            lp = lp.contiguous()
+        loss, grad, _ = ops.ctc_history_loss(lp, in_len, lens, offs, chars, depth_n, weights, w_stride_n, w_stride_i, mean_by_length, S_max,
+                                             blank, need_grad=ctx.needs_input_grad[0])
+        ctx.grad = grad
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        g = ctx.grad
+        ctx.grad = None
+        return (g * gout,) + (None,) * 11

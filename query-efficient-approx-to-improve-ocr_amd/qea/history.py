@@ -175,3 +175,89 @@ class AttentionPacker(LabelPacker):
         if len(idx) > self.row_len:
             return None                                         # str_to_tensor fails on the ragged rows: the host path raises
         return np.asarray(idx, dtype=np.int32).reshape(-1)
+
+
+# ----------------------------------------------------------------------------- the weighted CTC loss over the history (csrc/ctc_history.hip)
+CTC_MAX_LABEL = 127       # 2 L + 1 <= 256 states
+
+
+def ctc_steps_forced():
+    """QEA_HISTORY_CTC=steps keeps tracking_utils.weighted_ctc_loss's loop over the depths on a GPU too (A/B runs)"""
+    return os.environ.get("QEA_HISTORY_CTC", "fused") == "steps"
+
+
+def ctc_route(scores, loss_weights, window, max_label, loss_fn):
+    """'fused' (one qea_ctc_history_loss call) or 'steps' (one CTC evaluation per history depth) for one weighted_ctc_loss call.
+    `max_label`: the longest label of the call; `loss_fn`: the CTC module the loop would call (primary_loss_fn for decaying
+    weights, primary_loss_fn_sample_wise otherwise).  Callable without a GPU."""
+    from .loss import CTCLoss
+    if ctc_steps_forced() or not (torch.is_tensor(scores) and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 3):
+        return "steps"
+    if not (torch.is_tensor(loss_weights) and loss_weights.is_cuda and loss_weights.dtype == torch.float32 and not loss_weights.requires_grad):
+        return "steps"
+    if window < 1 or window > MAX_WINDOW or max_label > CTC_MAX_LABEL or not isinstance(loss_fn, CTCLoss):
+        return "steps"
+    return "fused"
+
+
+class TargetBatchPacker:
+    """`target_batches` of tracking_utils.generate_ctc_target_batches ([targets, target sizes, strip indices] per history depth)
+    -> one int32 array  [depth_n: W] [lens: n * W] [offs: n * W] [chars: total] [input_lengths: n]  (the last block only when the
+    input lengths are handed over as a host tensor), pinned when a GPU is present, so the whole call is one host-to-device copy.
+    lens is -1 where a strip has no label at a depth; offs points into chars.  The index list of a depth may be any set of distinct
+    strips: nothing assumes that a deeper list is a subset of a shallower one."""
+    _buffer = LabelPacker._buffer
+    to_device = LabelPacker.to_device
+
+    def __init__(self):
+        self._pinned = None
+        self._event = None
+
+    @staticmethod
+    def sizes(n, W, total, with_input_lengths=False):
+        """element offsets of (depth_n, lens, offs, chars, input_lengths, end) in the packed array"""
+        o_lens = W
+        o_offs = o_lens + n * W
+        o_chars = o_offs + n * W
+        o_in = o_chars + total
+        return 0, o_lens, o_offs, o_chars, o_in, o_in + (n if with_input_lengths else 0)
+
+    def pack(self, target_batches, n, input_lengths=None):
+        """-> (host int32 array, the pinned tensor it views or None, W, total characters, longest label), or None for batches the
+        fused call does not take (an index outside 0..n-1 or listed twice, sizes that do not match: the loop answers those)"""
+        W = len(target_batches)
+        parts = []
+        for target, target_size, idx in target_batches:
+            tg = torch.as_tensor(target).reshape(-1).numpy().astype(np.int32, copy=False)
+            ts = torch.as_tensor(target_size).reshape(-1).numpy().astype(np.int64, copy=False)
+            ix = np.asarray(idx, dtype=np.int64).reshape(-1)
+            if len(ts) != len(ix) or len(ix) == 0 or ts.min() < 0 or int(ts.sum()) != len(tg):
+                return None
+            if ix.min() < 0 or ix.max() >= n or len(np.unique(ix)) != len(ix):
+                return None
+            parts.append((tg, ts, ix))
+        if input_lengths is not None and len(input_lengths) != n:
+            return None
+        total = sum(len(tg) for tg, _, _ in parts)
+        o_depth, o_lens, o_offs, o_chars, o_in, end = self.sizes(n, W, total, input_lengths is not None)
+        host, pinned = self._buffer(end)
+        lens = host[o_lens:o_offs].reshape(n, W)
+        offs = host[o_offs:o_chars].reshape(n, W)
+        lens.fill(-1)
+        offs.fill(0)
+        base, longest = 0, 0
+        for i, (tg, ts, ix) in enumerate(parts):
+            host[o_depth + i] = len(ix)
+            lens[ix, i] = ts
+            offs[ix, i] = base + np.cumsum(ts) - ts
+            host[o_chars + base:o_chars + base + len(tg)] = tg
+            base += len(tg)
+            longest = max(longest, int(ts.max()))
+        if input_lengths is not None:
+            host[o_in:end] = torch.as_tensor(input_lengths).reshape(-1).numpy()
+        return host, pinned, W, total, longest
+
+    def unpack(self, host, n, W, total):
+        """views (depth_n [W], lens [n][W], offs [n][W], chars [total], the rest) of a packed array or device tensor"""
+        o_depth, o_lens, o_offs, o_chars, o_in, _ = self.sizes(n, W, total)
+        return host[o_depth:o_lens], host[o_lens:o_offs].reshape(n, W), host[o_offs:o_chars].reshape(n, W), host[o_chars:o_in], host[o_in:]

@@ -880,3 +880,41 @@ def history_attn_weights(char_idx, count, n, W, n_chars, embedding, wq_weight, w
                                                    _ptr(wq_bias), Dq, _ptr(coef_weight), _ptr(coef_bias), _ptr(pos),
                                                    HISTORY_ACTIVATIONS[activation], _ptr(out), _stream()), "qea_history_attn_weights")
     HISTORY_LAUNCHES["attn"] += 1
+
+
+HISTORY_CTC_LAUNCHES = {"ctc": 0}            # launches of csrc/ctc_history.hip issued through this module (tests, tools)
+
+
+def ctc_history_workspace_bytes(T, N, W, S_max):
+    return _lib.lib().qea_ctc_history_workspace_bytes(T, N, W, S_max)
+
+
+def ctc_history_loss(lp, input_lengths, lens, offs, chars, depth_n, weights, w_stride_n, w_stride_i, mean_by_length, S_max, blank=0,
+                     need_grad=True):
+    """include/qea_hip.h: qea_ctc_history_loss — lp [T][N][C] fp32 (last stride 1), input_lengths [N], lens / offs [N][W], chars,
+    depth_n [W] int32, weights fp32 read at n * w_stride_n + i * w_stride_i -> (loss [1], grad [T][N][C] or None, nll [N][W]).
+    Three launches (two without the gradient), no synchronisation."""
+    T, N, C_ = lp.shape
+    W = depth_n.numel()
+    if lp.dtype != torch.float32 or lp.stride(2) != 1 or weights.dtype != torch.float32:
+        raise _lib.QeaError("ctc_history_loss needs fp32 log-probs with a unit class stride and fp32 weights")
+    if any(t.dtype != torch.int32 or not t.is_contiguous() for t in (input_lengths, lens, offs, chars, depth_n)):
+        raise _lib.QeaError("ctc_history_loss needs contiguous int32 lengths, offsets, characters and depth counts")
+    if input_lengths.numel() != N or lens.numel() != N * W or offs.numel() != N * W:
+        raise _lib.QeaError(f"ctc_history_loss: tables of {lens.numel()} / {offs.numel()} entries for N={N}, W={W}")
+    if W < 1 or (N - 1) * w_stride_n + (W - 1) * w_stride_i >= weights.untyped_storage().nbytes() // 4 - weights.storage_offset():
+        raise _lib.QeaError("ctc_history_loss: the weight strides reach past the weight tensor")
+    if chars.numel() == 0:
+        chars = torch.zeros(1, dtype=torch.int32, device=lp.device)      # every label empty: the pointer is never read
+    L = _lib.lib()
+    dev = lp.device
+    loss = torch.empty(1, device=dev)
+    nll = torch.empty(N, W, device=dev)
+    grad = torch.empty(T, N, C_, device=dev) if need_grad else None
+    ws = workspace(L.qea_ctc_history_workspace_bytes(T, N, W, S_max), dev)
+    _lib.check(L.qea_ctc_history_loss(_ptr(lp), lp.stride(0), lp.stride(1), _ptr(input_lengths), _ptr(lens), _ptr(offs), _ptr(chars),
+                                      _ptr(depth_n), _ptr(weights), w_stride_n, w_stride_i, int(mean_by_length), T, N, C_, W, blank, S_max,
+                                      _ptr(loss), _ptr(grad), N * C_ if need_grad else 0, C_ if need_grad else 0, _ptr(nll), ws.data_ptr(),
+                                      ws.numel(), _stream()), "qea_ctc_history_loss")
+    HISTORY_CTC_LAUNCHES["ctc"] += 3 if need_grad else 2
+    return loss, grad, nll

@@ -38,6 +38,12 @@ def generate_ctc_target_batches(self, img_names):
 
 
 def weighted_ctc_loss(self, scores, pred_size, target_batches, loss_weights):
+    """[new] On the GPU with this project's CTCLoss the W depths are evaluated by ONE call of csrc/ctc_history.hip (three launches,
+    one pinned host-to-device copy); everything else — CPU tensors, torch's own CTCLoss, weights that carry a graph, a window above 8,
+    a label above 127 characters, QEA_HISTORY_CTC=steps — runs the reference's loop below."""
+    fused = _fused_weighted_ctc_loss(self, scores, pred_size, target_batches, loss_weights)
+    if fused is not None:
+        return fused
     losses = []
     for i in range(min(len(target_batches), self.window_size)):
         target, target_size, idx = target_batches[i]
@@ -48,6 +54,39 @@ def weighted_ctc_loss(self, scores, pred_size, target_batches, loss_weights):
             per = self.primary_loss_fn_sample_wise(sub, target, pred_size[idx], target_size)
             losses.append(torch.mean(loss_weights[idx, i] * per))
     return sum(losses)
+
+
+def _fused_weighted_ctc_loss(self, scores, pred_size, target_batches, loss_weights):
+    """the loss of weighted_ctc_loss from qea.autograd.HistoryCTCFn, or None when the call has to take the loop"""
+    from qea import history
+    W = min(len(target_batches), self.window_size)
+    decaying = self.weightgen_method == "decaying"
+    loss_fn = getattr(self, "primary_loss_fn" if decaying else "primary_loss_fn_sample_wise", None)
+    if W < 1 or history.ctc_route(scores, loss_weights, self.window_size, 0, loss_fn) != "fused":
+        return None
+    if loss_fn.reduction != ("mean" if decaying else "none") or loss_fn.max_target_length is not None:
+        return None
+    n = scores.shape[1]
+    if loss_weights.dim() != (1 if decaying else 2) or loss_weights.shape[-1] < W or (not decaying and loss_weights.shape[0] != n):
+        return None
+    if any(torch.is_tensor(t) and t.is_cuda for b in target_batches[:W] for t in b[:2]):
+        return None
+    from qea.autograd import HistoryCTCFn
+    packer = getattr(self, "_ctc_packer", None)
+    if packer is None:
+        packer = self._ctc_packer = history.TargetBatchPacker()
+    on_host = not (torch.is_tensor(pred_size) and pred_size.is_cuda)
+    packed = packer.pack(target_batches[:W], n, pred_size if on_host else None)
+    if packed is None or history.ctc_route(scores, loss_weights, self.window_size, packed[4], loss_fn) != "fused":
+        return None
+    host, _, W, total, longest = packed
+    dev = packer.to_device(packed[:2], scores.device)
+    depth_n, lens, offs, chars, in_len = packer.unpack(dev, n, W, total)
+    if not on_host:
+        in_len = pred_size.to(torch.int32).contiguous()
+    strides = (0, loss_weights.stride(0)) if decaying else (loss_weights.stride(0), loss_weights.stride(1))
+    return HistoryCTCFn.apply(scores, in_len, lens, offs, chars, depth_n, loss_weights, strides[0], strides[1], int(decaying),
+                              2 * max(longest, 1) + 1, loss_fn.blank)
 
 
 def add_labels_to_history(self, image_keys, ocr_labels):
