@@ -12,23 +12,10 @@
 // forms   grad[t,n,c] = (exp(lp) - exp(lse_{s: l'_s = c}(alpha+beta) + nll - lp)) * grad_out[n]
 // exactly as ATen does (reference call sites: train_nn_patch.py:143,178,294).
 // Latency-bound (31-step scan); bytes: 2 * T*N*C*4 in/out + 2 * N*T*S*4 workspace.
-#include "common.h"
+// The recursion, the gradient's inner loop and the tree sum live in ctc_core.h, shared with ctc_history.hip.
+#include "ctc_core.h"
 
 namespace {
-
-constexpr int CTC_MAX_S = 256;
-
-#define NEG_INF_D (-(double)INFINITY)
-__device__ __forceinline__ double lse3(double a, double b, double c) {
-  const double m = fmax(fmax(a, b), c);
-  if (m == NEG_INF_D) return NEG_INF_D;
-  return m + log(exp(a - m) + exp(b - m) + exp(c - m));
-}
-__device__ __forceinline__ double lse2(double a, double b) {
-  const double m = fmax(a, b);
-  if (m == NEG_INF_D) return NEG_INF_D;
-  return m + log(exp(a - m) + exp(b - m));
-}
 
 // one wave per row
 __global__ __launch_bounds__(256) void log_softmax_fwd_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy, long long M,
@@ -75,79 +62,11 @@ __global__ __launch_bounds__(CTC_MAX_S) void ctc_alpha_beta_kernel(const float* 
   __shared__ double prev[2][CTC_MAX_S + 2];
   const int n = blockIdx.x;
   const bool is_beta = blockIdx.y == 1;
-  const int s = threadIdx.x;
-  const int L = tg_len[n];
-  const int Tn = min(in_len[n], T);
-  const int S = 2 * L + 1;
-  const int* tg = targets + tg_off[n];
-  const float* lpn = lp + (size_t)n * ld_n;
-  double* out = (is_beta ? beta : alpha) + (size_t)n * T * S_max;
-
-  int ch = blank;      // l'_s
-  bool skip = false;   // alpha: may come from s-2 ; beta: may go to s+2
-  if (s < S && (s & 1)) {
-    ch = tg[s >> 1];
-    if (!is_beta) skip = (s >= 2) && (tg[(s >> 1) - 1] != ch);
-    else skip = (s + 2 < S) && (tg[(s >> 1) + 1] != ch);
-  }
-  if (Tn <= 0 || S > S_max) {  // degenerate / longer than the caller sized for: infeasible
-    if (!is_beta && s == 0) {
-      nll[n] = INFINITY;
-      nll64[n] = (double)INFINITY;
-    }
-    return;
-  }
-
-  // prev rows are padded by 2 on the side the recursion reaches into
-  double cur = NEG_INF_D;
-  if (!is_beta) {
-    if (s == 0) cur = (double)lpn[blank];
-    else if (s == 1 && S > 1) cur = (double)lpn[ch];
-  } else {
-    const float* lpt = lpn + (size_t)(Tn - 1) * ld_t;
-    if (s == S - 1) cur = (double)lpt[blank];
-    else if (s == S - 2 && S > 1) cur = (double)lpt[ch];
-  }
-  int buf = 0;
-  if (s < 2) {
-    prev[0][is_beta ? CTC_MAX_S + s : s] = NEG_INF_D;  // padding cells
-    prev[1][is_beta ? CTC_MAX_S + s : s] = NEG_INF_D;
-  }
-  // storage index: alpha uses prev[.][s+2] (reads s+1, s), beta uses prev[.][s] (reads s+1, s+2)
-  const int off = is_beta ? 0 : 2;
-  if (s < S) out[(size_t)(is_beta ? Tn - 1 : 0) * S_max + s] = cur;
-  prev[buf][s + off] = (s < S) ? cur : NEG_INF_D;
-  __syncthreads();
-  for (int step = 1; step < Tn; ++step) {
-    const int t = is_beta ? Tn - 1 - step : step;
-    double v = NEG_INF_D;
-    if (s < S) {
-      double a0, a1, a2;
-      if (!is_beta) {
-        a0 = prev[buf][s + 2];
-        a1 = prev[buf][s + 1];
-        a2 = skip ? prev[buf][s] : NEG_INF_D;
-      } else {
-        a0 = prev[buf][s];
-        a1 = (s + 1 < S) ? prev[buf][s + 1] : NEG_INF_D;
-        a2 = skip ? prev[buf][s + 2] : NEG_INF_D;
-      }
-      v = lse3(a0, a1, a2) + (double)lpn[(size_t)t * ld_t + ch];
-      out[(size_t)t * S_max + s] = v;
-    }
-    buf ^= 1;
-    prev[buf][s + off] = v;
-    __syncthreads();
-  }
-  if (!is_beta) {
-    // prev[buf] holds alpha_{Tn-1}
-    if (s == 0) {
-      const double a = prev[buf][(S - 1) + 2];
-      const double b = (S > 1) ? prev[buf][(S - 2) + 2] : NEG_INF_D;
-      const double v = -lse2(a, b);
-      nll64[n] = v;
-      nll[n] = (float)v;
-    }
+  const double v = ctc_scan(lp + (size_t)n * ld_n, ld_t, targets + tg_off[n], tg_len[n], min(in_len[n], T), blank, S_max, is_beta,
+                            (is_beta ? beta : alpha) + (size_t)n * T * S_max, prev);
+  if (!is_beta && threadIdx.x == 0) {
+    nll64[n] = v;
+    nll[n] = (float)v;
   }
 }
 
@@ -171,18 +90,13 @@ __global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__
   const int* tg = targets + tg_off[n];
   const double* al = alpha + ((size_t)n * T + t) * S_max;
   const double* be = beta + ((size_t)n * T + t) * S_max;
-  for (int s = threadIdx.x; s < S; s += blockDim.x) {
-    ab[s] = al[s] + be[s];
-    ext[s] = (s & 1) ? tg[s >> 1] : blank;
-  }
+  ctc_stage_row(al, be, tg, S, blank, ab, ext, blockDim.x);
   __syncthreads();
   const double nl = nll[n];
   const double go = (double)grad_out[n];
   const float* lpr = lp + (size_t)n * ld_n + (size_t)t * ld_t;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    double res = NEG_INF_D;
-    for (int s = 0; s < S; ++s)
-      if (ext[s] == c) res = lse2(res, ab[s]);
+    const double res = ctc_lse_char(ab, ext, S, c);
     const double l = (double)lpr[c];
     grow[c] = (float)((exp(l) - exp(res + nl - l)) * go);
   }
@@ -192,7 +106,6 @@ __global__ void ctc_reduce_kernel(const double* __restrict__ nll, const int* __r
                                   float* __restrict__ loss, float* __restrict__ grad_out) {
   // reduction 1 = mean: loss = mean_n(nll_n / max(len_n,1)), grad_out_n = scale_in / (N * max(len_n,1))
   // reduction 0 = none: grad_out_n = scale_in (caller multiplies by its own upstream gradient)
-  __shared__ double sred[256];
   double acc = 0;
   for (int n = threadIdx.x; n < N; n += blockDim.x) {
     const float tl = (float)max(tg_len[n], 1);
@@ -204,13 +117,8 @@ __global__ void ctc_reduce_kernel(const double* __restrict__ nll, const int* __r
       grad_out[n] = scale_in;
     }
   }
-  sred[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) sred[threadIdx.x] += sred[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = (reduction == 1) ? (float)(sred[0] / (double)N) : (float)sred[0];
+  const double sum = ctc_tree_sum_256(acc);
+  if (threadIdx.x == 0) loss[0] = (reduction == 1) ? (float)(sum / (double)N) : (float)sum;
 }
 
 }  // namespace
@@ -242,16 +150,14 @@ extern "C" int qea_ctc_loss(const float* lp, int32_t ld_t, int32_t ld_n, const i
                             int32_t gld_n, void* workspace, size_t workspace_bytes, void* stream) {
   QEA_REQUIRE(lp && targets && target_offsets && input_lengths && target_lengths && nll && loss, "qea_ctc_loss: null pointer");
   QEA_REQUIRE(T > 0 && N > 0 && C > 0 && blank >= 0 && blank < C, "qea_ctc_loss: bad dimensions");
-  QEA_REQUIRE(S_max >= 1 && S_max <= CTC_MAX_S, "qea_ctc_loss: S_max=%d must be in [1,%d] (targets up to %d chars)", S_max, CTC_MAX_S,
-              (CTC_MAX_S - 1) / 2);
+  if (const int rc = ctc_check_s_max("qea_ctc_loss", S_max)) return rc;
   QEA_REQUIRE(workspace && workspace_bytes >= qea_ctc_workspace_bytes(T, N, S_max), "qea_ctc_loss: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   double* alpha = (double*)workspace;
   double* beta = alpha + (size_t)N * T * S_max;
   double* nll64 = beta + (size_t)N * T * S_max;
   float* gout = (float*)(nll64 + N);
-  const int threads = ((S_max + 63) / 64) * 64;
-  hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3(N, grad ? 2 : 1), dim3(threads), 0, s, lp, ld_t, ld_n, targets,
+  hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3(N, grad ? 2 : 1), dim3(ctc_scan_threads(S_max)), 0, s, lp, ld_t, ld_n, targets,
                      (const long long*)target_offsets, input_lengths, target_lengths, T, blank, alpha, beta, nll, nll64, S_max);
   hipLaunchKernelGGL(ctc_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)nll64, target_lengths, N, reduction, grad_scale, loss, gout);
   if (grad) {

@@ -5,21 +5,23 @@
 // history_lev_kernel: one wave per workgroup, one LANE per unordered pair of words (W(W-1)/2 pairs per strip, S = LEV_LANES / pairs
 // strips per workgroup, capped so that the staged characters fit).  The characters of the workgroup's words sit in LDS
 // character-major (tok[c * slots + word]: the lanes of a pair loop read the same c, so at most the words differ), the DP row of a
-// lane column-major as in edit_distance_kernel (row[j * 64 + lane]: conflict-free).  The distances meet in LDS; one lane per
-// (strip, word) sums them as integers and evaluates the weight in fp64 with every operation rounded separately, as CPython does.
+// lane column-major (row[j * 64 + lane]: conflict-free); the recursion is edit_distance.h's, the one edit_distance_kernel runs.
+// The distances meet in LDS; one lane per (strip, word) sums them as integers and evaluates the weight in fp64 with every operation
+// rounded separately, as CPython does.
 //
 // history_attn_kernel: Wq is linear, so  q[w] = (1/n_chars) sum_c T[idx[w][c]] + P[w]  with  T = embedding Wq^T  [V1][Dq]  and
 // P = positional_encodings Wq^T + bias  [W][Dq].  Every workgroup builds T and P once in LDS ((V1 + W) * Dq floats, 12.6 KB at the
 // default sizes; 0.8 MFLOP) and then walks strips, one WAVE per strip: the gather-sum of T rows (four partial sums per element),
 // then lane i owns row i of softmax(q q^T / sqrt(Dq)), its Linear(W -> 1) and the activation.  fp32 throughout, no MFMA.
 #include "common.h"
+#include "edit_distance.h"
 #include <math.h>
 
 namespace {
 
 constexpr int HW_MAX = QEA_HISTORY_MAX_WINDOW;
-constexpr int LEV_L = QEA_HISTORY_MAX_LEN;
-constexpr int LEV_LANES = 64;
+constexpr int LEV_L = ED_MAX;
+constexpr int LEV_LANES = ED_LANES;
 constexpr int LEV_SLOTS = 56;                       // words staged per workgroup: 56 * 128 * 4 B = 28 KB next to the 33 KB of DP rows
 constexpr int ATTN_THREADS = 256;
 constexpr int ATTN_WAVES = ATTN_THREADS / QEA_WAVE;
@@ -68,22 +70,8 @@ __global__ __launch_bounds__(LEV_LANES) void history_lev_kernel(const int* __res
     const int cnt = min(max(count[r0 + s], 0), W);
     if (b < cnt) {
       const int sa = s * W + a, sb = s * W + b;
-      const int la = wlen[sa], lb = wlen[sb];
-      for (int j = 0; j <= lb; ++j) row[j * LEV_LANES + lane] = j;
-      for (int i = 1; i <= la; ++i) {
-        const int ca = tok[(i - 1) * slots + sa];
-        int diag = row[lane];
-        row[lane] = i;
-        int left = i;
-        for (int j = 1; j <= lb; ++j) {
-          const int up = row[j * LEV_LANES + lane];
-          const int v = min(min(up + 1, left + 1), diag + (tok[(j - 1) * slots + sb] != ca));
-          row[j * LEV_LANES + lane] = v;
-          diag = up;
-          left = v;
-        }
-      }
-      const int d = row[lb * LEV_LANES + lane];
+      const int d = edit_distance_lane(row, lane, wlen[sa], wlen[sb], [&](int i) { return tok[i * slots + sa]; },
+                                       [&](int j) { return tok[j * slots + sb]; });
       dist[sa * W + b] = d;
       dist[sb * W + a] = d;
     }

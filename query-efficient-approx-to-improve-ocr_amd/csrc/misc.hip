@@ -3,6 +3,7 @@
 // stable descending top-k (TopKCER), crop+pad gather / scatter-add, greedy CTC decode.
 // All HBM- or latency-bound; bytes noted per entry point in include/qea_hip.h.
 #include "common.h"
+#include "edit_distance.h"
 
 static __device__ __forceinline__ int qea_floordiv2(int d) { return d >= 0 ? d / 2 : -((-d + 1) / 2); }
 
@@ -214,33 +215,17 @@ __global__ __launch_bounds__(64) void greedy_decode_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------ edit distance (CER numerator)
-// one thread per sample, the DP row in LDS column-major (row[j*64 + lane]: conflict-free), unit costs
-constexpr int ED_MAX = 128;
-__global__ __launch_bounds__(64) void edit_distance_kernel(const int* __restrict__ pred, int ldp, const int* __restrict__ pred_len,
-                                                           const int* __restrict__ gt, const long long* __restrict__ gt_off,
-                                                           const int* __restrict__ gt_len, int N, int* __restrict__ out) {
-  __shared__ int row[(ED_MAX + 1) * 64];
+// one thread per sample (edit_distance.h): outer word = ground truth, inner word = prediction, both read from global memory
+__global__ __launch_bounds__(ED_LANES) void edit_distance_kernel(const int* __restrict__ pred, int ldp, const int* __restrict__ pred_len,
+                                                                 const int* __restrict__ gt, const long long* __restrict__ gt_off,
+                                                                 const int* __restrict__ gt_len, int N, int* __restrict__ out) {
+  __shared__ int row[(ED_MAX + 1) * ED_LANES];
   const int lane = threadIdx.x;
-  const int n = blockIdx.x * 64 + lane;
+  const int n = blockIdx.x * ED_LANES + lane;
   if (n >= N) return;
-  const int lp = min(pred_len[n], ED_MAX), lg = gt_len[n];
   const int* p = pred + (size_t)n * ldp;
   const int* g = gt + gt_off[n];
-  for (int j = 0; j <= lp; ++j) row[j * 64 + lane] = j;
-  for (int i = 1; i <= lg; ++i) {
-    const int gc = g[i - 1];
-    int diag = row[lane];  // D[i-1][0]
-    row[lane] = i;
-    int left = i;
-    for (int j = 1; j <= lp; ++j) {
-      const int up = row[j * 64 + lane];
-      const int v = min(min(up + 1, left + 1), diag + (p[j - 1] != gc));
-      row[j * 64 + lane] = v;
-      diag = up;
-      left = v;
-    }
-  }
-  out[n] = row[lp * 64 + lane];
+  out[n] = edit_distance_lane(row, lane, gt_len[n], min(pred_len[n], ED_MAX), [g](int i) { return g[i]; }, [p](int j) { return p[j]; });
 }
 
 int grid_for(long long n, int cap = 4096) {
@@ -346,8 +331,8 @@ extern "C" int qea_edit_distance(const int32_t* pred_tokens, int32_t ldp, const 
                                  const int64_t* gt_offsets, const int32_t* gt_len, int32_t N, int32_t* out, void* stream) {
   QEA_REQUIRE(pred_tokens && pred_len && gt_tokens && gt_offsets && gt_len && out && N > 0 && ldp > 0 && ldp <= ED_MAX,
               "qea_edit_distance: bad arguments (prediction length <= %d)", ED_MAX);
-  hipLaunchKernelGGL(edit_distance_kernel, dim3(qea_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, pred_tokens, ldp, pred_len, gt_tokens,
-                     (const long long*)gt_offsets, gt_len, N, out);
+  hipLaunchKernelGGL(edit_distance_kernel, dim3(qea_cdiv(N, ED_LANES)), dim3(ED_LANES), 0, (hipStream_t)stream, pred_tokens, ldp, pred_len,
+                     gt_tokens, (const long long*)gt_offsets, gt_len, N, out);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

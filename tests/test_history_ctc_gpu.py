@@ -1,6 +1,6 @@
 """The label-history weighted CTC loss in one device pass (csrc/ctc_history.hip through tracking_utils.weighted_ctc_loss): both
 weight forms against the fp64 loop, the long / short shapes, an infeasible label, the fixed launch count, bit-reproducibility,
-hipGraph replay, and the routing back to the loop over the depths.
+hipGraph replay, bit-equality with the plain CTC kernels at W = 1, and the routing back to the loop over the depths.
 
 The fp64 reference is tracking_utils.weighted_ctc_loss itself on CPU fp64 log-probs with torch.nn.CTCLoss: CPU tensors and torch's
 loss both send that call to the loop, so the reference never passes through the code under test."""
@@ -261,6 +261,41 @@ def test_graph_replay_is_bit_equal_to_eager():
         graph.replay()
         torch.cuda.synchronize()
         assert torch.equal(loss.detach(), eager) and torch.equal(lp.grad, g_eager)
+
+
+def test_window_one_is_bit_equal_to_the_plain_ctc_kernels():
+    """csrc/ctc.hip and csrc/ctc_history.hip run the one recursion of csrc/ctc_core.h: at W = 1 with every coefficient 0.25 (a power
+    of two, so the scaling is exact) the per-problem nll, the gradient and the loss agree bit for bit with the plain kernels."""
+    from qea import ops
+    T, N = 80, 4
+    rng = np.random.RandomState(0)
+    labels = [_word(rng, 65), "", "aab", _word(rng, 5)]          # S = 131: three waves in the scan, two rounds of the gradient's staging
+    in_len = [80, 3, 7, 80]
+    lp = _log_probs(T, N, 31)
+    y = torch.tensor([H.C2I[c] for c in "".join(labels)], dtype=torch.int)
+    ys = torch.tensor([len(l) for l in labels], dtype=torch.int)
+    il = torch.tensor(in_len, dtype=torch.int)
+    assert torch.isfinite(torch.nn.functional.ctc_loss(lp.double(), y, il, ys, reduction="none")).all()
+    off = torch.zeros(N, dtype=torch.int64)
+    off[1:] = torch.cumsum(ys.long(), 0)[:-1]
+    S_max = 2 * 65 + 1
+    dev = "cuda"
+    lpd, yd, ysd, ild = lp.to(dev), y.to(dev), ys.to(dev), il.to(dev)
+    nll_p, loss_p, grad_p = torch.empty(N, device=dev), torch.empty(1, device=dev), torch.empty(T, N, C, device=dev)
+    ops.ctc_loss(lpd, N * C, C, yd, off.to(dev), ild, ysd, T, N, C, 0, S_max, 0, 1.0, nll_p, loss_p, grad_p, N * C, C)
+    w = torch.ones(N, 2, device=dev)
+    depth_n = torch.tensor([4], dtype=torch.int, device=dev)
+    loss_h, grad_h, nll_h = ops.ctc_history_loss(lpd, ild, ysd.reshape(N, 1), off.int().to(dev).reshape(N, 1), yd, depth_n, w, 2, 1, 0, S_max)
+    torch.cuda.synchronize()
+    assert torch.equal(nll_h[:, 0], nll_p)
+    assert torch.equal(grad_h, grad_p * 0.25)
+    assert torch.equal(loss_h, loss_p * 0.25)
+    for n, L in enumerate(in_len):
+        assert (grad_h[L:, n, :] == 0).all() and (grad_p[L:, n, :] == 0).all(), n
+        assert (grad_p[:L, n, :] != 0).any(), n
+    tiny = torch.finfo(torch.float32).tiny                       # no subnormal on either side of the scaling by 0.25
+    for v in (nll_p, loss_p, grad_p, nll_h, loss_h, grad_h):
+        assert torch.isfinite(v).all() and (v[v != 0].abs() >= tiny).all()
 
 
 @pytest.mark.parametrize("why", ["weights_require_grad", "torch_ctc_loss", "label_of_130", "env_switch"])
