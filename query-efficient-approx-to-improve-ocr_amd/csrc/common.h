@@ -31,10 +31,13 @@ __device__ __forceinline__ void qea_split3(const f32x4 v, bf16x4& h, bf16x4& m, 
 
 // TWO-way fp16 split of a SCALED operand (round 3): xs = x * s with s a power of two chosen from the tensor's largest finite
 // magnitude m so that m * s is in [2^14, 2^15) (qea_f16_scale); h = f16(xs) and l = f16(xs - h) carry 11 + 11 significant bits
-// (+ the sign of l): |xs - (h + l)| <= 2^-24 |xs| — as good as the three bf16 pieces — for every element down to about 2^-16 of m
-// (|xs| >= 1/2: the residual's last fp32 bit is then still >= 2^-24, the spacing of the SUBNORMAL fp16 values l falls into once
-// |xs| < ~2^-3), and an ABSOLUTE error below 2^-25 in scaled units = 2^-40 m for the smaller ones (e.g. ~2^-11 relative at 2^-29 of
-// m: negligible against the rounding of the large terms such an element is summed with).  A product keeps hh,
+// (+ the sign of l).  Per element, for ANY bound m >= the tensor's maximum as the scale source:
+//     |xs - (h + l)| <= max(2^-23 |xs|, 2^-25)   in scaled units, i.e.   |x - (h + l) / s| <= max(2^-23 |x|, 2^-39 m).
+// The relative part: the residual xs - h is below half an ulp of h and l keeps 11 of its (up to 13) bits, so the pair is one bit short
+// of fp32 in the worst case (xs just above a power of two) and exact for most elements — it holds down to 2^-16 of m.  The absolute
+// part: 2^-25 is half the spacing of the SUBNORMAL fp16 values l falls into once |xs| < ~2^-3, and m s >= 2^14 makes it at most
+// 2^-39 m (2^-40 m only when m is just below a power of two) — e.g. ~2^-10 relative at 2^-29 of m: negligible against the rounding
+// of the large terms such an element is summed with.  tests/test_host_logic_cpu.py emulates both figures.  A product keeps hh,
 // hl, lh (three v_mfma_f32_32x32x16_f16, fp32 accumulate); the dropped ll is < 2^-22 |ab|.  Non-finite elements do not enter m
 // and stay non-finite in h (inf) / l (NaN).
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
@@ -48,6 +51,10 @@ __device__ __forceinline__ void qea_split2_f16(const f32x4 v, float s, f16x4& h,
   }
 }
 // s = 2^(15 - e) for m = f * 2^e, f in [0.5, 1): bits of the scale and of its inverse from the exponent field of m (m >= 0, finite)
+// SUPPORTED RANGE: m >= 2^-112.  Both s and 1 / s must be normal fp32 numbers, so the exponent is clamped to +-126 (the lower clamp is
+// never reached: m < 2^128 gives se >= -113).  For 2^-126 <= m < 2^-112 the scale stops at 2^126, m s falls short of 2^14 and the
+// absolute part of the bound above grows from 2^-39 m to 2^-25 * 2^-126 (2^-25 m at the smallest normal m); a subnormal m gets
+// scale 1 and its planes are zero.  Gradients of a mean-reduced loss sit near 2^-30; nothing in the models comes within 2^-60 of it.
 __device__ __forceinline__ void qea_f16_scale(float m, float& s, float& inv) {
   const unsigned E = (__float_as_uint(m) >> 23) & 0xffu;     // biased exponent; m = 1.x * 2^(E - 127), floor(log2 m) = E - 127
   int se = 14 - ((int)E - 127);                                // s = 2^se puts m * s into [2^14, 2^15)

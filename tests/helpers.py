@@ -11,6 +11,32 @@ assert len(CHAR_SET) == 95
 C2I = {c: i for i, c in enumerate(CHAR_SET)}
 I2C = {i: c for i, c in enumerate(CHAR_SET)}
 
+# The per-element contract of the two-way fp16 split (csrc/common.h, qea_split2_f16) for a scale taken from any bound m >= max |x|:
+# |x - (h + l) / s| <= max(SPLIT_REL * |x|, SPLIT_ABS * m).  Checked in numpy by tests/test_host_logic_cpu.py; the derived gates of
+# tests/test_operand_scale_gpu.py rest on it.
+SPLIT_REL = 2.0 ** -23
+SPLIT_ABS = 2.0 ** -39
+
+
+def split_probe_values(n, seed):
+    """n fp32 values with max |x| = 1.0 exactly (so a bound of 2^j is a power of two, where m * s sits at the BOTTOM of [2^14, 2^15)):
+    half of them log-uniform over [2^-17, 2^-14), around the edge 2^-16 of the relative regime of the split, the rest over 2^-30 ... 1.
+    An operand through an identity filter shows the split of every element; at that edge one bit of scale too few (m * s in
+    [2^13, 2^14)) doubles the error of the elements in [2^-16, 2^-15) past the gate below."""
+    g = torch.Generator().manual_seed(seed)
+    e = torch.where(torch.rand(n, generator=g) < 0.5, torch.rand(n, generator=g) * 3 - 17, torch.rand(n, generator=g) * 30 - 30)
+    x = (2.0 ** e.double() * (torch.randint(0, 2, (n,), generator=g) * 2 - 1)).float()
+    x[0] = 1.0
+    return x
+
+
+def split_element_gate(x, m):
+    """fp64 per-element bound on |y - x| for y = x through an identity filter of a split launch with bound m: the contract of the split
+    plus ONE fp32 rounding, that of adding the h and l products in the accumulator (the filter entry 1 is a single exact plane value,
+    the un-scaling by powers of two is exact).  The three-way bf16 split stays inside it too: 2^-24 for the three pieces, two roundings."""
+    ax = x.double().abs()
+    return torch.maximum(SPLIT_REL * ax, torch.full_like(ax, SPLIT_ABS * m)) + 2.0 ** -24 * ax
+
 
 def golden(name):
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name)

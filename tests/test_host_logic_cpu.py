@@ -180,3 +180,59 @@ def test_global_topk_reports_the_picked_count_when_the_minibatch_is_smaller_than
     assert k == 2 and counts == [2] and k == sum(counts)
     order, k = qdist.global_topk([0.1, 0.5, 0.4], 2)
     assert order.tolist() == [1, 2] and k == 2
+
+
+def test_f16_split_contract_in_numpy():
+    """csrc/common.h: qea_f16_scale / qea_split2_f16 emulated with numpy float16 casts.  For magnitudes spanning 2^-30 ... 1 of the bound
+    m (bounds just above / below a power of two, at gradient scale, near both ends of the supported range, and a bound 2^20 above the
+    data): |x - (h + l) / s| <= max(SPLIT_REL |x|, SPLIT_ABS m) for EVERY element — the relative part alone down to 2^-16 of m — and
+    both figures are reached (a 2^-24 relative / 2^-40 m absolute contract, as the comment once read, does not hold).  The derived
+    gates of tests/test_operand_scale_gpu.py rest on these two constants; an all-zero tensor gets scale 1."""
+    SPLIT_ABS, SPLIT_REL = H.SPLIT_ABS, H.SPLIT_REL
+
+    def f16_scale(m):
+        m = np.float32(m)
+        e = int((m.view(np.uint32) >> 23) & 0xFF)
+        se = 0 if (m == 0 or e == 0) else min(126, max(-126, 14 - (e - 127)))
+        return np.float32(2.0) ** np.float32(se)
+
+    def split2(x, s):
+        xs = x * s                                              # fp32
+        h = xs.astype(np.float16)
+        l = (xs - h.astype(np.float32)).astype(np.float16)
+        return h, l
+
+    assert f16_scale(0.0) == 1.0 and f16_scale(1e-45) == 1.0
+    rng = np.random.default_rng(0)
+    worst_rel = worst_abs = 0.0
+    for m in (1.0, np.nextafter(np.float32(2.0), np.float32(0)), 1.5, 4.7, 3e-9, 1.3 * 2.0 ** -100, 2.0 ** 100, 2.0 ** -112):
+        m = float(np.float32(m))
+        s = f16_scale(m)
+        assert 2.0 ** 14 <= m * float(s) < 2.0 ** 15
+        for top in (0.0, -20.0):                                 # data up to the bound / a bound 2^20 above the data
+            mag = 2.0 ** rng.uniform(-30.0, top, 400_000)
+            x = (mag * m * rng.choice([-1.0, 1.0], mag.size)).astype(np.float32)
+            x[:4] = np.float32([m, -m, 0.0, m * 2.0 ** -16]) if top == 0.0 else 0.0
+            h, l = split2(x, s)
+            assert np.isfinite(h).all() and np.isfinite(l).all()
+            err = np.abs((h.astype(np.float64) + l.astype(np.float64)) / float(s) - x.astype(np.float64))
+            ax = np.abs(x.astype(np.float64))
+            assert (err <= np.maximum(SPLIT_REL * ax, SPLIT_ABS * m)).all()
+            big = ax >= 2.0 ** -16 * m
+            if big.any():
+                assert (err[big] <= SPLIT_REL * ax[big]).all()
+                worst_rel = max(worst_rel, float((err[big] / ax[big]).max()))
+            worst_abs = max(worst_abs, float(err[~big].max()) / m)
+    assert worst_rel > 2.0 ** -24 and worst_abs > 2.0 ** -40      # the bounds are tight to a factor of two, not loose
+    # the element-level probe of tests/test_operand_scale_gpu.py (an operand through an identity filter), emulated: the right scale is
+    # inside helpers.split_element_gate, a scale one bit short (se = 13 - ...) is outside it — the mutation that every gate on a sum of
+    # many terms is blind to
+    x = H.split_probe_values(16384, 3).numpy()
+    for se_base, inside in ((14, True), (13, False)):
+        s = np.float32(2.0) ** np.float32(se_base)                # the bound is max |x| = 1.0
+        h, l = split2(x, s)
+        y = ((h.astype(np.float32) * s + l.astype(np.float32) * s) / s / s).astype(np.float32)   # hh + lh in an fp32 accumulator, un-scaled
+        err = np.abs(y.astype(np.float64) - x.astype(np.float64))
+        assert bool((err <= H.split_element_gate(torch.from_numpy(x), 1.0).numpy()).all()) == inside, se_base
+    # below the supported range (m < 2^-112) the scale stops at 2^126: the planes lose bits against m, silently
+    assert f16_scale(2.0 ** -120) == np.float32(2.0) ** 126
