@@ -223,7 +223,9 @@ typedef struct qea_wgrad_desc {
   int32_t accumulate; /* dw += result                                                     */
   int32_t splits;     /* 0 = auto                                                         */
   int32_t tile;       /* 0 = auto; 23 = the nine-tap LDS-halo kernel (with both abs-max pointers and R, C multiples of 64: its
-                       * producer / consumer form, round 4), 29 = the nine-tap kernel in the round-3 form (every wave stages) */
+                       * producer / consumer form, round 4), 29 = the nine-tap kernel in the round-3 form (every wave stages),
+                       * 6 = the fp32 LDS-halo kernel; every other id is a row of TILES in csrc/conv_wgrad.hip (route() there
+                       * holds the order of preference for tile 0) */
   /* ABI v6: when BOTH are non-NULL (device pointers to one float each: qea_absmax of p and of q) a launch that runs on a split tile —
    * the nine-tap LDS-halo kernel (3x3 pad 1 stride 1, PW in {16, 32k}, R and C multiples of 32) or tiles 20-22 — takes the TWO-way
    * fp16 split: three MFMAs per product instead of six (see qea_conv_desc.x_absmax).  Other launches ignore them. */
@@ -237,6 +239,10 @@ typedef struct qea_wgrad_desc {
 } qea_wgrad_desc;
 
 int qea_conv_wgrad_fuses_bias(const qea_wgrad_desc* d);
+/* Additive (no ABI bump).  1 when the launch this descriptor routes to reads p_absmax / q_absmax once both are set (the nine-tap kernel in
+ * any form, tiles 20-22), 0 when it would ignore them (the fp32 tiles): lets a caller skip the two qea_absmax passes nothing would read.
+ * Depends on the shape, the tile and the MFMA mode only, not on whether the pointers are set; needs no device pointers. */
+int qea_conv_wgrad_wants_absmax(const qea_wgrad_desc* d);
 size_t qea_conv_wgrad_workspace_bytes(const qea_wgrad_desc* d);
 int qea_conv_wgrad(const qea_wgrad_desc* d, void* stream);
 

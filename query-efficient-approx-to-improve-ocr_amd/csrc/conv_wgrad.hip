@@ -493,50 +493,139 @@ size_t slab_workspace_bytes(size_t slab_floats, int splits) {
   return b;
 }
 
-int tile_slots(int tile);  // workgroups of this tile's kernel the whole chip holds at once
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel; a refused reservation fails every launch of that kernel
+template <auto Kernel>
+int reserve_lds(size_t bytes) {
+  static const hipError_t rc = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (rc != hipSuccess) {
+    qea_set_error("qea_conv_wgrad: cannot reserve %zu bytes of LDS: %s", bytes, hipGetErrorString(rc));
+    return QEA_ERR_LAUNCH;
+  }
+  return QEA_OK;
+}
+
+// workgroups of this kernel the whole chip holds at once (asked once per kernel)
+template <auto Kernel>
+int resident_slots(int threads, size_t lds) {
+  static int slots = 0;
+  if (slots == 0) {
+    int per_cu = 0, dev = 0, cus = 0;
+    (void)reserve_lds<Kernel>(lds);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kernel, threads, lds) != hipSuccess || per_cu < 1) per_cu = 2;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+      cus = 256;
+    (void)hipGetLastError();
+    slots = per_cu * cus;
+  }
+  return slots;
+}
+
+template <int BR, int BC, int WR, int WC, int WK, int BKP>
+constexpr size_t lds_bytes() {
+  const size_t stage = (size_t)2 * BKP * (BR + BC) * sizeof(float);
+  const size_t red = (WK > 1) ? (size_t)WK * BR * BC * sizeof(float) : 0;
+  return red > stage ? red : stage;
+}
+
+template <int BR, int BC, int NPL = 3>
+constexpr size_t lds_bytes_bf3() {
+  return (size_t)2 * NPL * 16 * ((BR >= 128 ? BR : BR + 32) + (BC >= 128 ? BC : BC + 32)) * 2;
+}
+
+template <auto Kernel, size_t LDS>
+int launch_tile(const WgArgs& a, hipStream_t s) {
+  const int rc = reserve_lds<Kernel>(LDS);
+  if (rc != QEA_OK) return rc;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)a.tiles * (unsigned)a.splits), dim3(256), LDS, s, a);
+  return QEA_OK;
+}
+
+template <auto Kernel, size_t LDS>
+int tile_slots() { return resident_slots<Kernel>(256, LDS); }
+
+template <int BR, int BC, int NPL>
+int launch_bf3_(const WgArgs& a, hipStream_t s) { return launch_tile<wgrad_bf3_kernel<BR, BC, 2, 2, NPL>, lds_bytes_bf3<BR, BC, NPL>()>(a, s); }
+
+template <int BR, int BC>
+int launch_bf3(const WgArgs& a, hipStream_t s) {
+  // both abs-max values given: the two-way fp16 split
+  return (a.pmax && a.qmax) ? launch_bf3_<BR, BC, 2>(a, s) : launch_bf3_<BR, BC, 3>(a, s);
+}
+
+// THE list of generic (per-tap GEMM) tiles: what an id means, how it is launched and how many of its workgroups the chip
+// holds are all read from this table, so a tile is added, dropped or re-shaped in one row.
+struct Tile {
+  int id, br, bc;
+  int (*launch)(const WgArgs&, hipStream_t);
+  int (*slots)();
+};
+
+template <int ID, int BR, int BC, int WR, int WC, int WK, int BKP = 32>
+constexpr Tile f32_tile() {   // fp32 MFMA: WR x WC waves per tile, WK-way K split inside the workgroup, BKP pixels per stage
+  return {ID, BR, BC, launch_tile<wgrad_kernel<BR, BC, WR, WC, WK, BKP>, lds_bytes<BR, BC, WR, WC, WK, BKP>()>,
+          tile_slots<wgrad_kernel<BR, BC, WR, WC, WK, BKP>, lds_bytes<BR, BC, WR, WC, WK, BKP>()>};
+}
+
+template <int ID, int BR, int BC>
+constexpr Tile bf3_tile() {   // split-bf16 (two-way fp16 with both abs-max pointers); slots are those of the three-plane form
+  return {ID, BR, BC, launch_bf3<BR, BC>, tile_slots<wgrad_bf3_kernel<BR, BC, 2, 2, 3>, lds_bytes_bf3<BR, BC, 3>()>};
+}
+
+constexpr int FIRST_SPLIT_TILE = 20;   // ids from here on read p_absmax / q_absmax
+
+const Tile TILES[] = {
+    f32_tile<1, 128, 128, 2, 2, 1>(),
+    f32_tile<2, 64, 64, 1, 1, 4>(),
+    f32_tile<3, 32, 32, 1, 1, 4>(),
+    f32_tile<4, 32, 64, 1, 1, 4>(),
+    f32_tile<5, 64, 32, 1, 1, 4>(),
+    f32_tile<7, 128, 64, 2, 2, 1>(),
+    f32_tile<8, 64, 128, 2, 2, 1>(),
+    f32_tile<9, 128, 128, 2, 2, 1, 16>(),   // 16-pixel stages: half the LDS per workgroup
+    f32_tile<10, 128, 64, 2, 2, 1, 16>(),
+    f32_tile<11, 64, 128, 2, 2, 1, 16>(),
+    bf3_tile<20, 128, 128>(),
+    bf3_tile<21, 128, 64>(),
+    bf3_tile<22, 64, 128>(),
+};
+
+const Tile* find_tile(int id) {
+  for (const Tile& t : TILES)
+    if (t.id == id) return &t;
+  return nullptr;
+}
+
+// the generic tile an automatic launch (tile 0) takes
+int auto_tile(int R, int C) {
+  // 16-pixel stages (tiles 9-11): half the LDS of the 32-pixel ones, more resident workgroups, +3-5 % (MI355X);
+  // tiles 20-22 are their split-bf16 forms (default unless QEA_MFMA=f32)
+  const bool bf3 = qea_split_bf16_enabled();
+  if (R >= 128 && C >= 128) return bf3 ? 20 : 9;
+  if (R >= 128 && C == 64) return bf3 ? 21 : 10;
+  if (R == 64 && C >= 128) return bf3 ? 22 : 11;
+  if (R <= 32 && C <= 32) return 3;
+  if (R <= 32) return 4;
+  if (C <= 32) return 5;
+  return 2;
+}
 
 struct Plan {
-  int tile;  // 1/9: 128x128  2: 64x64 (K-split)  3: 32x32 (K-split)  4: 32x64  5: 64x32  7/10: 128x64  8/11: 64x128
-  int br, bc;
+  const Tile* tile;  // row of TILES
   int splits, chunk, tiles, r_tiles, c_tiles;
 };
 
-Plan make_plan(const qea_wgrad_desc* d) {
+Plan make_plan(const qea_wgrad_desc* d, const Tile* t) {
   Plan p;
-  const int R = d->R, C = d->C;
-  int tile = d->tile;
-  if (tile == 0) {
-    // 16-pixel stages (tiles 9-11): half the LDS of the 32-pixel ones, more resident workgroups, +3-5 % (MI355X);
-    // tiles 20-22 are their split-bf16 forms (default unless QEA_MFMA=f32)
-    const bool bf3 = qea_split_bf16_enabled();
-    if (R >= 128 && C >= 128) tile = bf3 ? 20 : 9;
-    else if (R >= 128 && C == 64) tile = bf3 ? 21 : 10;
-    else if (R == 64 && C >= 128) tile = bf3 ? 22 : 11;
-    else if (R <= 32 && C <= 32) tile = 3;
-    else if (R <= 32) tile = 4;
-    else if (C <= 32) tile = 5;
-    else tile = 2;
-  }
-  p.tile = tile;
-  switch (tile) {
-    case 1: p.br = 128; p.bc = 128; break;
-    case 2: p.br = 64; p.bc = 64; break;
-    case 3: p.br = 32; p.bc = 32; break;
-    case 4: p.br = 32; p.bc = 64; break;
-    case 7: case 10: case 21: p.br = 128; p.bc = 64; break;
-    case 8: case 11: case 22: p.br = 64; p.bc = 128; break;
-    case 9: case 20: p.br = 128; p.bc = 128; break;
-    default: p.br = 64; p.bc = 32; break;
-  }
-  p.r_tiles = qea_cdiv(R, p.br);
-  p.c_tiles = qea_cdiv(C, p.bc);
+  p.tile = t;
+  p.r_tiles = qea_cdiv(d->R, t->br);
+  p.c_tiles = qea_cdiv(d->C, t->bc);
   p.tiles = p.r_tiles * p.c_tiles * d->KH * d->KW;
   const long long M = (long long)d->B * d->PH * d->PW;
   int splits = d->splits;
   if (splits <= 0) {
     // fill the chip a whole number of times: the workgroups are equally long, so a grid just past a multiple of
     // the resident-workgroup count leaves a nearly empty last round (2052 workgroups on 512 slots: 20 % idle)
-    const int slots = tile_slots(tile);
+    const int slots = t->slots();
     const int rounds = (2048 + slots / 2) / slots > 0 ? (2048 + slots / 2) / slots : 1;
     splits = rounds * slots / p.tiles;
     const long long max_by_m = (M + 4 * BKP_MAX - 1) / (4 * BKP_MAX);  // at least 4 stages per split
@@ -552,99 +641,22 @@ Plan make_plan(const qea_wgrad_desc* d) {
   return p;
 }
 
-template <int BR, int BC, int WR, int WC, int WK, int BKP>
-constexpr size_t lds_bytes() {
-  const size_t stage = (size_t)2 * BKP * (BR + BC) * sizeof(float);
-  const size_t red = (WK > 1) ? (size_t)WK * BR * BC * sizeof(float) : 0;
-  return red > stage ? red : stage;
-}
-
-template <int BR, int BC, int WR, int WC, int WK, int BKP = 32>
-void launch(const WgArgs& a, hipStream_t s) {
-  constexpr size_t lds = lds_bytes<BR, BC, WR, WC, WK, BKP>();
-  auto kern = wgrad_kernel<BR, BC, WR, WC, WK, BKP>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)a.tiles * (unsigned)a.splits), dim3(256), lds, s, a);
-}
-
-template <int BR, int BC, int WR, int WC, int WK, int BKP = 32>
-int slots_of() {
-  static int slots = 0;
-  if (slots == 0) {
-    int per_cu = 0, dev = 0, cus = 0;
-    constexpr size_t lds = lds_bytes<BR, BC, WR, WC, WK, BKP>();
-    auto kern = wgrad_kernel<BR, BC, WR, WC, WK, BKP>;
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess || per_cu < 1) per_cu = 2;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-      cus = 256;
-    (void)hipGetLastError();
-    slots = per_cu * cus;
-  }
-  return slots;
-}
-
-template <int BR, int BC, int NPL = 3>
-constexpr size_t lds_bytes_bf3() {
-  return (size_t)2 * NPL * 16 * ((BR >= 128 ? BR : BR + 32) + (BC >= 128 ? BC : BC + 32)) * 2;
-}
-
-template <int BR, int BC, int WR, int WC, int NPL>
-void launch_bf3_(const WgArgs& a, hipStream_t s) {
-  constexpr size_t lds = lds_bytes_bf3<BR, BC, NPL>();
-  auto kern = wgrad_bf3_kernel<BR, BC, WR, WC, NPL>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)a.tiles * (unsigned)a.splits), dim3(256), lds, s, a);
-}
-
-template <int BR, int BC, int WR, int WC>
-void launch_bf3(const WgArgs& a, hipStream_t s) {
-  if (a.pmax && a.qmax) launch_bf3_<BR, BC, WR, WC, 2>(a, s);   // both abs-max values given: the two-way fp16 split
-  else launch_bf3_<BR, BC, WR, WC, 3>(a, s);
-}
-
-template <int BR, int BC, int WR, int WC>
-int slots_of_bf3() {
-  static int slots = 0;
-  if (slots == 0) {
-    int per_cu = 0, dev = 0, cus = 0;
-    constexpr size_t lds = lds_bytes_bf3<BR, BC>();
-    auto kern = wgrad_bf3_kernel<BR, BC, WR, WC>;
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess || per_cu < 1) per_cu = 2;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-      cus = 256;
-    (void)hipGetLastError();
-    slots = per_cu * cus;
-  }
-  return slots;
-}
-
-int tile_slots(int tile) {
-  switch (tile) {
-    case 20: return slots_of_bf3<128, 128, 2, 2>();
-    case 21: return slots_of_bf3<128, 64, 2, 2>();
-    case 22: return slots_of_bf3<64, 128, 2, 2>();
-    case 1: return slots_of<128, 128, 2, 2, 1>();
-    case 2: return slots_of<64, 64, 1, 1, 4>();
-    case 3: return slots_of<32, 32, 1, 1, 4>();
-    case 4: return slots_of<32, 64, 1, 1, 4>();
-    case 5: return slots_of<64, 32, 1, 1, 4>();
-    case 7: return slots_of<128, 64, 2, 2, 1>();
-    case 8: return slots_of<64, 128, 2, 2, 1>();
-    case 9: return slots_of<128, 128, 2, 2, 1, 16>();
-    case 10: return slots_of<128, 64, 2, 2, 1, 16>();
-    case 11: return slots_of<64, 128, 2, 2, 1, 16>();
-    default: return 512;
-  }
+// slabs > 0: the kernel writes one partial dW per split into the workspace; 0: it writes dW itself
+int launch_generic(const qea_wgrad_desc* d, const Plan& p, int slabs, hipStream_t s) {
+  WgArgs a;
+  a.p = d->p; a.q = d->q;
+  a.B = d->B; a.PH = d->PH; a.PW = d->PW; a.QH = d->QH; a.QW = d->QW; a.R = d->R; a.C = d->C;
+  a.KH = d->KH; a.KW = d->KW; a.pad_h = d->pad_h; a.pad_w = d->pad_w; a.stride_h = d->stride_h; a.stride_w = d->stride_w;
+  a.ldp = d->ldp; a.ldq = d->ldq;
+  a.M = d->B * d->PH * d->PW;
+  a.chunk = p.chunk; a.splits = p.splits;
+  a.r_tiles = p.r_tiles; a.c_tiles = p.c_tiles; a.tiles = p.tiles;
+  a.slab = (long long)d->R * d->KH * d->KW * d->C;
+  a.out = slabs ? (float*)d->workspace : d->dw;
+  a.accumulate = slabs ? 0 : d->accumulate;
+  a.pmax = d->p_absmax;
+  a.qmax = d->q_absmax;
+  return p.tile->launch(a, s);
 }
 
 int validate(const qea_wgrad_desc* d, const char* who) {
@@ -792,15 +804,20 @@ HaloPlan halo_plan(const qea_wgrad_desc* d) {
 }
 
 template <int R, int C, int TH>
-void launch_halo(const qea_wgrad_desc* d, const HaloPlan& h, hipStream_t s) {
+int launch_halo_(const qea_wgrad_desc* d, const HaloPlan& h, hipStream_t s) {
   constexpr size_t lds = ((size_t)TH * 32 * R + (size_t)(TH + 2) * 34 * C) * sizeof(float);
-  auto kern = wgrad_halo_kernel<R, C, TH>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(h.grid), dim3(256), lds, s, d->p, d->q, (float*)d->workspace, d->B, d->PH, d->PW, d->ldp, d->ldq, h.n_tiles);
+  const int rc = reserve_lds<wgrad_halo_kernel<R, C, TH>>(lds);
+  if (rc != QEA_OK) return rc;
+  hipLaunchKernelGGL((wgrad_halo_kernel<R, C, TH>), dim3(h.grid), dim3(256), lds, s, d->p, d->q, (float*)d->workspace, d->B, d->PH, d->PW, d->ldp,
+                     d->ldq, h.n_tiles);
+  return QEA_OK;
+}
+
+int launch_halo(const qea_wgrad_desc* d, const HaloPlan& h, hipStream_t s) {   // TH as in halo_plan
+  if (d->R == 32 && d->C == 32) return launch_halo_<32, 32, 8>(d, h, s);
+  if (d->R == 32 && d->C == 64) return launch_halo_<32, 64, 4>(d, h, s);
+  if (d->R == 64 && d->C == 32) return launch_halo_<64, 32, 4>(d, h, s);
+  return launch_halo_<64, 64, 2>(d, h, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1490,21 +1507,13 @@ Halo9Plan halo9_plan(const qea_wgrad_desc* d) {
   return h;
 }
 
-// the 32- and 64-channel layers are taken by both halo kernels: the split-bf16 nine-tap form wins unless QEA_MFMA=f32
-bool prefer_halo9(const qea_wgrad_desc* d) { return qea_split_bf16_enabled() && halo9_plan(d).ok; }
-
-template <int SW, int RB, int CB, int NPL = 3>
+template <int SW, int RB, int CB, int NPL>
 int launch_halo9_(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s) {
   constexpr size_t lds = (size_t)NPL * (64 * RB + H9_HP_MAX * CB) * 2;
-  const long long grid = (long long)h.r_blks * h.c_blks * h.splits;
-  auto kern = wgrad_halo9_bf3_kernel<SW, RB, CB, NPL>;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_wgrad: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, s, d->p, d->q, (float*)d->workspace, d->B, d->PH, d->PW, d->R, d->C, d->ldp, d->ldq, h,
-                     d->p_absmax, d->q_absmax);
+  const int rc = reserve_lds<wgrad_halo9_bf3_kernel<SW, RB, CB, NPL>>(lds);
+  if (rc != QEA_OK) return rc;
+  hipLaunchKernelGGL((wgrad_halo9_bf3_kernel<SW, RB, CB, NPL>), dim3((unsigned)((long long)h.r_blks * h.c_blks * h.splits)), dim3(256), lds, s, d->p, d->q,
+                     (float*)d->workspace, d->B, d->PH, d->PW, d->R, d->C, d->ldp, d->ldq, h, d->p_absmax, d->q_absmax);
   return QEA_OK;
 }
 
@@ -1514,162 +1523,135 @@ int launch_halo9_any(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s)
   return (d->p_absmax && d->q_absmax) ? launch_halo9_<SW, RB, CB, 2>(d, h, s) : launch_halo9_<SW, RB, CB, 3>(d, h, s);
 }
 
-template <int SW>
-int launch_halo9_spec(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s, double* bias_ws) {
-  constexpr size_t lds = halo9_spec_lds<SW>();
-  const long long grid = (long long)h.r_blks * h.c_blks * h.splits;
-  auto kern = wgrad_halo9_spec_kernel<SW>;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_wgrad: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, d->p, d->q, (float*)d->workspace, d->B, d->PH, d->PW, d->R, d->C, d->ldp, d->ldq, h,
-                     d->p_absmax, d->q_absmax, bias_ws);
+// the producer / consumer forms: the ring kernel for 32-pixel-wide tiles, wgrad_halo9_spec_kernel<16> for the 16-wide ones
+template <auto Kernel, size_t LDS>
+int launch_halo9_pc(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s, double* bias_ws) {
+  const int rc = reserve_lds<Kernel>(LDS);
+  if (rc != QEA_OK) return rc;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)((long long)h.r_blks * h.c_blks * h.splits)), dim3(512), LDS, s, d->p, d->q, (float*)d->workspace, d->B, d->PH, d->PW,
+                     d->R, d->C, d->ldp, d->ldq, h, d->p_absmax, d->q_absmax, bias_ws);
   return QEA_OK;
 }
 
-int launch_halo9_ring(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s, double* bias_ws) {
-  constexpr size_t lds = halo9_ring_lds();
-  const long long grid = (long long)h.r_blks * h.c_blks * h.splits;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)wgrad_halo9_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_wgrad: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(wgrad_halo9_ring_kernel, dim3((unsigned)grid), dim3(512), lds, s, d->p, d->q, (float*)d->workspace, d->B, d->PH, d->PW, d->R, d->C,
-                     d->ldp, d->ldq, h, d->p_absmax, d->q_absmax, bias_ws);
-  return QEA_OK;
-}
-
-int launch_halo9(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s, double* bias_ws = nullptr) {
-  if (h.spec) return h.sw == 32 ? launch_halo9_ring(d, h, s, bias_ws) : launch_halo9_spec<16>(d, h, s, bias_ws);
+int launch_halo9(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s, double* bias_ws) {
+  if (h.spec)
+    return h.sw == 32 ? launch_halo9_pc<wgrad_halo9_ring_kernel, halo9_ring_lds()>(d, h, s, bias_ws)
+                      : launch_halo9_pc<wgrad_halo9_spec_kernel<16>, halo9_spec_lds<16>()>(d, h, s, bias_ws);
   if (h.sw == 32) return h.rb == 64 ? launch_halo9_any<32, 64, 64>(d, h, s) : launch_halo9_any<32, 32, 32>(d, h, s);
   return h.rb == 64 ? launch_halo9_any<16, 64, 64>(d, h, s) : launch_halo9_any<16, 32, 32>(d, h, s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The route: which kernel family runs a descriptor, on how many slabs, with how much workspace.  Every entry point below
+// asks this one function, so the queries cannot disagree with the launch.  Order of preference:
+//   1. NINE_TAP  (tile 0 in split-bf16 mode, or tile 23 / 29) where halo9_plan takes the shape; a forced 23 / 29 that does not fit fails;
+//   2. HALO_F32  (tile 0 otherwise, or tile 6) where halo_plan takes the shape; a forced 6 that does not fit fails;
+//   3. GENERIC   the per-tap GEMM tiles of TILES: the forced id, or auto_tile() for tile 0.
+// The family does not depend on p_absmax / q_absmax / dbias being set: of the plans only Halo9Plan::spec and ::splits do.
+// ---------------------------------------------------------------------------------------------
+enum Family { GENERIC, HALO_F32, NINE_TAP };
+
+struct Route {
+  Family family;
+  union {   // the family's plan
+    Plan generic;
+    HaloPlan halo;
+    Halo9Plan nine;
+  };
+  size_t slab_floats;      // one partial dW
+  int n_slabs;             // partial dWs in the workspace, summed by reduce_slabs; 0: the kernel writes dW itself
+  size_t slab_bytes;       // the slabs (and the group partials of a two-level reduction): the fp64 bias partials sit behind them
+  size_t bias_bytes;       // 0 unless the producer / consumer form runs with dbias set
+  size_t workspace_bytes;  // what qea_conv_wgrad_workspace_bytes reports
+  bool fuses_bias;         // the launch can take dbias
+  bool wants_absmax;       // the launch reads p_absmax / q_absmax when both are set
+  int split_tag;           // qea_prof_end: 0 = fp32 MFMA, 1 = three-way bf16 split, 2 = two-way fp16 split
+  const char* error;       // printf format (one int: the tile) of a forced tile that cannot run; null = fine
+};
+
+Route route(const qea_wgrad_desc* d) {
+  Route r = {};
+  const int tile = d->tile;
+  const int both_tag = (d->p_absmax && d->q_absmax) ? 2 : 1;
+  r.slab_floats = (size_t)d->R * d->KH * d->KW * d->C;
+  if ((tile == 0 && qea_split_bf16_enabled()) || tile == 23 || tile == 29) {
+    r.nine = halo9_plan(d);
+    if (r.nine.ok) {
+      r.family = NINE_TAP;
+      r.n_slabs = r.nine.splits * r.nine.wk;
+      r.fuses_bias = r.nine.spec;
+      if (r.nine.spec && d->dbias) r.bias_bytes = (size_t)r.nine.splits * 4 * d->R * sizeof(double);   // one row per (split, staging wave)
+      r.wants_absmax = true;
+      r.split_tag = both_tag;
+    } else if (tile != 0) {
+      r.error = "qea_conv_wgrad: tile 23 (nine-tap split-bf16) needs a 3x3 pad-1 stride-1 conv, R,C multiples of 64, PW in {16, 32k}";
+    }
+  }
+  if (r.family == GENERIC && !r.error && (tile == 0 || tile == 6)) {
+    r.halo = halo_plan(d);
+    if (r.halo.ok) {
+      r.family = HALO_F32;
+      r.n_slabs = r.halo.grid * r.halo.wk;
+    } else if (tile != 0) {
+      r.error = "qea_conv_wgrad: tile 6 (LDS-halo) needs a 3x3 pad-1 stride-1 conv with R,C in {32,64}, PW %% 32 == 0";
+    }
+  }
+  if (r.family == GENERIC && !r.error) {
+    const Tile* t = find_tile(tile ? tile : auto_tile(d->R, d->C));
+    if (!t) {
+      r.error = "qea_conv_wgrad: unknown tile %d";
+      return r;
+    }
+    r.generic = make_plan(d, t);
+    r.n_slabs = r.generic.splits > 1 ? r.generic.splits : 0;
+    r.wants_absmax = t->id >= FIRST_SPLIT_TILE;
+    r.split_tag = r.wants_absmax ? both_tag : 0;
+  }
+  r.slab_bytes = r.n_slabs ? slab_workspace_bytes(r.slab_floats, r.n_slabs) : 0;
+  r.workspace_bytes = r.slab_bytes + r.bias_bytes;
+  return r;
+}
+
+// the queries take descriptors without pointers; these are the fields the plans divide by
+bool has_dims(const qea_wgrad_desc* d) { return d && d->R > 0 && d->C > 0 && d->B > 0; }
+
 }  // namespace
 
-extern "C" int qea_conv_wgrad_fuses_bias(const qea_wgrad_desc* d) {
-  if (!d || d->R <= 0 || d->C <= 0 || d->B <= 0) return 0;
-  if (!((d->tile == 0 && qea_split_bf16_enabled()) || d->tile == 23)) return 0;
-  const Halo9Plan h9 = halo9_plan(d);
-  return (h9.ok && h9.spec) ? 1 : 0;
-}
+extern "C" int qea_conv_wgrad_fuses_bias(const qea_wgrad_desc* d) { return (has_dims(d) && route(d).fuses_bias) ? 1 : 0; }
 
-extern "C" size_t qea_conv_wgrad_workspace_bytes(const qea_wgrad_desc* d) {
-  if (!d || d->R <= 0 || d->C <= 0 || d->B <= 0) return 0;
-  if ((d->tile == 0 && !prefer_halo9(d)) || d->tile == 6) {
-    const HaloPlan h = halo_plan(d);
-    if (h.ok) return slab_workspace_bytes((size_t)d->R * 9 * d->C, h.grid * h.wk);
-  }
-  if ((d->tile == 0 && qea_split_bf16_enabled()) || d->tile == 23 || d->tile == 29) {
-    const Halo9Plan h9 = halo9_plan(d);
-    if (h9.ok) return slab_workspace_bytes((size_t)d->R * 9 * d->C, h9.splits * h9.wk) + ((h9.spec && d->dbias) ? (size_t)h9.splits * 4 * d->R * sizeof(double) : 0);
-  }
-  const Plan p = make_plan(d);
-  if (p.splits <= 1) return 0;
-  return slab_workspace_bytes((size_t)d->R * d->KH * d->KW * d->C, p.splits);
-}
+extern "C" int qea_conv_wgrad_wants_absmax(const qea_wgrad_desc* d) { return (has_dims(d) && route(d).wants_absmax) ? 1 : 0; }
+
+extern "C" size_t qea_conv_wgrad_workspace_bytes(const qea_wgrad_desc* d) { return has_dims(d) ? route(d).workspace_bytes : 0; }
 
 extern "C" int qea_conv_wgrad(const qea_wgrad_desc* d, void* stream) {
   int rc = validate(d, "qea_conv_wgrad");
   if (rc != QEA_OK) return rc;
-  if ((d->tile == 0 && !prefer_halo9(d)) || d->tile == 6) {
-    const HaloPlan h = halo_plan(d);
-    if (h.ok) {
-      const size_t slab = (size_t)d->R * 9 * d->C;
-      const size_t need_h = slab_workspace_bytes(slab, h.grid * h.wk);
-      QEA_REQUIRE(d->workspace && d->workspace_bytes >= need_h && ((uintptr_t)d->workspace & 15) == 0,
-                  "qea_conv_wgrad: workspace of %zu bytes required, %zu given", need_h, (size_t)d->workspace_bytes);
-      hipStream_t hs = (hipStream_t)stream;
-      qea_prof_begin(QEA_PROF_CONV_WGRAD, hs);
-      if (d->R == 32 && d->C == 32) launch_halo<32, 32, 8>(d, h, hs);
-      else if (d->R == 32 && d->C == 64) launch_halo<32, 64, 4>(d, h, hs);
-      else if (d->R == 64 && d->C == 32) launch_halo<64, 32, 4>(d, h, hs);
-      else launch_halo<64, 64, 2>(d, h, hs);
-      reduce_slabs((float*)d->workspace, d->dw, (long long)slab / 4, h.grid * h.wk, d->accumulate, hs);
-      // algorithmic bytes: dY once + X once + dW once
-      qea_prof_end(QEA_PROF_CONV_WGRAD, hs, 2.0 * d->B * d->PH * (double)d->PW * (double)slab,
-                   4.0 * ((double)d->B * d->PH * d->PW * d->R + (double)d->B * d->QH * d->QW * d->C + (double)slab));
-      QEA_CHECK_LAUNCH();
-      return QEA_OK;
-    }
-    QEA_REQUIRE(d->tile == 0, "qea_conv_wgrad: tile 6 (LDS-halo) needs a 3x3 pad-1 stride-1 conv with R,C in {32,64}, PW %% 32 == 0");
-  }
-  if ((d->tile == 0 && qea_split_bf16_enabled()) || d->tile == 23 || d->tile == 29) {
-    const Halo9Plan h9 = halo9_plan(d);
-    if (h9.ok) {
-      const size_t slab = (size_t)d->R * 9 * d->C;
-      const size_t need_dw = slab_workspace_bytes(slab, h9.splits * h9.wk);
-      const bool fused_bias = h9.spec && d->dbias;
-      const size_t need9 = need_dw + (fused_bias ? (size_t)h9.splits * 4 * d->R * sizeof(double) : 0);
-      QEA_REQUIRE(d->workspace && d->workspace_bytes >= need9 && ((uintptr_t)d->workspace & 15) == 0,
-                  "qea_conv_wgrad: workspace of %zu bytes required, %zu given", need9, (size_t)d->workspace_bytes);
-      QEA_REQUIRE(!d->dbias || h9.spec, "qea_conv_wgrad: dbias is taken by the producer / consumer nine-tap form only (ask qea_conv_wgrad_fuses_bias first)");
-      hipStream_t hs = (hipStream_t)stream;
-      qea_prof_begin(QEA_PROF_CONV_WGRAD, hs);
-      double* bias_ws = fused_bias ? reinterpret_cast<double*>(reinterpret_cast<char*>(d->workspace) + need_dw) : nullptr;
-      rc = launch_halo9(d, h9, hs, bias_ws);
-      if (rc != QEA_OK) {
-        qea_prof_abort(QEA_PROF_CONV_WGRAD);
-        return rc;
-      }
-      reduce_slabs((float*)d->workspace, d->dw, (long long)slab / 4, h9.splits * h9.wk, d->accumulate, hs);
-      if (fused_bias) hipLaunchKernelGGL(bias_finalize_kernel, dim3(qea_cdiv(d->R, 4)), dim3(256), 0, hs, (const double*)bias_ws, h9.splits * 4, d->R, d->dbias, d->accumulate);
-      qea_prof_end(QEA_PROF_CONV_WGRAD, hs, 2.0 * d->B * d->PH * (double)d->PW * (double)slab,
-                   4.0 * ((double)d->B * d->PH * d->PW * d->R + (double)d->B * d->QH * d->QW * d->C + (double)slab),
-                   (d->p_absmax && d->q_absmax) ? 2 : 1);
-      QEA_CHECK_LAUNCH();
-      return QEA_OK;
-    }
-    QEA_REQUIRE(d->tile == 0, "qea_conv_wgrad: tile 23 (nine-tap split-bf16) needs a 3x3 pad-1 stride-1 conv, R,C multiples of 64, PW in {16, 32k}");
-  }
-  QEA_REQUIRE(!d->dbias, "qea_conv_wgrad: dbias is taken by the producer / consumer nine-tap form only (ask qea_conv_wgrad_fuses_bias first)");
-  const Plan p = make_plan(d);
-  const size_t need = (p.splits > 1) ? slab_workspace_bytes((size_t)d->R * d->KH * d->KW * d->C, p.splits) : 0;
+  const Route r = route(d);
+  QEA_REQUIRE(!r.error, r.error, d->tile);
+  // checked against the bytes this launch touches, not against the figure the query reports: a query that under-reports is refused here
+  const size_t need = r.slab_bytes + r.bias_bytes;
   QEA_REQUIRE(need == 0 || (d->workspace && d->workspace_bytes >= need && ((uintptr_t)d->workspace & 15) == 0),
               "qea_conv_wgrad: workspace of %zu bytes required, %zu given", need, (size_t)d->workspace_bytes);
-
-  WgArgs a;
-  a.p = d->p; a.q = d->q;
-  a.B = d->B; a.PH = d->PH; a.PW = d->PW; a.QH = d->QH; a.QW = d->QW; a.R = d->R; a.C = d->C;
-  a.KH = d->KH; a.KW = d->KW; a.pad_h = d->pad_h; a.pad_w = d->pad_w; a.stride_h = d->stride_h; a.stride_w = d->stride_w;
-  a.ldp = d->ldp; a.ldq = d->ldq;
-  a.M = d->B * d->PH * d->PW;
-  a.chunk = p.chunk; a.splits = p.splits;
-  a.r_tiles = p.r_tiles; a.c_tiles = p.c_tiles; a.tiles = p.tiles;
-  a.slab = (long long)d->R * d->KH * d->KW * d->C;
-  a.out = (p.splits > 1) ? (float*)d->workspace : d->dw;
-  a.accumulate = (p.splits > 1) ? 0 : d->accumulate;
-  a.pmax = d->p_absmax;
-  a.qmax = d->q_absmax;
-
+  QEA_REQUIRE(!d->dbias || r.bias_bytes, "qea_conv_wgrad: dbias is taken by the producer / consumer nine-tap form only (ask qea_conv_wgrad_fuses_bias first)");
   hipStream_t s = (hipStream_t)stream;
   qea_prof_begin(QEA_PROF_CONV_WGRAD, s);
-  switch (p.tile) {
-    case 1: launch<128, 128, 2, 2, 1>(a, s); break;
-    case 2: launch<64, 64, 1, 1, 4>(a, s); break;
-    case 3: launch<32, 32, 1, 1, 4>(a, s); break;
-    case 4: launch<32, 64, 1, 1, 4>(a, s); break;
-    case 5: launch<64, 32, 1, 1, 4>(a, s); break;
-    case 7: launch<128, 64, 2, 2, 1>(a, s); break;
-    case 8: launch<64, 128, 2, 2, 1>(a, s); break;
-    case 9: launch<128, 128, 2, 2, 1, 16>(a, s); break;   // 16-pixel stages: half the LDS per workgroup
-    case 10: launch<128, 64, 2, 2, 1, 16>(a, s); break;
-    case 11: launch<64, 128, 2, 2, 1, 16>(a, s); break;
-    case 20: launch_bf3<128, 128, 2, 2>(a, s); break;      // split-bf16 forms
-    case 21: launch_bf3<128, 64, 2, 2>(a, s); break;
-    case 22: launch_bf3<64, 128, 2, 2>(a, s); break;
-    default:
-      qea_prof_abort(QEA_PROF_CONV_WGRAD);
-      qea_set_error("qea_conv_wgrad: unknown tile %d", p.tile);
-      return QEA_ERR_INVALID;
+  double* bias_ws = r.bias_bytes ? reinterpret_cast<double*>(reinterpret_cast<char*>(d->workspace) + r.slab_bytes) : nullptr;
+  switch (r.family) {
+    case HALO_F32: rc = launch_halo(d, r.halo, s); break;
+    case NINE_TAP: rc = launch_halo9(d, r.nine, s, bias_ws); break;
+    case GENERIC: rc = launch_generic(d, r.generic, r.n_slabs, s); break;
   }
-  if (p.splits > 1) reduce_slabs((float*)d->workspace, d->dw, a.slab / 4, p.splits, d->accumulate, s);
-  qea_prof_end(QEA_PROF_CONV_WGRAD, s, 2.0 * a.M * (double)a.slab,
-               4.0 * ((double)a.M * d->R + (double)d->B * d->QH * d->QW * d->C + (double)a.slab),
-               p.tile >= 20 ? ((a.pmax && a.qmax) ? 2 : 1) : 0);
+  if (rc != QEA_OK) {
+    qea_prof_abort(QEA_PROF_CONV_WGRAD);
+    return rc;
+  }
+  if (r.n_slabs) reduce_slabs((float*)d->workspace, d->dw, (long long)r.slab_floats / 4, r.n_slabs, d->accumulate, s);
+  if (bias_ws)
+    hipLaunchKernelGGL(bias_finalize_kernel, dim3(qea_cdiv(d->R, 4)), dim3(256), 0, s, (const double*)bias_ws, r.nine.splits * 4, d->R, d->dbias, d->accumulate);
+  // algorithmic bytes: P once + Q once + dW once
+  const double M = (double)d->B * d->PH * d->PW;
+  qea_prof_end(QEA_PROF_CONV_WGRAD, s, 2.0 * M * (double)r.slab_floats, 4.0 * (M * d->R + (double)d->B * d->QH * d->QW * d->C + (double)r.slab_floats),
+               r.split_tag);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

@@ -40,6 +40,9 @@ class ConvDesc(C.Structure):
 
 
 class WgradDesc(C.Structure):
+    """qea_wgrad_desc.  Three queries read it without device pointers and all answer from the one route qea_conv_wgrad itself takes:
+    qea_conv_wgrad_wants_absmax (does the launch read p_absmax / q_absmax?), qea_conv_wgrad_fuses_bias (may dbias be set?) and
+    qea_conv_wgrad_workspace_bytes (ask last: the answer depends on the abs-max pointers and dbias)."""
     _fields_ = [
         ("p", _fp), ("q", _fp), ("dw", _fp), ("workspace", _fp), ("workspace_bytes", C.c_size_t),
         ("B", _i32), ("PH", _i32), ("PW", _i32), ("QH", _i32), ("QW", _i32), ("R", _i32), ("C", _i32),

@@ -136,3 +136,64 @@ def test_wgrad_bias_gradient_rides_with_the_staging_waves(B, H, W, Cin, Cout, sp
     db2 = torch.full((Cout,), base, device="cuda")
     ops.conv_wgrad(dy, x, dw1.fill_(base), dbias=db2, **kw)
     assert torch.equal(db, db2)
+
+
+# (B, H, W, Cin, Cout, K, tile) -> does the launch read p_absmax / q_absmax?  Written down from the kernels each descriptor reaches
+# (csrc/conv_wgrad.hip): the nine-tap kernels and wgrad_bf3_kernel (tiles 20-22) take the two-way fp16 split from the two slots;
+# wgrad_kernel (tiles 1-5, 7-11), wgrad_halo_kernel (tile 6) never load them.
+_ABSMAX_READ = (
+    [((2, 8, 32, 128, 128, 3, t), 1) for t in (0, 23, 29)]        # nine-tap, 64-wide blocks: producer / consumer form (0, 23), round-3 form (29)
+    + [((2, 8, 32, 64, 32, 3, 23), 1)]                             # nine-tap, 32-wide blocks
+    + [((2, 4, 16, 64, 64, 3, 0), 1)]                              # nine-tap, 16-pixel-wide tiles
+    + [((3, 5, 7, 36, 44, 3, t), 1) for t in (20, 21, 22)]        # generic split tiles
+    + [((3, 5, 7, 36, 44, 3, t), 0) for t in (1, 2, 3, 4, 5, 7, 8, 9, 10, 11)]
+    + [((2, 7, 32, 64, 64, 3, 0), 0)]                              # odd PH: no halo kernel takes it, the fp32 64x64 tile runs
+    + [((2, 8, 32, 32, 32, 3, 6), 0)]                              # fp32 LDS-halo kernel
+    + [((1, 1, 217, 512, 96, 1, 0), 0)]                            # a Linear layer's weight gradient: fp32 64x64 tile
+)
+
+
+@pytest.mark.parametrize("case,wants", _ABSMAX_READ, ids=["-".join(map(str, c)) for c, _ in _ABSMAX_READ])
+def test_wgrad_wants_absmax_is_what_the_launch_reads(case, wants, monkeypatch):
+    """qea_conv_wgrad_wants_absmax answers from the route qea_conv_wgrad takes.  Where it says 1 the launch really reads the two slots
+    (ops.conv_wgrad computing them itself is bit-equal to passing ops.absmax results; slots 2^20 too large change dw: the fp16 planes of
+    operands scaled 2^20 too small lose their low bits); where it says 0 the slots are never read (dw bit-equal with absurd slots) and
+    ops.conv_wgrad spends no absmax pass; under "f32" it spends none for any shape."""
+    import ctypes as C
+    from qea import _lib, ops
+    B, H, W, Cin, Cout, K, tile = case
+    pad = 1 if K == 3 else 0
+    g = torch.Generator().manual_seed(11 + tile)
+    x = torch.randn(B, H, W, Cin, generator=g).cuda()
+    dy = torch.randn(B, H, W, Cout, generator=g).cuda()
+    kw = dict(B=B, PH=H, PW=W, QH=H, QW=W, R=Cout, Cc=Cin, KH=K, KW=K, pad=(pad, pad), ldp=Cout, ldq=Cin, tile=tile)
+    passes = []
+    real_absmax = ops.absmax
+    monkeypatch.setattr(ops, "absmax", lambda *a: passes.append(1) or real_absmax(*a))
+
+    def run(**amax):
+        dw = torch.full((Cout, K, K, Cin), float("nan"), device="cuda")
+        ops.conv_wgrad(dy, x, dw, **kw, **amax)
+        return dw
+
+    prev = ops.set_mfma_mode("split_f16")
+    try:
+        d = _lib.WgradDesc(B=B, PH=H, PW=W, QH=H, QW=W, R=Cout, C=Cin, KH=K, KW=K, pad_h=pad, pad_w=pad, stride_h=1, stride_w=1,
+                           ldp=Cout, ldq=Cin, tile=tile)
+        assert _lib.lib().qea_conv_wgrad_wants_absmax(C.byref(d)) == wants
+        own = run()
+        assert len(passes) == 2 * wants
+        pm, qm = real_absmax(dy, Cout, B * H * W, Cout), real_absmax(x, Cin, B * H * W, Cin)
+        absurd = run(p_amax=pm * 2.0 ** 20, q_amax=qm * 2.0 ** 20)
+        if wants:
+            assert torch.equal(own, run(p_amax=pm, q_amax=qm))
+            assert not torch.equal(own, absurd)
+        else:
+            assert torch.equal(own, absurd)
+        del passes[:]
+        ops.set_mfma_mode("f32")
+        run()
+        assert not passes
+    finally:
+        ops.set_mfma_mode(prev)
+    assert torch.isfinite(own).all()
