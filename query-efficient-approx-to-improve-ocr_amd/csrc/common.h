@@ -89,6 +89,30 @@ void qea_set_error(const char* fmt, ...);
 
 static inline int qea_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel; a refused reservation fails every launch of that kernel.
+// `who` names the entry point in the error text.
+template <auto Kernel>
+int reserve_lds(const char* who, size_t bytes) {
+  static const hipError_t rc = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (rc != hipSuccess) {
+    qea_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, bytes, hipGetErrorString(rc));
+    return QEA_ERR_LAUNCH;
+  }
+  return QEA_OK;
+}
+
+// grid of a PERSISTENT launch that keeps `per_cu` workgroups on every CU: a multiple of 8, so that the items a workgroup walks
+// (blockIdx.x, + gridDim.x, ...) stay on its XCD's contiguous range of qea_xcd_swizzle
+static inline int qea_persistent_grid(int per_cu) {
+  static const int cus = [] {
+    int dev = 0, n = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n;
+  }();
+  return per_cu * (cus & ~7);
+}
+
 // Bijective XCD-aware remap of a 1-D block id: blocks that land on the same XCD
 // (bid % 8 equal under round-robin dispatch) get a contiguous chunk of tile ids, so
 // neighbouring tiles share that XCD's L2.  Speed only; any placement is correct.

@@ -437,23 +437,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_m16_wg
 template <int COUT, bool STATS, int IMW = 0, int PKW = 0, bool BST = false>
 int launch_halo_m16_(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = IMW ? (size_t)2 * (4 + 1) * (32 / IMW) * (IMW + 2) * 64 * 2 : (size_t)2 * (4 + 2) * 34 * 64 * 2;
-  auto kern = conv3x3_halo_m16_kernel<COUT, STATS, IMW, PKW, BST>;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_igemm(halo m16): cannot reserve %zu bytes of LDS: %s", (size_t)lds, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
+  constexpr auto kern = conv3x3_halo_m16_kernel<COUT, STATS, IMW, PKW, BST>;
+  const int rc = reserve_lds<kern>("qea_conv_igemm(halo m16)", lds);
+  if (rc != QEA_OK) return rc;
   const long long total = IMW ? (long long)qea_cdiv(a.B, (32 / IMW) * (4 / (IMW / 4))) * (a.N / COUT) : (long long)a.B * (a.H / 4) * (a.W / 32) * (a.N / COUT);
   if (total <= 0 || total > 0x7fffffffLL) {
     qea_set_error("qea_conv_igemm(halo m16): grid %lld out of range", total);
     return QEA_ERR_INVALID;
   }
-  static const int resident = [] {
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return halo_m16_wgs(COUT) * (cus & ~7);
-  }();
+  const int resident = qea_persistent_grid(halo_m16_wgs(COUT));
   const unsigned grid = (total > resident && COUT > 32) ? (unsigned)resident : (unsigned)total;   // (32-channel outputs: one item per workgroup, see above)
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a.x, (const _Float16*)a.wp, a.y, a.B, a.H, a.W, a.ldx, a.ldy, a.scale, a.bias, a.relu, a.stats,
                      a.Cin / 64, a.N, a.mask, a.ldmask, (int)total, a.xmax, a.yamax, a.pool_y, a.ldpool, a.pool_amax, a.bst_y, a.ldbst, a.bst64, a.bst_scale,

@@ -11,6 +11,7 @@
 //
 // Roofline: MFMA-bound (fp32 matrix peak 157.3 TFLOP/s); 2*M*N*K algorithmic flops/launch.
 #include "conv_args.h"
+#include <string>
 #include <type_traits>
 #include <stdlib.h>
 #include <string.h>
@@ -87,6 +88,126 @@ struct IgemmGather {
   }
 };
 
+template <int MI, int NJ>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[MI][NJ]) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// ---- The pieces the three generic split kernels (conv_igemm_bf3_kernel, _p3_kernel, _bf3w_kernel) are built from.  They share one
+// LDS image, one fragment read and one MFMA sequence, which is what makes their results bit-identical
+// (tests/test_conv_igemm_gpu.py::test_presplit_planes_bit_identical).  NPL = 3: three bf16 planes, six MFMAs per product;
+// NPL = 2: two fp16 planes of the scaled operand, three MFMAs.
+constexpr int ROWB = 16;                       // 16-bit elements per LDS row: 32 bytes, unpadded; the two 16-byte halves of rows
+                                               // 8..15 (mod 16) are swapped, which keeps ds_read_b128 conflict-free
+template <int NPL>
+using split_frag = typename std::conditional<NPL == 2, f16x8, bf16x8>::type;
+typedef __attribute__((address_space(3))) void qea_lds_void;
+typedef __attribute__((address_space(1))) const void qea_glob_void;
+
+// float4 number kc of row ro of a K stage: split and stored into the swizzled rows of its planes (`plane` elements apart)
+template <int NPL>
+__device__ __forceinline__ void split_store(__bf16* dst, int plane, int ro, int kc, const f32x4 v, float sx = 1.f) {
+  const int o = ro * ROWB + (((kc >> 1) ^ ((ro >> 3) & 1)) << 3) + (kc & 1) * 4;
+  if constexpr (NPL == 2) {
+    f16x4 h, l;
+    qea_split2_f16(v, sx, h, l);
+    *reinterpret_cast<f16x4*>(dst + o) = h;
+    *reinterpret_cast<f16x4*>(dst + plane + o) = l;
+  } else {
+    bf16x4 h, m, l;
+    qea_split3(v, h, m, l);
+    *reinterpret_cast<bf16x4*>(dst + o) = h;
+    *reinterpret_cast<bf16x4*>(dst + plane + o) = m;
+    *reinterpret_cast<bf16x4*>(dst + 2 * plane + o) = l;
+  }
+}
+
+// the wave's fragments of one stage; a_src / b_src point at the lane's row and (swapped) half of plane 0
+template <int NPL, int MI, int NJ>
+__device__ __forceinline__ void load_frags(split_frag<NPL> (&af)[MI][NPL], split_frag<NPL> (&bf)[NJ][NPL], const __bf16* a_src, const __bf16* b_src,
+                                           int a_plane, int b_plane) {
+#pragma unroll
+  for (int pl = 0; pl < NPL; ++pl) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i) af[i][pl] = *reinterpret_cast<const split_frag<NPL>*>(a_src + pl * a_plane + i * 32 * ROWB);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) bf[j][pl] = *reinterpret_cast<const split_frag<NPL>*>(b_src + pl * b_plane + j * 32 * ROWB);
+  }
+}
+
+// one split product into a 32x32 accumulator, smallest terms first (ll-class terms are dropped): lh, hl, mm, mh, hm, hh with three
+// planes, lh, hl, hh with two.  a[pl], b[pl] are the fragments of plane pl.
+template <int NPL, typename F>
+__device__ __forceinline__ f32x16 mfma_split(f32x16 acc, const F (&a)[NPL], const F (&b)[NPL]) {
+  if constexpr (NPL == 2) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], acc, 0, 0, 0);
+  } else {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// the product of every (i, j) accumulator of a wave with the fragments load_frags read
+template <int NPL, int MI, int NJ>
+__device__ __forceinline__ void mfma_split_tile(f32x16 (&acc)[MI][NJ], const split_frag<NPL> (&af)[MI][NPL], const split_frag<NPL> (&bf)[NJ][NPL]) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = mfma_split<NPL>(acc[i][j], af[i], bf[j]);
+}
+
+// Filter stage by LDS-DMA from pre-split planes [row][K/16][NPL][16]: every wave issues its share of the stage's NPL * BN / 32 pieces of
+// 1 KiB (global_load_lds_dwordx4: 32 rows x 32 bytes of ONE plane per wave-instruction); lane (row = l >> 1, half = l & 1) of piece j
+// fills LDS row rb * 32 + row, 16-byte half `half`; rows past N read the zero chunk kept behind the planes.
+template <int NPL, int BN, int NW>
+struct FilterDma {
+  static constexpr int NB = NPL * BN / 32;               // pieces per stage
+  static constexpr int IB = (NB + NW - 1) / NW;          // per wave
+  int b_off[IB];
+
+  __device__ __forceinline__ void init(const ConvArgs& p, int wave, int lane, int n0) {
+    const int l_row = lane >> 1, l_half = lane & 1;
+#pragma unroll
+    for (int i = 0; i < IB; ++i) {
+      const int j = wave + NW * i;
+      b_off[i] = -1;
+      if (j < NB) {
+        const int rb = j / NPL, plane = j - rb * NPL;
+        const int row = rb * 32 + l_row;
+        const int hsrc = l_half ^ ((row >> 3) & 1);
+        const int n = n0 + row;
+        if (n < p.N) b_off[i] = n * (p.K >> 4) * (NPL * 32) + plane * 32 + hsrc * 16;
+      }
+    }
+  }
+
+  __device__ __forceinline__ void issue(const ConvArgs& p, char* lds_b, int wave, int buf, int tap, int cs, int cslices) const {
+    const int dB = (tap * cslices + cs) * (NPL * 32);
+#pragma unroll
+    for (int i = 0; i < IB; ++i) {
+      const int j = wave + NW * i;
+      if (j < NB) {
+        const int rb = j / NPL, plane = j - rb * NPL;
+        const unsigned off = (b_off[i] >= 0) ? (unsigned)(b_off[i] + dB) : p.wp_zero;
+        char* dst = lds_b + ((buf * NPL + plane) * BN + rb * 32) * (ROWB * 2);
+        __builtin_amdgcn_global_load_lds((qea_glob_void*)(p.wp + off), (qea_lds_void*)dst, 16, 0, 0);
+      }
+    }
+  }
+};
+
 // Cin must be a multiple of 32 (checked by the entry point); the K-slice BK is 16 or 32
 
 template <int BM, int BN, int WGM, int WGN, int BK>
@@ -134,12 +255,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_kernel(const ConvAr
   };
 
   f32x16 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int fr = lane & 31;  // fragment row (A: m, B: n)
   const int fh = lane >> 5;  // K half inside a group of 8
@@ -212,8 +328,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) __attribute__((amdgpu_waves_per_eu(
 void conv_igemm_bf3_kernel(const ConvArgs p) {
   constexpr int BK = 16;
   constexpr int NT = WGM * WGN * 64;
-  constexpr int ROWB = 16;                     // bf16 elements per LDS row: 32 bytes, unpadded; the two 16-byte halves of rows
-                                               // 8..15 (mod 16) are swapped, which keeps ds_read_b128 conflict-free (see frag)
   constexpr int KCH = BK / 4;                  // float4 per row of a K-slice
   constexpr int RPP = NT / KCH;                // rows covered per pass of the workgroup's threads
   constexpr int TM = BM / WGM, TN = BN / WGN;  // wave tile
@@ -241,34 +355,13 @@ void conv_igemm_bf3_kernel(const ConvArgs p) {
     __bf16* a_dst = As + (size_t)buf * 3 * BM * ROWB;
     __bf16* b_dst = Bs + (size_t)buf * 3 * BN * ROWB;
 #pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-      bf16x4 h, m, l;
-      qea_split3(g.a_reg[i], h, m, l);
-      const int ro = lrow + RPP * i;
-      const int o = ro * ROWB + (((kc >> 1) ^ ((ro >> 3) & 1)) << 3) + (kc & 1) * 4;
-      *reinterpret_cast<bf16x4*>(a_dst + o) = h;
-      *reinterpret_cast<bf16x4*>(a_dst + BM * ROWB + o) = m;
-      *reinterpret_cast<bf16x4*>(a_dst + 2 * BM * ROWB + o) = l;
-    }
+    for (int i = 0; i < A_LD; ++i) split_store<3>(a_dst, BM * ROWB, lrow + RPP * i, kc, g.a_reg[i]);
 #pragma unroll
-    for (int j = 0; j < B_LD; ++j) {
-      bf16x4 h, m, l;
-      qea_split3(g.b_reg[j], h, m, l);
-      const int ro = lrow + RPP * j;
-      const int o = ro * ROWB + (((kc >> 1) ^ ((ro >> 3) & 1)) << 3) + (kc & 1) * 4;
-      *reinterpret_cast<bf16x4*>(b_dst + o) = h;
-      *reinterpret_cast<bf16x4*>(b_dst + BN * ROWB + o) = m;
-      *reinterpret_cast<bf16x4*>(b_dst + 2 * BN * ROWB + o) = l;
-    }
+    for (int j = 0; j < B_LD; ++j) split_store<3>(b_dst, BN * ROWB, lrow + RPP * j, kc, g.b_reg[j]);
   };
 
   f32x16 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int fr = lane & 31, fh = lane >> 5;
   gather(0);
@@ -281,26 +374,9 @@ void conv_igemm_bf3_kernel(const ConvArgs p) {
     const int hsw = (fh ^ ((fr >> 3) & 1)) * 8;   // wm*TM, wn*TN and i*32 are multiples of 16: the swap depends on fr only
     const __bf16* a_src = As + (size_t)cur * 3 * BM * ROWB + (wm * TM + fr) * ROWB + hsw;
     const __bf16* b_src = Bs + (size_t)cur * 3 * BN * ROWB + (wn * TN + fr) * ROWB + hsw;
-    bf16x8 af[3][MI], bf[3][NJ];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) af[pl][i] = *reinterpret_cast<const bf16x8*>(a_src + pl * BM * ROWB + i * 32 * ROWB);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bf[pl][j] = *reinterpret_cast<const bf16x8*>(b_src + pl * BN * ROWB + j * 32 * ROWB);
-    }
-    // smallest terms first (ll-class terms are dropped): lh, hl, mm, mh, hm, hh
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[0][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[2][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[1][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
-      }
+    bf16x8 af[MI][3], bf[NJ][3];
+    load_frags<3>(af, bf, a_src, b_src, BM * ROWB, BN * ROWB);
+    mfma_split_tile<3>(acc, af, bf);
     if (kt + 1 < KT) stage(cur ^ 1);
     __syncthreads();
   }
@@ -320,18 +396,14 @@ void conv_igemm_bf3_kernel(const ConvArgs p) {
 // The LDS image, the fragment reads and the MFMA sequence are those of conv_igemm_bf3_kernel, so the results are
 // bit-identical to it (tests/test_conv_igemm_gpu.py::test_presplit_planes_bit_identical).
 // ---------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void qea_lds_void;
-typedef __attribute__((address_space(1))) const void qea_glob_void;
-
 template <int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(WGM * WGN * 64) __attribute__((amdgpu_waves_per_eu(WGM * WGN == 8 ? 4 : 1)))
 void conv_igemm_p3_kernel(const ConvArgs p) {
   constexpr int NW = WGM * WGN;
-  constexpr int ROWB = 16;                     // bf16 per LDS row (32 bytes); halves of rows 8..15 (mod 16) swapped, as in bf3
   constexpr int TM = BM / WGM, TN = BN / WGN;
   constexpr int MI = TM / 32, NJ = TN / 32;
-  constexpr int NA = 3 * BM / 32, NB = 3 * BN / 32;            // 1 KiB DMA pieces per stage (A, B)
-  constexpr int IA = (NA + NW - 1) / NW, IB = (NB + NW - 1) / NW;   // per wave
+  constexpr int NA = 3 * BM / 32;                              // 1 KiB DMA pieces per stage (A)
+  constexpr int IA = (NA + NW - 1) / NW;                       // per wave
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __bf16* As = reinterpret_cast<__bf16*>(smem);  // [2][3][BM][ROWB]
@@ -352,7 +424,7 @@ void conv_igemm_p3_kernel(const ConvArgs p) {
   const int l_row = lane >> 1, l_half = lane & 1;
   int a_off[IA];
   unsigned a_mask[IA];
-  int b_off[IB];
+  FilterDma<3, BN, NW> fb;
   {
     const int ohw = p.OH * p.OW;
 #pragma unroll
@@ -380,18 +452,7 @@ void conv_igemm_p3_kernel(const ConvArgs p) {
         }
       }
     }
-#pragma unroll
-    for (int i = 0; i < IB; ++i) {
-      const int j = wave + NW * i;
-      b_off[i] = -1;
-      if (j < NB) {
-        const int rb = j / 3, plane = j - rb * 3;
-        const int row = rb * 32 + l_row;
-        const int hsrc = l_half ^ ((row >> 3) & 1);
-        const int n = n0 + row;
-        if (n < p.N) b_off[i] = n * (p.K >> 4) * 96 + plane * 32 + hsrc * 16;
-      }
-    }
+    fb.init(p, wave, lane, n0);
   }
   char* const lds_a = reinterpret_cast<char*>(As);
   char* const lds_b = reinterpret_cast<char*>(Bs);
@@ -401,7 +462,6 @@ void conv_igemm_p3_kernel(const ConvArgs p) {
     const int kh = tap / p.KW;
     const int kw = tap - kh * p.KW;
     const int dA = ((kh * p.W + kw) * cslices + cs) * 96;
-    const int dB = (tap * cslices + cs) * 96;
 #pragma unroll
     for (int i = 0; i < IA; ++i) {
       const int j = wave + NW * i;
@@ -412,25 +472,11 @@ void conv_igemm_p3_kernel(const ConvArgs p) {
         __builtin_amdgcn_global_load_lds((qea_glob_void*)(p.xp + off), (qea_lds_void*)dst, 16, 0, 0);
       }
     }
-#pragma unroll
-    for (int i = 0; i < IB; ++i) {
-      const int j = wave + NW * i;
-      if (j < NB) {
-        const int rb = j / 3, plane = j - rb * 3;
-        const unsigned off = (b_off[i] >= 0) ? (unsigned)(b_off[i] + dB) : p.wp_zero;
-        char* dst = lds_b + ((buf * 3 + plane) * BN + rb * 32) * (ROWB * 2);
-        __builtin_amdgcn_global_load_lds((qea_glob_void*)(p.wp + off), (qea_lds_void*)dst, 16, 0, 0);
-      }
-    }
+    fb.issue(p, lds_b, wave, buf, tap, cs, cslices);
   };
 
   f32x16 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int fr = lane & 31, fh = lane >> 5;
   const int hsw = (fh ^ ((fr >> 3) & 1)) * 8;
@@ -441,26 +487,9 @@ void conv_igemm_p3_kernel(const ConvArgs p) {
     if (kt + 1 < KT) dma(kt + 1, cur ^ 1);      // lands under the MFMAs below; __syncthreads() waits for it (vmcnt)
     const __bf16* a_src = As + (size_t)cur * 3 * BM * ROWB + (wm * TM + fr) * ROWB + hsw;
     const __bf16* b_src = Bs + (size_t)cur * 3 * BN * ROWB + (wn * TN + fr) * ROWB + hsw;
-    bf16x8 af[3][MI], bf[3][NJ];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) af[pl][i] = *reinterpret_cast<const bf16x8*>(a_src + pl * BM * ROWB + i * 32 * ROWB);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bf[pl][j] = *reinterpret_cast<const bf16x8*>(b_src + pl * BN * ROWB + j * 32 * ROWB);
-    }
-    // smallest terms first (ll-class terms are dropped): lh, hl, mm, mh, hm, hh — the order of conv_igemm_bf3_kernel
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[0][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[2][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[1][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
-      }
+    bf16x8 af[MI][3], bf[NJ][3];
+    load_frags<3>(af, bf, a_src, b_src, BM * ROWB, BN * ROWB);
+    mfma_split_tile<3>(acc, af, bf);
     // hipcc otherwise hoists the barrier (and the vmcnt(0) in front of it) above the register-only MFMAs, which exposes
     // the whole DMA latency of the next stage instead of hiding it under this stage's matrix work
     __builtin_amdgcn_sched_barrier(0);
@@ -546,18 +575,14 @@ template <int BM, int BN, int WGM, int WGN, bool STATS, int NPL = 3>
 __global__ __launch_bounds__(WGM * WGN * 64) __attribute__((amdgpu_waves_per_eu(WGM * WGN == 8 ? 4 : 1)))
 void conv_igemm_bf3w_kernel(const ConvArgs p) {
   constexpr bool F16 = NPL == 2;
-  typedef typename std::conditional<F16, f16x8, bf16x8>::type frag_t;
   constexpr int BK = 16;
   constexpr int NW = WGM * WGN;
   constexpr int NT = NW * 64;
-  constexpr int ROWB = 16;
   constexpr int KCH = BK / 4;
   constexpr int RPP = NT / KCH;
   constexpr int TM = BM / WGM, TN = BN / WGN;
   constexpr int MI = TM / 32, NJ = TN / 32;
   constexpr int A_LD = BM / RPP;
-  constexpr int NB = NPL * BN / 32;
-  constexpr int IB = (NB + NW - 1) / NW;
   static_assert(BM % RPP == 0, "tile rows must be a multiple of the rows staged per pass");
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -583,6 +608,10 @@ void conv_igemm_bf3w_kernel(const ConvArgs p) {
   g.init(p, tid, m0, n0);
   const int lrow = g.lrow, kc = g.kc;
   const int KT = ntaps * cslices;
+  // FilterDma's code, spelled in place: through the struct the compiler allocates two SGPRs fewer for the three-plane 256x64
+  // instances (tile 23), and this kernel's generated code is kept as it was measured
+  constexpr int NB = NPL * BN / 32;
+  constexpr int IB = (NB + NW - 1) / NW;
   const int l_row = lane >> 1, l_half = lane & 1;
   int b_off[IB];
 #pragma unroll
@@ -616,31 +645,11 @@ void conv_igemm_bf3w_kernel(const ConvArgs p) {
   auto stage_a = [&](int buf) {
     __bf16* a_dst = As + (size_t)buf * NPL * BM * ROWB;
 #pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-      const int ro = lrow + RPP * i;
-      const int o = ro * ROWB + (((kc >> 1) ^ ((ro >> 3) & 1)) << 3) + (kc & 1) * 4;
-      if constexpr (F16) {
-        f16x4 h, l;
-        qea_split2_f16(g.a_reg[i], sx, h, l);
-        *reinterpret_cast<f16x4*>(a_dst + o) = h;
-        *reinterpret_cast<f16x4*>(a_dst + BM * ROWB + o) = l;
-      } else {
-        bf16x4 h, m, l;
-        qea_split3(g.a_reg[i], h, m, l);
-        *reinterpret_cast<bf16x4*>(a_dst + o) = h;
-        *reinterpret_cast<bf16x4*>(a_dst + BM * ROWB + o) = m;
-        *reinterpret_cast<bf16x4*>(a_dst + 2 * BM * ROWB + o) = l;
-      }
-    }
+    for (int i = 0; i < A_LD; ++i) split_store<NPL>(a_dst, BM * ROWB, lrow + RPP * i, kc, g.a_reg[i], sx);
   };
 
   f32x16 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int fr = lane & 31, fh = lane >> 5;
   const int hsw = (fh ^ ((fr >> 3) & 1)) * 8;
@@ -656,31 +665,9 @@ void conv_igemm_bf3w_kernel(const ConvArgs p) {
     }
     const __bf16* a_src = As + (size_t)cur * NPL * BM * ROWB + (wm * TM + fr) * ROWB + hsw;
     const __bf16* b_src = Bs + (size_t)cur * NPL * BN * ROWB + (wn * TN + fr) * ROWB + hsw;
-    frag_t af[NPL][MI], bf[NPL][NJ];
-#pragma unroll
-    for (int pl = 0; pl < NPL; ++pl) {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) af[pl][i] = *reinterpret_cast<const frag_t*>(a_src + pl * BM * ROWB + i * 32 * ROWB);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bf[pl][j] = *reinterpret_cast<const frag_t*>(b_src + pl * BN * ROWB + j * 32 * ROWB);
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        if constexpr (F16) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
-        } else {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[2][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
-        }
-      }
+    split_frag<NPL> af[MI][NPL], bf[NJ][NPL];
+    load_frags<NPL>(af, bf, a_src, b_src, BM * ROWB, BN * ROWB);
+    mfma_split_tile<NPL>(acc, af, bf);
     if (kt + 1 < KT) stage_a(cur ^ 1);
     __syncthreads();
   }
@@ -695,95 +682,51 @@ void conv_igemm_bf3w_kernel(const ConvArgs p) {
   conv_epilogue<MI, NJ, TM, TN, STATS>(p, acc, m0, n0, wm, wn, fr, fh, tile_m * WGM + wm);
 }
 
-template <int BM, int BN, int WGM, int WGN, bool STATS, int NPL = 3>
-int launch_bf3w_(const ConvArgs& a, hipStream_t s) {
+// The one launch of a generic tile: the grid of BM x BN tiles, the kernel's dynamic LDS reserved once, the grid range checked
+template <auto Kernel>
+int launch_tiled(const ConvArgs& a, size_t lds, int BM, int BN, int threads, hipStream_t s) {
   ConvArgs p = a;
   p.m_tiles = qea_cdiv(p.M, BM);
   p.n_tiles = qea_cdiv(p.N, BN);
-  const size_t lds = (size_t)2 * NPL * (BM + BN) * 16 * 2;
-  auto kern = conv_igemm_bf3w_kernel<BM, BN, WGM, WGN, STATS, NPL>;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_igemm: cannot reserve %zu bytes of LDS for the %dx%d tile: %s", lds, BM, BN, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
+  static const std::string who = "qea_conv_igemm(" + std::to_string(BM) + "x" + std::to_string(BN) + " tile)";   // a kernel has one tile size
+  const int rc = reserve_lds<Kernel>(who.c_str(), lds);
+  if (rc != QEA_OK) return rc;
   const long long grid = (long long)p.m_tiles * p.n_tiles;
   if (grid <= 0 || grid > 0x7fffffffLL) {
     qea_set_error("qea_conv_igemm: grid %lld out of range", grid);
     return QEA_ERR_INVALID;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WGM * WGN * 64), lds, s, p);
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)grid), dim3(threads), lds, s, p);
   return QEA_OK;
 }
 
+constexpr size_t split_lds(int npl, int bm, int bn) { return (size_t)2 * npl * (bm + bn) * ROWB * 2; }
+
+// the three operand forms of a split tile: hybrid (filter planes by DMA; two-way fp16 split when the input's abs-max came with them,
+// ABI v6), all-DMA, split on the fly
 template <int BM, int BN, int WGM, int WGN>
 int launch_bf3w(const ConvArgs& a, hipStream_t s) {
-  if (a.xmax)                                              // two-way fp16 split: fp16 filter planes + the input's abs-max (ABI v6)
-    return a.stats ? launch_bf3w_<BM, BN, WGM, WGN, true, 2>(a, s) : launch_bf3w_<BM, BN, WGM, WGN, false, 2>(a, s);
-  return a.stats ? launch_bf3w_<BM, BN, WGM, WGN, true>(a, s) : launch_bf3w_<BM, BN, WGM, WGN, false>(a, s);
+  constexpr int T = WGM * WGN * 64;
+  if (a.xmax)
+    return a.stats ? launch_tiled<conv_igemm_bf3w_kernel<BM, BN, WGM, WGN, true, 2>>(a, split_lds(2, BM, BN), BM, BN, T, s)
+                   : launch_tiled<conv_igemm_bf3w_kernel<BM, BN, WGM, WGN, false, 2>>(a, split_lds(2, BM, BN), BM, BN, T, s);
+  return a.stats ? launch_tiled<conv_igemm_bf3w_kernel<BM, BN, WGM, WGN, true>>(a, split_lds(3, BM, BN), BM, BN, T, s)
+                 : launch_tiled<conv_igemm_bf3w_kernel<BM, BN, WGM, WGN, false>>(a, split_lds(3, BM, BN), BM, BN, T, s);
 }
 
 template <int BM, int BN, int WGM, int WGN>
 int launch_p3(const ConvArgs& a, hipStream_t s) {
-  ConvArgs p = a;
-  p.m_tiles = qea_cdiv(p.M, BM);
-  p.n_tiles = qea_cdiv(p.N, BN);
-  const size_t lds = (size_t)2 * 3 * (BM + BN) * 16 * 2;
-  auto kern = conv_igemm_p3_kernel<BM, BN, WGM, WGN>;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_igemm: cannot reserve %zu bytes of LDS for the %dx%d tile: %s", lds, BM, BN, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
-  const long long grid = (long long)p.m_tiles * p.n_tiles;
-  if (grid <= 0 || grid > 0x7fffffffLL) {
-    qea_set_error("qea_conv_igemm: grid %lld out of range", grid);
-    return QEA_ERR_INVALID;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WGM * WGN * 64), lds, s, p);
-  return QEA_OK;
+  return launch_tiled<conv_igemm_p3_kernel<BM, BN, WGM, WGN>>(a, split_lds(3, BM, BN), BM, BN, WGM * WGN * 64, s);
 }
 
 template <int BM, int BN, int WGM, int WGN>
 int launch_bf3(const ConvArgs& a, hipStream_t s) {
-  ConvArgs p = a;
-  p.m_tiles = qea_cdiv(p.M, BM);
-  p.n_tiles = qea_cdiv(p.N, BN);
-  const size_t lds = (size_t)2 * 3 * (BM + BN) * 16 * 2;
-  auto kern = conv_igemm_bf3_kernel<BM, BN, WGM, WGN>;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_igemm: cannot reserve %zu bytes of LDS for the %dx%d split-bf16 tile: %s", lds, BM, BN, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
-  const long long grid = (long long)p.m_tiles * p.n_tiles;
-  if (grid <= 0 || grid > 0x7fffffffLL) {
-    qea_set_error("qea_conv_igemm: grid %lld out of range", grid);
-    return QEA_ERR_INVALID;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WGM * WGN * 64), lds, s, p);
-  return QEA_OK;
+  return launch_tiled<conv_igemm_bf3_kernel<BM, BN, WGM, WGN>>(a, split_lds(3, BM, BN), BM, BN, WGM * WGN * 64, s);
 }
 
 template <int BM, int BN, int WGM, int WGN, int BK>
-int launch(const ConvArgs& a, hipStream_t s) {
-  ConvArgs p = a;
-  p.m_tiles = qea_cdiv(p.M, BM);
-  p.n_tiles = qea_cdiv(p.N, BN);
-  const size_t lds = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float);
-  auto kern = conv_igemm_kernel<BM, BN, WGM, WGN, BK>;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_igemm: cannot reserve %zu bytes of LDS for the %dx%d tile: %s", lds, BM, BN, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
-  const long long grid = (long long)p.m_tiles * p.n_tiles;
-  if (grid <= 0 || grid > 0x7fffffffLL) {
-    qea_set_error("qea_conv_igemm: grid %lld out of range", grid);
-    return QEA_ERR_INVALID;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WGM * WGN * 64), lds, s, p);
-  return QEA_OK;
+int launch_f32(const ConvArgs& a, hipStream_t s) {
+  return launch_tiled<conv_igemm_kernel<BM, BN, WGM, WGN, BK>>(a, (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float), BM, BN, WGM * WGN * 64, s);
 }
 
 
@@ -938,12 +881,9 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const float* __restri
 template <int CIN, int COUT, int TH, bool STATS>
 int launch_halo_(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = (size_t)(TH + 2) * 34 * (CIN + 4) * sizeof(float);
-  auto kern = conv3x3_halo_kernel<CIN, COUT, TH, STATS>;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_igemm(halo): cannot reserve %zu bytes of LDS: %s", (size_t)lds, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
+  constexpr auto kern = conv3x3_halo_kernel<CIN, COUT, TH, STATS>;
+  const int rc = reserve_lds<kern>("qea_conv_igemm(halo)", lds);
+  if (rc != QEA_OK) return rc;
   const long long grid = (long long)a.B * (a.H / TH) * (a.W / 32);
   if (grid <= 0 || grid > 0x7fffffffLL) {
     qea_set_error("qea_conv_igemm(halo): grid %lld out of range", grid);
@@ -1190,31 +1130,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_bf3_wg
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
           const int f = st * MI + i;
-          const frag_t* a = ar[f & 1];
           const bool more = f + 1 < STEPS * MI;
           if (more) read_a((f + 1) / MI, (f + 1) % MI, ar[(f + 1) & 1]);
-          if constexpr (F16) {
-            // smallest terms first (ll is dropped): lh, hl, hh
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], bq[cb][0], acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], bq[cb][1], acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], bq[cb][0], acc[i], 0, 0, 0);
-            if (more) {
-              __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // the two LDS reads of row f + 1 ...
-              __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);   // ... ahead of the three MFMAs of row f
-            }
-          }
-          else {
-            // smallest terms first (ll-class terms are dropped): lh, hl, mm, mh, hm, hh
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], bq[cb][0], acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[cb][2], acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], bq[cb][1], acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], bq[cb][0], acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[cb][1], acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[cb][0], acc[i], 0, 0, 0);
-            if (more) {
-              __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);   // the three LDS reads of row f + 1 ...
-              __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);   // ... ahead of the six MFMAs of row f
-            }
+          acc[i] = mfma_split<NPL>(acc[i], ar[f & 1], bq[cb]);
+          if (more) {
+            __builtin_amdgcn_sched_group_barrier(0x100, NPL, 0);                // the NPL LDS reads of row f + 1 ...
+            __builtin_amdgcn_sched_group_barrier(0x008, NPL == 2 ? 3 : 6, 0);   // ... ahead of the three / six MFMAs of row f
           }
         }
       }
@@ -1509,12 +1430,9 @@ __global__ void pack_frag_planes_f16_m16_kernel(const float* __restrict__ w, _Fl
 template <int CIN, int COUT, int TH, bool STATS, int IMW = 0, int NPL = 3, int PKW = 0, bool BST = false>
 int launch_halo_bf3_(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = IMW ? (size_t)NPL * (TH + 1) * (32 / IMW) * (IMW + 2) * CIN * 2 : (size_t)NPL * (TH + 2) * 34 * CIN * 2;
-  auto kern = conv3x3_halo_bf3_kernel<CIN, COUT, TH, STATS, IMW, NPL, PKW, BST>;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_igemm(halo bf3): cannot reserve %zu bytes of LDS: %s", (size_t)lds, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
+  constexpr auto kern = conv3x3_halo_bf3_kernel<CIN, COUT, TH, STATS, IMW, NPL, PKW, BST>;
+  const int rc = reserve_lds<kern>("qea_conv_igemm(halo bf3)", lds);
+  if (rc != QEA_OK) return rc;
   const long long total = IMW ? (long long)qea_cdiv(a.B, (32 / IMW) * (TH / (IMW / 4))) * (a.N / COUT)
                               : (long long)a.B * (a.H / TH) * (a.W / 32) * (a.N / COUT);
   if (total <= 0 || total > 0x7fffffffLL) {
@@ -1522,12 +1440,7 @@ int launch_halo_bf3_(const ConvArgs& a, hipStream_t s) {
     return QEA_ERR_INVALID;
   }
   // persistent: two workgroups per CU (the LDS bound) once there are more items than that
-  static const int resident = [] {
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return halo_bf3_wgs(CIN, COUT, NPL, BST) * (cus & ~7);
-  }();
+  const int resident = qea_persistent_grid(halo_bf3_wgs(CIN, COUT, NPL, BST));
   // (32-channel outputs keep one item per workgroup: two persistent workgroups of a CU fall into lockstep there — both staging,
   // then both in their MFMA phase — and lose the overlap that staggered dispatch gives: 150-159 vs 159-166 TFLOP/s measured)
   // (re-measured with the fp16 split and three workgroups per CU: persistent 0.779 / 1.431 ms against 0.750 / 1.331 one item each)
@@ -1538,20 +1451,16 @@ int launch_halo_bf3_(const ConvArgs& a, hipStream_t s) {
   return QEA_OK;
 }
 
-// the instances with the fused max-pool (fp16 form, no statistics): the layers that are followed by a pool — CRNN conv2 (2x2) and conv4
-// (2x1), the second conv of the UNet encoder levels in the inference pass (BatchNorm + ReLU in the epilogue)
-template <int CIN, int COUT, int TH, int IMW = 0>
-int launch_halo_bf3_pool(const ConvArgs& a, hipStream_t s) {
-  if (a.pool_kw == 1) return launch_halo_bf3_<CIN, COUT, TH, false, IMW, 2, 1>(a, s);
-  return launch_halo_bf3_<CIN, COUT, TH, false, IMW, 2, 2>(a, s);
-}
-
+// every variant of one (chunk, output group, tile height, image width).  The two-way fp16 split runs here with 32 input channels
+// only: with 64-channel chunks it is the 16x16x32 kernel of conv_halo16.hip (route(): SPLIT_HALO_M16)
 template <int CIN, int COUT, int TH, int IMW = 0>
 int launch_halo_bf3(const ConvArgs& a, hipStream_t s) {
-  if (a.xmax && a.bst_y)                                   // ... with the BatchNorm-backward sums of the tensor it writes (fp16 form only)
-    return launch_halo_bf3_<CIN, COUT, TH, false, IMW, 2, 0, true>(a, s);
-  if (a.xmax)                                              // two-way fp16 split: the caller gave the input's abs-max and fp16 filter planes
-    return a.stats ? launch_halo_bf3_<CIN, COUT, TH, true, IMW, 2>(a, s) : launch_halo_bf3_<CIN, COUT, TH, false, IMW, 2>(a, s);
+  if constexpr (CIN == 32) {
+    if (a.xmax && a.bst_y)                                 // ... with the BatchNorm-backward sums of the tensor it writes (fp16 form only)
+      return launch_halo_bf3_<CIN, COUT, TH, false, IMW, 2, 0, true>(a, s);
+    if (a.xmax)                                            // two-way fp16 split: the caller gave the input's abs-max and fp16 filter planes
+      return a.stats ? launch_halo_bf3_<CIN, COUT, TH, true, IMW, 2>(a, s) : launch_halo_bf3_<CIN, COUT, TH, false, IMW, 2>(a, s);
+  }
   return a.stats ? launch_halo_bf3_<CIN, COUT, TH, true, IMW>(a, s) : launch_halo_bf3_<CIN, COUT, TH, false, IMW>(a, s);
 }
 
@@ -1598,17 +1507,11 @@ bool halo_bf3_pool_shape(const qea_conv_desc* d, int kw) {
   return d->N % 128 == 0;                                // <64,128,4>: both windows
 }
 
+// the 32x32x16 form (route(): SPLIT_HALO)
 int launch_halo_bf3_any(const qea_conv_desc* d, const ConvArgs& a, hipStream_t s) {
   const int sm = halo_bf3_small(d);
-  if (a.xmax && d->Cin % 64 == 0) {                        // two-way fp16 split, 64-channel chunks: the 16x16x32 kernel (round 4)
-    return qea_conv::launch_halo_m16_any(d->N == 32 ? 32 : (d->N == 64 ? 64 : 128), sm, a, s);   // (conv_halo16.hip)
-  }
-  if (a.pool_y) {
-    if (sm == 16) return launch_halo_bf3_<64, 128, 4, false, 16, 2, 2>(a, s);
-    if (d->Cin == 32) return launch_halo_bf3_<32, 32, 8, false, 0, 2, 2>(a, s);
-    if (d->N == 64) return launch_halo_bf3_<64, 64, 4, false, 0, 2, 2>(a, s);
-    return launch_halo_bf3_pool<64, 128, 4>(a, s);
-  }
+  // the fused max-pool (fp16 form, no statistics) needs x_absmax, which leaves this kernel the 32-channel inputs: 32 -> 32, 2 x 2 window
+  if (a.pool_y) return launch_halo_bf3_<32, 32, 8, false, 0, 2, 2>(a, s);
   if (sm == 16) return launch_halo_bf3<64, 128, 4, 16>(a, s);
   if (sm == 8) return launch_halo_bf3<64, 128, 4, 8>(a, s);
   if (d->Cin == 32) {
@@ -1631,10 +1534,6 @@ int launch_halo_any(const qea_conv_desc* d, const ConvArgs& a, hipStream_t s) {
   return launch_halo<64, 64, 4>(a, s);
 }
 
-// The split-bf16 LDS-halo kernel beats the generic split tiles on EVERY shape it takes (tools/bench_conv.py, B = 512:
-// 32->32 168 vs 95 fp32-halo; 128->64 211 vs 140; 128->128 208 vs 186; 256->256 226 vs 215; 512->512 238 vs 226 TFLOP/s).
-bool halo_bf3_wins(const qea_conv_desc* d) { return halo_bf3_eligible(d); }
-
 // tile 26 (gemm1x1.hip): 1x1 stride-1 GEMMs on the 128-row LDS tile, two-way fp16 split only (needs x_absmax + the planes of
 // qea_pack_frag_planes_f16_1x1): K a multiple of 64, N a multiple of 128, bias / ReLU epilogue, NHWC / TBC / transposed-conv store
 bool gemm1x1_eligible(const qea_conv_desc* d) {
@@ -1644,89 +1543,220 @@ bool gemm1x1_eligible(const qea_conv_desc* d) {
          (d->out_mode != QEA_OUT_CONVT || (long long)d->B * d->H * d->W * 4 < 0x7fffffffLL);   // (output pixel rows are kept as int32)
 }
 
-// Tile choice for tile == 0 (measured on MI355X with tools/bench_conv.py)
-int pick_tile(const qea_conv_desc* d, const ConvArgs& a) {
-  int tile = 0;
+// THE list of generic (implicit-GEMM) tiles: what an id means, how each operand form of it is launched and how many rows of
+// statistics partials it writes are all read from this table, so a tile is added, dropped or re-shaped in one row.
+struct GenericTile {
+  typedef int (*Launch)(const ConvArgs&, hipStream_t);
+  int id, BM, BN, WGM, WGN, BK;
+  Launch fly, hybrid, dma;   // operands split on the fly (the only form of an fp32 tile) / filter planes by DMA / both by DMA
+  bool stats;                // the hybrid form is offered with the fused-statistics epilogue: one row of partials per (M-tile, wave row)
+};
+
+template <int ID, int BM, int BN, int WGM, int WGN, int BK>
+constexpr GenericTile f32_tile() { return {ID, BM, BN, WGM, WGN, BK, launch_f32<BM, BN, WGM, WGN, BK>, nullptr, nullptr, false}; }
+
+template <int ID, int BM, int BN, int WGM, int WGN, bool STATS = true>
+constexpr GenericTile split_tile() {
+  return {ID, BM, BN, WGM, WGN, 16, launch_bf3<BM, BN, WGM, WGN>, launch_bf3w<BM, BN, WGM, WGN>, launch_p3<BM, BN, WGM, WGN>, STATS};
+}
+
+constexpr int FIRST_SPLIT_TILE = 20;   // ids from here on run on the split MFMA forms and may take pre-split operands
+
+const GenericTile TILES[] = {
+    f32_tile<1, 128, 128, 2, 2, 32>(),
+    f32_tile<2, 256, 64, 4, 1, 32>(),
+    f32_tile<3, 256, 32, 4, 1, 32>(),
+    f32_tile<5, 128, 128, 2, 2, 16>(),
+    f32_tile<6, 128, 64, 2, 2, 32>(),    // small grids: twice the workgroups of tile 1
+    f32_tile<7, 256, 128, 4, 2, 16>(),   // 8 waves
+    f32_tile<8, 128, 256, 2, 4, 16>(),   // 8 waves
+    f32_tile<9, 256, 64, 4, 1, 16>(),    // tile 2 with half the LDS (3 workgroups per CU)
+    split_tile<20, 128, 128, 2, 2, false>(),   // (never offered with statistics)
+    split_tile<21, 256, 128, 4, 2>(),
+    split_tile<22, 128, 256, 2, 4>(),
+    split_tile<23, 256, 64, 4, 1>(),
+    split_tile<25, 128, 128, 4, 2>(),    // 8 waves on a 128x128 tile: small grids
+};
+
+const GenericTile* find_tile(int id) {
+  for (const GenericTile& t : TILES)
+    if (t.id == id) return &t;
+  return nullptr;
+}
+
+// Tile choice for tile == 0 (measured on MI355X with tools/bench_conv.py); tile == -1: the choice without tiles 24 / 26
+int pick_tile(const qea_conv_desc* d, int M, int K) {
   // measured on MI355X (tools/bench_conv.py): the 16-deep K-slice (half the LDS, 4 workgroups per CU) wins
   // only when the grid is large enough to keep all of them busy
-  const long long tiles128 = (long long)qea_cdiv(a.M, 128) * qea_cdiv(d->N, 128);
-  const long long tiles7 = (long long)qea_cdiv(a.M, 256) * qea_cdiv(d->N, 128);   // 256x128, 8 waves
-  const long long tiles8 = (long long)qea_cdiv(a.M, 128) * qea_cdiv(d->N, 256);   // 128x256, 8 waves
+  const long long tiles128 = (long long)qea_cdiv(M, 128) * qea_cdiv(d->N, 128);
   // 8-wave workgroups (twice the tile, 16-deep K-slice, 4 waves per SIMD) reach 124-135 TFLOP/s once the grid
   // holds at least two of them per CU; below that the 4-wave tiles win (tools/bench_conv.py on MI355X)
+  const long long tiles256x128 = (long long)qea_cdiv(M, 256) * qea_cdiv(d->N, 128);   // tiles 7 and 21
+  const long long tiles128x256 = (long long)qea_cdiv(M, 128) * qea_cdiv(d->N, 256);   // tiles 8 and 22
   // split-bf16 tiles (20-23) for every layer of 64+ output channels unless QEA_MFMA=f32 asks for the native fp32 MFMA:
   // 160-186 TFLOP/s against 110-134, and closer to the fp64 result than the fp32 instruction (fewer accumulator roundings)
-  const long long tiles21 = (long long)qea_cdiv(a.M, 256) * qea_cdiv(d->N, 128);
-  const long long tiles22 = (long long)qea_cdiv(a.M, 128) * qea_cdiv(d->N, 256);
   // (short-K launches — the transposed convs — are bound by their output traffic, and N < 128 wastes the tile)
-  const bool bf3 = qea_split_bf16_enabled() && d->N >= 128 && a.K >= 256;
+  const bool split = qea_split_bf16_enabled();
+  const bool bf3 = split && d->N >= 128 && K >= 256;
+  if (split && d->tile != -1 && gemm1x1_eligible(d)) return 26;     // 1x1 / transposed-conv GEMMs: 128-row LDS tile (fp16 split)
+  // The split-bf16 LDS-halo kernel beats the generic split tiles on EVERY shape it takes (tools/bench_conv.py, B = 512:
+  // 32->32 168 vs 95 fp32-halo; 128->64 211 vs 140; 128->128 208 vs 186; 256->256 226 vs 215; 512->512 238 vs 226 TFLOP/s).
+  if (split && d->tile != -1 && halo_bf3_eligible(d)) return 24;
   // 33..64 output channels: the split-bf16 256x64 tile beats both the fp32 256x64 tile (132 vs 107 TFLOP/s at Cin = 128) and
   // the fp32 LDS-halo kernel at Cin = 64 (120 vs 111); the halo kernel keeps Cin = 32 (K = 288: 102 vs 91)
-  if (qea_split_bf16_enabled() && d->tile != -1 && gemm1x1_eligible(d)) tile = 26;     // 1x1 / transposed-conv GEMMs: 128-row LDS tile (fp16 split)
-  else if (qea_split_bf16_enabled() && d->tile != -1 && halo_bf3_wins(d)) tile = 24;   // narrow layers: split-bf16 LDS-halo kernel (168-208 vs 95-120 TFLOP/s)
-  else if (qea_split_bf16_enabled() && d->N > 32 && d->N <= 64 && a.K >= 256 && d->Cin >= 64) tile = 23;
-  else if (halo_eligible(d)) tile = 4;
+  if (split && d->N > 32 && d->N <= 64 && K >= 256 && d->Cin >= 64) return 23;
+  if (halo_eligible(d)) return 4;
   // transposed convolutions (forward scatter / stride-2 input gradient) with K <= 256: traffic-bound launches of 4-16 K
   // stages; the 8-wave 128x128 split tile has the shortest prologue per output byte (tools/bench_convt.py at B = 2048:
   // 64->32 fwd 970 -> 821 us, dgrad 708 -> 573; 128->64 604 -> 470 / 320 -> 266; 256->128 343 -> 315 / 224 -> 216)
-  else if (qea_split_bf16_enabled() && (d->out_mode == QEA_OUT_CONVT || (d->stride_h == 2 && d->stride_w == 2)) && d->N >= 64 && a.K >= 64 &&
-           a.K <= 256 && d->Cin % 16 == 0)
-    tile = 25;
-  else if (d->N <= 32) tile = 3;
-  else if (d->N <= 64) tile = 9;  // 16-deep slice: 51 KB of LDS, three workgroups per CU (107 vs 80 TFLOP/s at 32-deep; the split-bf16 256x64 tile is slower here)
-  else if (bf3 && d->N % 256 == 0 && tiles22 >= 512) tile = 22;
-  else if (bf3 && tiles21 >= 512) tile = 21;
-  else if (bf3) tile = 25;  // small grids: 8 waves on a 128x128 tile (146-166 vs 110-150 TFLOP/s for the 4-wave tile 20)
-  else if (d->N % 256 == 0 && tiles8 >= 1024) tile = 8;
-  else if (tiles7 >= 512) tile = 7;
-  else if (tiles128 >= 2048) tile = 5;
-  else if (tiles128 < 192) tile = 6;
-  else tile = 1;
-  return tile;
+  if (split && (d->out_mode == QEA_OUT_CONVT || (d->stride_h == 2 && d->stride_w == 2)) && d->N >= 64 && K >= 64 && K <= 256 && d->Cin % 16 == 0)
+    return 25;
+  if (d->N <= 32) return 3;
+  if (d->N <= 64) return 9;  // 16-deep slice: 51 KB of LDS, three workgroups per CU (107 vs 80 TFLOP/s at 32-deep; the split-bf16 256x64 tile is slower here)
+  if (bf3 && d->N % 256 == 0 && tiles128x256 >= 512) return 22;
+  if (bf3 && tiles256x128 >= 512) return 21;
+  if (bf3) return 25;  // small grids: 8 waves on a 128x128 tile (146-166 vs 110-150 TFLOP/s for the 4-wave tile 20)
+  if (d->N % 256 == 0 && tiles128x256 >= 1024) return 8;
+  if (tiles256x128 >= 512) return 7;
+  if (tiles128 >= 2048) return 5;
+  if (tiles128 < 192) return 6;
+  return 1;
 }
 
-// the tile a launch runs on: forced, or the automatic choice — which falls back to the fp32 halo / generic split tile when the
-// narrow-layer split kernel was chosen but the caller did not supply the fragment-order filter planes
-int resolve_tile(const qea_conv_desc* d, const ConvArgs& a) {
-  int tile = d->tile ? d->tile : pick_tile(d, a);
-  if (!d->tile && ((tile == 24 && !d->w_frag_planes) || (tile == 26 && !(d->w_frag_planes && d->x_absmax)))) {
+// Which kernel runs a descriptor, and everything the launch and the queries need to know about it: ONE answer, read by
+// qea_conv_igemm and by qea_conv_igemm_{stats_blocks, can_pool, uses_split_bf16, wants_frag_planes}.
+enum Family {
+  GENERIC_F32,      // conv_igemm_kernel: a row of TILES
+  GENERIC_SPLIT,    // conv_igemm_bf3_kernel / _bf3w_kernel / _p3_kernel by `form`: a row of TILES
+  HALO_F32,         // tile 4: conv3x3_halo_kernel
+  SPLIT_HALO,       // tile 24, 32x32x16 MFMA: conv3x3_halo_bf3_kernel
+  SPLIT_HALO_M16,   // tile 24, 16x16x32 MFMA (fp16 form, 64-channel chunks): conv_halo16.hip
+  GEMM_1X1,         // tile 26: gemm1x1.hip
+};
+enum Form { ON_THE_FLY, HYBRID, ALL_DMA };   // operands of a split tile: split in the kernel / filter planes by DMA / both by DMA
+
+struct Route {
+  int preferred;             // forced, or the automatic choice BEFORE the operand fallback: what wants_frag_planes, uses_split_bf16 and
+                             // can_pool report (ops.conv_igemm asks them before it has made the planes)
+  int tile;                  // the tile that runs given the operands actually supplied
+  Family family;
+  Form form;
+  const GenericTile* generic;   // row of TILES (generic families)
+  int planes;                // 3 (bf16) or 2 (fp16) per split operand; 0: fp32 MFMA
+  int stats_blocks;          // rows of partials the fused-statistics epilogue writes; 0: this launch has none
+  bool pool[3];              // [kw]: an instance with the fused 2 x kw max-pool exists (given the fp16 operands)
+  int tag;                   // profiler tag: the kernel that runs
+  unsigned xp_zero, wp_zero; // byte offset of the zero chunk behind the pre-split planes
+  char err[320];             // why the launch is refused (route() != QEA_OK)
+};
+
+#define ROUTE_REQUIRE(cond, ...)                     \
+  do {                                               \
+    if (!(cond)) {                                   \
+      snprintf(r->err, sizeof(r->err), __VA_ARGS__); \
+      return QEA_ERR_INVALID;                        \
+    }                                                \
+  } while (0)
+
+// Reads no device memory and dereferences no operand pointer.  Everything the queries read (preferred, tile, family, form, planes,
+// stats_blocks, pool, tag) is filled whatever is returned; xp_zero / wp_zero only once the planes have passed their checks.
+int route(const qea_conv_desc* d, Route* r) {
+  memset(r, 0, sizeof(*r));
+  const int M = d->B * d->OH * d->OW, K = d->KH * d->KW * d->Cin;
+  r->preferred = r->tile = d->tile ? d->tile : pick_tile(d, M, K);
+  // the automatic choice falls back to the fp32 halo / generic tiles when the caller did not supply what tile 24 / 26 read
+  if (!d->tile && ((r->tile == 24 && !d->w_frag_planes) || (r->tile == 26 && !(d->w_frag_planes && d->x_absmax)))) {
     qea_conv_desc e = *d;
-    e.tile = -1;                                           // the choice without tiles 24 / 26
-    tile = pick_tile(&e, a);
+    e.tile = -1;
+    r->tile = pick_tile(&e, M, K);
   }
-  return tile;
+  const int tile = r->tile;
+  r->generic = find_tile(tile);
+  if (tile >= FIRST_SPLIT_TILE && d->w_planes) r->form = d->x_planes ? ALL_DMA : HYBRID;
+  if (tile == 4) r->family = HALO_F32;
+  else if (tile == 24) r->family = (d->x_absmax && d->Cin % 64 == 0) ? SPLIT_HALO_M16 : SPLIT_HALO;
+  else if (tile == 26) r->family = GEMM_1X1;
+  else r->family = (r->generic && r->generic->hybrid) ? GENERIC_SPLIT : GENERIC_F32;
+  // two planes: the fp16 split, switched on by x_absmax (ABI v6) — of the generic tiles only the hybrid form has it
+  if (tile == 24 || tile == 26) r->planes = d->x_absmax ? 2 : 3;
+  else if (r->family == GENERIC_SPLIT) r->planes = (r->form == HYBRID && d->x_absmax) ? 2 : 3;
+
+  // fused statistics: the output must be the plain conv result (no scale / bias / ReLU / mask / accumulate, NHWC)
+  if (!(d->scale || d->bias || d->mask || d->relu || d->accumulate) && d->out_mode == QEA_OUT_NHWC) {
+    if (tile == 4 && halo_eligible(d)) r->stats_blocks = d->B * (d->H / (d->Cin == 32 ? 8 : 4)) * (d->W / 32) * 4;   // one per workgroup and wave
+    else if (tile == 24 && halo_bf3_eligible(d)) r->stats_blocks = (int)halo_bf3_tiles(d) * halo_bf3_wm(d);
+    else if (r->form == HYBRID && r->generic && r->generic->stats) r->stats_blocks = qea_cdiv(M, r->generic->BM) * r->generic->WGM;
+  }
+  for (int kw = 1; kw <= 2; ++kw) r->pool[kw] = r->preferred == 24 && halo_bf3_pool_shape(d, kw);
+  // tag = the kernel that runs: QEA_PROF_TAG_CONV(tile, input-channel chunk, output-channel group, fused statistics) for the
+  // LDS-halo split kernel (its template instantiation), the tile id otherwise
+  // (the small-image instantiations of the halo kernel are their own kernels in a trace: + 20 * image width)
+  // (... and so are the instances with the fused max-pool: + 2000 * window width; the fp16 form: + 5)
+  r->tag = tile != 24 ? tile
+                      : QEA_PROF_TAG_HALO_BF3(d->Cin == 32 ? 32 : 64, d->N > 128 ? 128 : d->N, d->stats != nullptr) + 20 * halo_bf3_small(d) +
+                            (d->pool_y ? 2000 * d->pool_kw : 0) + (d->x_absmax ? 5 : 0);
+
+  if (d->pool_y)                                           // fused max-pool: only where qea_conv_igemm_can_pool says so, fp16 operands given
+    ROUTE_REQUIRE(tile == 24 && (d->pool_kw == 1 || d->pool_kw == 2) && r->pool[d->pool_kw] && d->x_absmax && d->w_frag_planes && d->ldpool >= d->N &&
+                      d->ldpool % 4 == 0,
+                  "qea_conv_igemm: pool_y needs a launch qea_conv_igemm_can_pool accepts (tile 24, fp16 operands), ldpool >= N");
+  ROUTE_REQUIRE(tile != 4 || halo_eligible(d),
+                "qea_conv_igemm: tile 4 (LDS-halo 3x3) needs Cin,N in {32,64}, 3x3 pad 1 stride 1, W %% 32 == 0, no mask / accumulate");
+  if (r->form != ON_THE_FLY) {
+    const unsigned long long xb = r->form == ALL_DMA ? (unsigned long long)d->B * d->H * d->W * d->Cin * 6 : 0;
+    const unsigned long long wb = (unsigned long long)d->N * K * (r->form == HYBRID && d->x_absmax ? 4 : 6);
+    ROUTE_REQUIRE(d->Cin % 16 == 0 && xb + 128 < 0x7fffffffULL && wb + 128 < 0x7fffffffULL,
+                  "qea_conv_igemm: pre-split operands need Cin %% 16 == 0 and planes below 2 GiB (%llu, %llu bytes)", xb, wb);
+    ROUTE_REQUIRE(((uintptr_t)d->x_planes & 15) == 0 && ((uintptr_t)d->w_planes & 15) == 0, "qea_conv_igemm: planes must be 16-byte aligned");
+    r->xp_zero = (unsigned)xb;
+    r->wp_zero = (unsigned)wb;
+  }
+  ROUTE_REQUIRE(!d->stats || r->stats_blocks > 0, "qea_conv_igemm: this launch cannot produce fused statistics (ask qea_conv_igemm_stats_blocks first)");
+  if (d->bst_y)                                            // BatchNorm-backward sums instead of the forward statistics: LDS-halo kernel, fp16 form
+    ROUTE_REQUIRE(d->stats && tile == 24 && d->x_absmax && !d->pool_y && d->bst_stat64 && d->bst_scale && d->bst_shift && d->ldbst >= d->N,
+                  "qea_conv_igemm: bst_y needs stats (the partials), tile 24 with fp16 operands, bst_stat64 / bst_scale / bst_shift, ldbst >= N");
+  ROUTE_REQUIRE(tile != 24 || (halo_bf3_eligible(d) && d->w_frag_planes),
+                "qea_conv_igemm: tile 24 needs Cin = 32 or 64k <= 512, N in {32,64,128k}, 3x3 pad 1 stride 1, W %% 32 == 0 (or 4x16 / 2x8 images with Cin = 64k, N = 128k), no accumulate, and w_frag_planes");
+  ROUTE_REQUIRE(tile != 26 || (gemm1x1_eligible(d) && d->w_frag_planes && d->x_absmax),
+                "qea_conv_igemm: tile 26 needs a 1x1 stride-1 GEMM with Cin %% 64 == 0, N %% 128 == 0, no scale / mask / accumulate / stats, x_absmax and the w_frag_planes of qea_pack_frag_planes_f16_1x1");
+  ROUTE_REQUIRE(r->generic || tile == 4 || tile == 24 || tile == 26, "qea_conv_igemm: unknown tile id %d", tile);
+  return QEA_OK;
 }
 
-// Partial blocks the fused-statistics epilogue of this launch writes, 0 when the chosen kernel has none: the hybrid
-// split-bf16 tiles (one block per M-tile and wave row) and the fp32 LDS-halo kernel (one per workgroup and wave); the output
-// must be the plain conv result (no scale / bias / ReLU / mask / accumulate, NHWC).
-int stats_blocks_for(const qea_conv_desc* d, const ConvArgs& a, int tile, bool wp3) {
-  if (d->scale || d->bias || d->mask || d->relu || d->accumulate || d->out_mode != QEA_OUT_NHWC) return 0;
-  if (tile == 4 && halo_eligible(d)) return d->B * (d->H / (d->Cin == 32 ? 8 : 4)) * (d->W / 32) * 4;
-  if (tile == 24 && halo_bf3_eligible(d)) return (int)halo_bf3_tiles(d) * halo_bf3_wm(d);
-  if (!wp3) return 0;
-  switch (tile) {
-    case 21: return qea_cdiv(a.M, 256) * 4;
-    case 22: return qea_cdiv(a.M, 128) * 2;
-    case 23: return qea_cdiv(a.M, 256) * 4;
-    case 25: return qea_cdiv(a.M, 128) * 4;
-    default: return 0;
-  }
+// the queries route a descriptor that carries no device pointers; a descriptor no launch would take answers 0
+bool route_query(const qea_conv_desc* d, Route* r) {
+  if (!d || d->Cin <= 0 || d->Cin % 32 || d->B <= 0) return false;
+  (void)route(d, r);
+  return true;
 }
 
 }  // namespace
 
 extern "C" int qea_conv_igemm_stats_blocks(const qea_conv_desc* d) {
-  if (!d || d->Cin <= 0 || d->Cin % 32 || d->B <= 0) return 0;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.M = d->B * d->OH * d->OW;
-  a.N = d->N;
-  a.K = d->KH * d->KW * d->Cin;
-  const int tile = resolve_tile(d, a);
-  return stats_blocks_for(d, a, tile, tile >= 20 && !d->x_planes && d->w_planes);
+  Route r;
+  return route_query(d, &r) ? r.stats_blocks : 0;
 }
 
+extern "C" int qea_conv_igemm_can_pool(const qea_conv_desc* d, int32_t kw) {
+  Route r;
+  return (route_query(d, &r) && (kw == 1 || kw == 2) && r.pool[kw]) ? 1 : 0;
+}
+
+extern "C" int qea_conv_igemm_uses_split_bf16(const qea_conv_desc* d) {
+  Route r;
+  return (route_query(d, &r) && r.preferred >= FIRST_SPLIT_TILE) ? 1 : 0;
+}
+
+/* 1 when qea_conv_igemm would pick the LDS-halo kernel (tile 24: wants the w_frag_planes of qea_pack_frag_planes[_f16]); 2 when it
+ * would pick the 1x1 LDS tile (tile 26: wants those of qea_pack_frag_planes_f16_1x1 AND x_absmax — without them the launch runs on
+ * the generic tiles); else 0 */
+extern "C" int qea_conv_igemm_wants_frag_planes(const qea_conv_desc* d) {
+  Route r;
+  if (!route_query(d, &r)) return 0;
+  return r.preferred == 24 ? 1 : (r.preferred == 26 ? 2 : 0);
+}
+
+// four steps: validate the pointers and dimensions, route(), fill ConvArgs, launch by family
 extern "C" int qea_conv_igemm(const qea_conv_desc* d, void* stream) {
   QEA_REQUIRE(d && d->x && d->w && d->y, "qea_conv_igemm: null pointer");
   QEA_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->OH > 0 && d->OW > 0 && d->N > 0,
@@ -1746,106 +1776,47 @@ extern "C" int qea_conv_igemm(const qea_conv_desc* d, void* stream) {
   QEA_REQUIRE((long long)d->B * d->H * d->W < 0x7fffffffLL && (long long)d->B * d->OH * d->OW < 0x7fffffffLL,
               "qea_conv_igemm: pixel count overflows int32");
 
-  ConvArgs a;
+  Route r;
+  QEA_REQUIRE(route(d, &r) == QEA_OK, "%s", r.err);
+
+  ConvArgs a = {};
   a.x = d->x; a.w = d->w; a.y = d->y; a.scale = d->scale; a.bias = d->bias; a.mask = d->mask;
   a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.OH = d->OH; a.OW = d->OW; a.N = d->N;
   a.KH = d->KH; a.KW = d->KW; a.pad_h = d->pad_h; a.pad_w = d->pad_w; a.stride_h = d->stride_h; a.stride_w = d->stride_w;
   a.ldx = d->ldx; a.ldy = d->ldy; a.ldmask = d->ldmask; a.relu = d->relu; a.accumulate = d->accumulate; a.out_mode = d->out_mode;
-  a.xmax = nullptr;
-  a.yamax = d->y_absmax;
   a.M = d->B * d->OH * d->OW;
   a.K = d->KH * d->KW * d->Cin;
-  a.m_tiles = a.n_tiles = 0;
   a.xp = (const char*)d->x_planes;
-  a.wp = (const char*)d->w_planes;
-  a.xp_zero = a.wp_zero = 0;
-  a.stats = nullptr;
-  a.pool_y = nullptr;
-  a.ldpool = a.pool_kw = 0;
-  a.pool_amax = nullptr;
-  a.bst_y = nullptr;
-  a.ldbst = 0;
-  a.bst64 = nullptr;
-  a.bst_scale = a.bst_shift = nullptr;
-
-  hipStream_t s = (hipStream_t)stream;
-  int tile = resolve_tile(d, a);
-  if (d->pool_y) {                                         // fused max-pool: only where qea_conv_igemm_can_pool says so, fp16 operands given
-    QEA_REQUIRE(tile == 24 && halo_bf3_pool_shape(d, d->pool_kw) && d->x_absmax && d->w_frag_planes && d->ldpool >= d->N && d->ldpool % 4 == 0,
-                "qea_conv_igemm: pool_y needs a launch qea_conv_igemm_can_pool accepts (tile 24, fp16 operands), ldpool >= N");
+  // tiles 24 / 26 read the filter from its fragment-order planes
+  a.wp = (const char*)((r.tile == 24 || r.tile == 26) ? d->w_frag_planes : d->w_planes);
+  a.xp_zero = r.xp_zero;
+  a.wp_zero = r.wp_zero;
+  a.xmax = r.planes == 2 ? d->x_absmax : nullptr;          // non-NULL: fp16 planes + scales (ABI v6)
+  a.yamax = d->y_absmax;
+  a.stats = d->stats;
+  if (d->pool_y) {
     a.pool_y = d->pool_y;
     a.ldpool = d->ldpool;
     a.pool_kw = d->pool_kw;
     a.pool_amax = d->pool_absmax;
   }
-  if (tile == 4 && !halo_eligible(d)) {
-    qea_set_error("qea_conv_igemm: tile 4 (LDS-halo 3x3) needs Cin,N in {32,64}, 3x3 pad 1 stride 1, W %% 32 == 0, no mask / accumulate");
-    return QEA_ERR_INVALID;
-  }
-  const bool p3 = tile >= 20 && d->x_planes && d->w_planes;
-  const bool wp3 = tile >= 20 && !d->x_planes && d->w_planes;
-  if (p3 || wp3) {
-    const bool f16w = wp3 && d->x_absmax;                  // hybrid tile on the two-way fp16 split: two planes per value
-    const unsigned long long xb = p3 ? (unsigned long long)d->B * d->H * d->W * d->Cin * 6 : 0, wb = (unsigned long long)d->N * a.K * (f16w ? 4 : 6);
-    if (f16w) a.xmax = d->x_absmax;
-    QEA_REQUIRE(d->Cin % 16 == 0 && xb + 128 < 0x7fffffffULL && wb + 128 < 0x7fffffffULL,
-                "qea_conv_igemm: pre-split operands need Cin %% 16 == 0 and planes below 2 GiB (%llu, %llu bytes)", xb, wb);
-    QEA_REQUIRE(((uintptr_t)d->x_planes & 15) == 0 && ((uintptr_t)d->w_planes & 15) == 0, "qea_conv_igemm: planes must be 16-byte aligned");
-    a.xp_zero = (unsigned)xb;
-    a.wp_zero = (unsigned)wb;
-  }
-  if (d->stats) {
-    const int blocks = stats_blocks_for(d, a, tile, wp3);
-    QEA_REQUIRE(blocks > 0, "qea_conv_igemm: this launch cannot produce fused statistics (ask qea_conv_igemm_stats_blocks first)");
-    a.stats = d->stats;
-  }
-  if (d->bst_y) {                                          // BatchNorm-backward sums instead of the forward statistics: LDS-halo kernel, fp16 form
-    QEA_REQUIRE(d->stats && tile == 24 && d->x_absmax && !d->pool_y && d->bst_stat64 && d->bst_scale && d->bst_shift && d->ldbst >= d->N,
-                "qea_conv_igemm: bst_y needs stats (the partials), tile 24 with fp16 operands, bst_stat64 / bst_scale / bst_shift, ldbst >= N");
+  if (d->bst_y) {
     a.bst_y = d->bst_y;
     a.ldbst = d->ldbst;
     a.bst64 = d->bst_stat64;
     a.bst_scale = d->bst_scale;
     a.bst_shift = d->bst_shift;
   }
-  if (tile == 24 && (!halo_bf3_eligible(d) || !d->w_frag_planes)) {
-    qea_set_error("qea_conv_igemm: tile 24 needs Cin = 32 or 64k <= 512, N in {32,64,128k}, 3x3 pad 1 stride 1, W %% 32 == 0 (or 4x16 / 2x8 images with Cin = 64k, N = 128k), no accumulate, and w_frag_planes");
-    return QEA_ERR_INVALID;
-  }
-  if (tile == 26 && (!gemm1x1_eligible(d) || !d->w_frag_planes || !d->x_absmax)) {
-    qea_set_error("qea_conv_igemm: tile 26 needs a 1x1 stride-1 GEMM with Cin %% 64 == 0, N %% 128 == 0, no scale / mask / accumulate / stats, x_absmax and the w_frag_planes of qea_pack_frag_planes_f16_1x1");
-    return QEA_ERR_INVALID;
-  }
+
+  hipStream_t s = (hipStream_t)stream;
   qea_prof_begin(QEA_PROF_CONV_IGEMM, s);
   int rc;
-  switch (tile) {
-    case 4: rc = launch_halo_any(d, a, s); break;
-    case 26:                                               // 1x1 / transposed-conv GEMM on the 128-row LDS tile (gemm1x1.hip)
-      a.wp = (const char*)d->w_frag_planes;
-      a.xmax = d->x_absmax;
-      rc = qea_conv::launch_gemm1x1_f16(a, s);
-      break;
-    case 24:                                               // split-bf16 LDS-halo kernel of the narrow layers: filter in fragment-order planes
-      a.wp = (const char*)d->w_frag_planes;
-      a.xmax = d->x_absmax;                                // non-NULL: fp16 planes + scales (ABI v6)
-      rc = launch_halo_bf3_any(d, a, s);
-      break;
-    case 1: rc = launch<128, 128, 2, 2, 32>(a, s); break;
-    case 2: rc = launch<256, 64, 4, 1, 32>(a, s); break;
-    case 3: rc = launch<256, 32, 4, 1, 32>(a, s); break;
-    case 5: rc = launch<128, 128, 2, 2, 16>(a, s); break;
-    case 6: rc = launch<128, 64, 2, 2, 32>(a, s); break;   // small grids: twice the workgroups of tile 1
-    case 7: rc = launch<256, 128, 4, 2, 16>(a, s); break;  // 8 waves
-    case 8: rc = launch<128, 256, 2, 4, 16>(a, s); break;  // 8 waves
-    case 9: rc = launch<256, 64, 4, 1, 16>(a, s); break;   // tile 2 with half the LDS (3 workgroups per CU)
-    // split-bf16 forms; with pre-split operands (x_planes, w_planes) the LDS-DMA kernel, else the split-on-the-fly kernel
-    // (x_planes + w_planes: all-DMA kernel; w_planes only: hybrid — activations split on the fly, filter by DMA)
-    case 20: rc = p3 ? launch_p3<128, 128, 2, 2>(a, s) : wp3 ? launch_bf3w<128, 128, 2, 2>(a, s) : launch_bf3<128, 128, 2, 2>(a, s); break;
-    case 21: rc = p3 ? launch_p3<256, 128, 4, 2>(a, s) : wp3 ? launch_bf3w<256, 128, 4, 2>(a, s) : launch_bf3<256, 128, 4, 2>(a, s); break;
-    case 22: rc = p3 ? launch_p3<128, 256, 2, 4>(a, s) : wp3 ? launch_bf3w<128, 256, 2, 4>(a, s) : launch_bf3<128, 256, 2, 4>(a, s); break;
-    case 23: rc = p3 ? launch_p3<256, 64, 4, 1>(a, s) : wp3 ? launch_bf3w<256, 64, 4, 1>(a, s) : launch_bf3<256, 64, 4, 1>(a, s); break;
-    case 25: rc = p3 ? launch_p3<128, 128, 4, 2>(a, s) : wp3 ? launch_bf3w<128, 128, 4, 2>(a, s) : launch_bf3<128, 128, 4, 2>(a, s); break;  // 8 waves on a 128x128 tile: small grids
-    default: qea_set_error("qea_conv_igemm: unknown tile id %d", tile); rc = QEA_ERR_INVALID; break;
+  switch (r.family) {
+    case HALO_F32: rc = launch_halo_any(d, a, s); break;
+    case SPLIT_HALO: rc = launch_halo_bf3_any(d, a, s); break;
+    case SPLIT_HALO_M16: rc = qea_conv::launch_halo_m16_any(d->N == 32 ? 32 : (d->N == 64 ? 64 : 128), halo_bf3_small(d), a, s); break;
+    case GEMM_1X1: rc = qea_conv::launch_gemm1x1_f16(a, s); break;
+    default: rc = (r.form == ALL_DMA ? r.generic->dma : r.form == HYBRID ? r.generic->hybrid : r.generic->fly)(a, s); break;
   }
   if (rc != QEA_OK) {
     qea_prof_abort(QEA_PROF_CONV_IGEMM);
@@ -1853,38 +1824,9 @@ extern "C" int qea_conv_igemm(const qea_conv_desc* d, void* stream) {
   }
   // algorithmic bytes: input once + filter once + output once
   const double abytes = 4.0 * ((double)d->B * d->H * d->W * d->Cin + (double)d->N * a.K + (double)a.M * d->N);
-  // tag = the kernel that ran: QEA_PROF_TAG_CONV(tile, input-channel chunk, output-channel group, fused statistics) for the
-  // LDS-halo split kernel (its template instantiation), the tile id otherwise
-  // (the small-image instantiations of the halo kernel are their own kernels in a trace: + 20 * image width)
-  // (... and so are the instances with the fused max-pool: + 2000 * window width)
-  const int tag = tile == 24 ? QEA_PROF_TAG_HALO_BF3(d->Cin == 32 ? 32 : 64, d->N > 128 ? 128 : d->N, a.stats != nullptr) + 20 * halo_bf3_small(d) +
-                                   (a.pool_y ? 2000 * a.pool_kw : 0)
-                             : tile;
-  qea_prof_end(QEA_PROF_CONV_IGEMM, s, 2.0 * a.M * (double)a.N * a.K, abytes, tile >= 20 ? (a.xmax ? 2 : 1) : 0, tag + (tile == 24 && a.xmax ? 5 : 0));
+  qea_prof_end(QEA_PROF_CONV_IGEMM, s, 2.0 * a.M * (double)a.N * a.K, abytes, r.planes == 2 ? 2 : (r.planes == 3 ? 1 : 0), r.tag);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
-}
-
-extern "C" int qea_conv_igemm_can_pool(const qea_conv_desc* d, int32_t kw) {
-  if (!d || d->Cin <= 0 || d->Cin % 32 || d->B <= 0) return 0;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.M = d->B * d->OH * d->OW;
-  a.N = d->N;
-  a.K = d->KH * d->KW * d->Cin;
-  const int tile = d->tile ? d->tile : pick_tile(d, a);
-  return (tile == 24 && halo_bf3_pool_shape(d, kw)) ? 1 : 0;
-}
-
-extern "C" int qea_conv_igemm_uses_split_bf16(const qea_conv_desc* d) {
-  if (!d || d->Cin <= 0 || d->Cin % 32 || d->B <= 0) return 0;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.M = d->B * d->OH * d->OW;
-  a.N = d->N;
-  a.K = d->KH * d->KW * d->Cin;
-  const int tile = d->tile ? d->tile : pick_tile(d, a);
-  return tile >= 20 ? 1 : 0;
 }
 
 extern "C" size_t qea_split_planes_bytes(int64_t M, int32_t C) { return (size_t)M * (size_t)C * 6 + 128; }
@@ -1941,18 +1883,4 @@ extern "C" int qea_pack_frag_planes_f16(const float* w, int32_t N, int32_t Cin, 
                      Cin == 32 ? 32 : 64, wmax);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
-}
-
-/* 1 when qea_conv_igemm would pick the LDS-halo kernel (tile 24: wants the w_frag_planes of qea_pack_frag_planes[_f16]); 2 when it
- * would pick the 1x1 LDS tile (tile 26: wants those of qea_pack_frag_planes_f16_1x1 AND x_absmax — without them the launch runs on
- * the generic tiles); else 0 */
-extern "C" int qea_conv_igemm_wants_frag_planes(const qea_conv_desc* d) {
-  if (!d || d->Cin <= 0 || d->Cin % 32 || d->B <= 0) return 0;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.M = d->B * d->OH * d->OW;
-  a.N = d->N;
-  a.K = d->KH * d->KW * d->Cin;
-  const int tile = d->tile ? d->tile : pick_tile(d, a);
-  return tile == 24 ? 1 : (tile == 26 ? 2 : 0);
 }

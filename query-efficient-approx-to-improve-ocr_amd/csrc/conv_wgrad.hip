@@ -493,24 +493,13 @@ size_t slab_workspace_bytes(size_t slab_floats, int splits) {
   return b;
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel; a refused reservation fails every launch of that kernel
-template <auto Kernel>
-int reserve_lds(size_t bytes) {
-  static const hipError_t rc = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (rc != hipSuccess) {
-    qea_set_error("qea_conv_wgrad: cannot reserve %zu bytes of LDS: %s", bytes, hipGetErrorString(rc));
-    return QEA_ERR_LAUNCH;
-  }
-  return QEA_OK;
-}
-
 // workgroups of this kernel the whole chip holds at once (asked once per kernel)
 template <auto Kernel>
 int resident_slots(int threads, size_t lds) {
   static int slots = 0;
   if (slots == 0) {
     int per_cu = 0, dev = 0, cus = 0;
-    (void)reserve_lds<Kernel>(lds);
+    (void)reserve_lds<Kernel>("qea_conv_wgrad", lds);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kernel, threads, lds) != hipSuccess || per_cu < 1) per_cu = 2;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
       cus = 256;
@@ -534,7 +523,7 @@ constexpr size_t lds_bytes_bf3() {
 
 template <auto Kernel, size_t LDS>
 int launch_tile(const WgArgs& a, hipStream_t s) {
-  const int rc = reserve_lds<Kernel>(LDS);
+  const int rc = reserve_lds<Kernel>("qea_conv_wgrad", LDS);
   if (rc != QEA_OK) return rc;
   hipLaunchKernelGGL(Kernel, dim3((unsigned)a.tiles * (unsigned)a.splits), dim3(256), LDS, s, a);
   return QEA_OK;
@@ -806,7 +795,7 @@ HaloPlan halo_plan(const qea_wgrad_desc* d) {
 template <int R, int C, int TH>
 int launch_halo_(const qea_wgrad_desc* d, const HaloPlan& h, hipStream_t s) {
   constexpr size_t lds = ((size_t)TH * 32 * R + (size_t)(TH + 2) * 34 * C) * sizeof(float);
-  const int rc = reserve_lds<wgrad_halo_kernel<R, C, TH>>(lds);
+  const int rc = reserve_lds<wgrad_halo_kernel<R, C, TH>>("qea_conv_wgrad", lds);
   if (rc != QEA_OK) return rc;
   hipLaunchKernelGGL((wgrad_halo_kernel<R, C, TH>), dim3(h.grid), dim3(256), lds, s, d->p, d->q, (float*)d->workspace, d->B, d->PH, d->PW, d->ldp,
                      d->ldq, h.n_tiles);
@@ -1510,7 +1499,7 @@ Halo9Plan halo9_plan(const qea_wgrad_desc* d) {
 template <int SW, int RB, int CB, int NPL>
 int launch_halo9_(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s) {
   constexpr size_t lds = (size_t)NPL * (64 * RB + H9_HP_MAX * CB) * 2;
-  const int rc = reserve_lds<wgrad_halo9_bf3_kernel<SW, RB, CB, NPL>>(lds);
+  const int rc = reserve_lds<wgrad_halo9_bf3_kernel<SW, RB, CB, NPL>>("qea_conv_wgrad", lds);
   if (rc != QEA_OK) return rc;
   hipLaunchKernelGGL((wgrad_halo9_bf3_kernel<SW, RB, CB, NPL>), dim3((unsigned)((long long)h.r_blks * h.c_blks * h.splits)), dim3(256), lds, s, d->p, d->q,
                      (float*)d->workspace, d->B, d->PH, d->PW, d->R, d->C, d->ldp, d->ldq, h, d->p_absmax, d->q_absmax);
@@ -1526,7 +1515,7 @@ int launch_halo9_any(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s)
 // the producer / consumer forms: the ring kernel for 32-pixel-wide tiles, wgrad_halo9_spec_kernel<16> for the 16-wide ones
 template <auto Kernel, size_t LDS>
 int launch_halo9_pc(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s, double* bias_ws) {
-  const int rc = reserve_lds<Kernel>(LDS);
+  const int rc = reserve_lds<Kernel>("qea_conv_wgrad", LDS);
   if (rc != QEA_OK) return rc;
   hipLaunchKernelGGL(Kernel, dim3((unsigned)((long long)h.r_blks * h.c_blks * h.splits)), dim3(512), LDS, s, d->p, d->q, (float*)d->workspace, d->B, d->PH, d->PW,
                      d->R, d->C, d->ldp, d->ldq, h, d->p_absmax, d->q_absmax, bias_ws);

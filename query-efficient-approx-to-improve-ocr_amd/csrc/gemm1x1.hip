@@ -233,23 +233,15 @@ template <int CIN, int WM, int NJ>
 int launch_(const ConvArgs& a, hipStream_t s) {
   constexpr int NB = (4 / WM) * NJ * 32;
   constexpr size_t lds = (size_t)2 * 128 * CIN * 2 + 2 * 128 * sizeof(int);
-  auto kern = gemm1x1_f16_kernel<CIN, WM, NJ>;
-  static int attr_rc = (int)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr_rc != (int)hipSuccess) {
-    qea_set_error("qea_conv_igemm(1x1 tile): cannot reserve %zu bytes of LDS: %s", (size_t)lds, hipGetErrorString((hipError_t)attr_rc));
-    return QEA_ERR_LAUNCH;
-  }
+  constexpr auto kern = gemm1x1_f16_kernel<CIN, WM, NJ>;
+  const int rc = reserve_lds<kern>("qea_conv_igemm(1x1 tile)", lds);
+  if (rc != QEA_OK) return rc;
   const long long total = (long long)qea_cdiv(a.M, 128) * (a.N / NB);
   if (total <= 0 || total > 0x7fffffffLL) {
     qea_set_error("qea_conv_igemm(1x1 tile): grid %lld out of range", total);
     return QEA_ERR_INVALID;
   }
-  static const int resident = [] {
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return gemm1x1_wgs(CIN, WM, NJ) * (cus & ~7);
-  }();
+  const int resident = qea_persistent_grid(gemm1x1_wgs(CIN, WM, NJ));
   const unsigned grid = total > resident ? (unsigned)resident : (unsigned)total;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, (const _Float16*)a.wp, a.K / CIN, (int)total);
   return QEA_OK;

@@ -439,3 +439,74 @@ def test_max_pool_in_the_conv_epilogue_is_bit_identical(Cin, Cout, H, W, B, kw):
         assert not ops.conv_can_pool(B=B, H=H, W=W, Cin=Cin, N=Cout, kw=3, ldx=Cin, ldy=Cout)
     finally:
         ops.set_mfma_mode(prev)
+
+
+def _stats_launch(B, H, W, Cin, Cout, tile, form):
+    """One 3x3 pad-1 launch through the C ABI with `stats` set; form: None (no extra operand), "hybrid" (bf16 w_planes), "hybrid16" (fp16
+    w_planes + x_absmax), "frag" (bf16 fragment planes) or "frag16" (fp16 fragment planes + x_absmax).  Returns (rc, blocks the query reported, partials, y)."""
+    from qea import _lib, ops
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(B * 1000 + Cin + Cout + tile)
+    x = torch.randn(B, H, W, Cin, generator=g).cuda()
+    w = (torch.randn(Cout, 3, 3, Cin, generator=g) * 0.05).cuda()
+    y = torch.full((B * H * W, Cout), float("nan"), device="cuda")
+    d = _lib.ConvDesc(x=x.data_ptr(), w=w.data_ptr(), y=y.data_ptr(), B=B, H=H, W=W, Cin=Cin, OH=H, OW=W, N=Cout, KH=3, KW=3, pad_h=1, pad_w=1,
+                      stride_h=1, stride_w=1, ldx=Cin, ldy=Cout, out_mode=0, tile=tile)
+    keep = []
+    if form == "hybrid":
+        keep.append(ops.split_planes(w, 9 * Cin, Cout, 9 * Cin))
+        d.w_planes = keep[-1].data_ptr()
+    elif form == "hybrid16":
+        keep += [ops.split_planes_f16(w, 9 * Cin, Cout, 9 * Cin), ops.absmax(x, Cin, B * H * W, Cin)]
+        d.w_planes, d.x_absmax = keep[0].data_ptr(), keep[1].data_ptr()
+    elif form == "frag":
+        keep.append(torch.empty(L.qea_pack_frag_planes_bytes(Cout, Cin), dtype=torch.uint8, device="cuda"))
+        _lib.check(L.qea_pack_frag_planes(w.data_ptr(), Cout, Cin, keep[-1].data_ptr(), ops._stream()), "qea_pack_frag_planes")
+        d.w_frag_planes = keep[-1].data_ptr()
+    elif form == "frag16":
+        keep += [ops.absmax(w, 9 * Cin, Cout, 9 * Cin), ops.absmax(x, Cin, B * H * W, Cin),
+                 torch.empty(L.qea_pack_frag_planes_f16_bytes(Cout, Cin), dtype=torch.uint8, device="cuda")]
+        _lib.check(L.qea_pack_frag_planes_f16(w.data_ptr(), Cout, Cin, keep[0].data_ptr(), keep[2].data_ptr(), ops._stream()), "qea_pack_frag_planes_f16")
+        d.w_frag_planes, d.x_absmax = keep[2].data_ptr(), keep[1].data_ptr()
+    blocks = L.qea_conv_igemm_stats_blocks(C.byref(d))
+    part = torch.full((blocks + 8, Cout, 2), float("nan"), dtype=torch.float64, device="cuda")
+    d.stats = part.data_ptr()
+    rc = L.qea_conv_igemm(C.byref(d), ops._stream())
+    torch.cuda.synchronize()
+    return rc, blocks, part.cpu(), y.cpu().double()
+
+
+@pytest.mark.parametrize("shape,tile,form", [
+    ((3, 8, 32, 32, 32), 4, None), ((3, 8, 32, 32, 32), 24, "frag"), ((3, 8, 32, 32, 32), 24, "frag16"),      # fp32 halo; split halo, both splits
+    ((2, 4, 32, 64, 128), 24, "frag16"), ((2, 4, 32, 64, 128), 24, "frag"),                                   # 16x16x32 form; its bf16 sibling
+    ((5, 4, 16, 64, 128), 24, "frag16"), ((5, 4, 16, 64, 128), 24, "frag"),                                   # small images, last tile partly empty
+    ((2, 8, 32, 128, 256), 21, "hybrid"), ((2, 8, 32, 128, 256), 22, "hybrid"), ((2, 8, 32, 128, 256), 23, "hybrid"),
+    ((2, 8, 32, 128, 256), 25, "hybrid"),
+    ((5, 7, 9, 64, 40), 21, "hybrid"), ((5, 7, 9, 64, 40), 22, "hybrid"), ((5, 7, 9, 64, 40), 23, "hybrid"),  # M = 315, N = 40: ragged last tiles
+    ((5, 7, 9, 64, 40), 25, "hybrid"),
+    ((2, 8, 32, 128, 256), 23, "hybrid16"), ((5, 7, 9, 64, 40), 21, "hybrid16")])                             # the hybrid tiles' fp16 form
+def test_stats_blocks_query_is_the_rows_the_launch_writes(shape, tile, form):
+    """qea_conv_igemm_stats_blocks and the launch read one route(): the launch fills exactly rows [0, blocks) of the partials — finite,
+    summing to the fp64 column sums of the stored output within test_fused_bn_statistics_epilogue's gate (1e-12 of the largest
+    magnitude, on the mean) — and leaves the rows behind them untouched."""
+    B, H, W, Cin, Cout = shape
+    rc, blocks, part, y = _stats_launch(B, H, W, Cin, Cout, tile, form)
+    assert rc == 0 and blocks > 0, (rc, blocks)
+    assert torch.isfinite(y).all()
+    assert torch.isfinite(part[:blocks]).all(), "a row the query promised was not written"
+    assert torch.isnan(part[blocks:]).all(), "the launch wrote behind the rows the query reported"
+    M = B * H * W
+    sums = part[:blocks].sum(0)
+    e1 = (sums[:, 0] / M - y.mean(0)).abs().max().item()
+    e2 = (sums[:, 1] / M - (y * y).mean(0)).abs().max().item()
+    print(f"tile {tile} {form} {shape}: blocks {blocks}, mean err {e1:.3e}, mean-square err {e2:.3e}")
+    assert e1 <= 1e-12 * max(1.0, y.abs().max().item())
+    assert e2 <= 1e-12 * max(1.0, (y * y).max().item())
+
+
+def test_tile_20_reports_no_statistics_and_refuses_them():
+    from qea import _lib
+    rc, blocks, part, _ = _stats_launch(2, 8, 32, 128, 256, 20, "hybrid")
+    assert blocks == 0 and rc != 0
+    assert "cannot produce fused statistics" in _lib.lib().qea_last_error().decode()
+    assert torch.isnan(part).all()
