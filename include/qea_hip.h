@@ -304,7 +304,8 @@ int qea_bn_bwd_pool(const float* da, int32_t ldda, const float* dpool, int32_t l
                     void* stream);
 /* ABI v7 (additive).  qea_bn_bwd with the two per-channel reductions taken from `partials` [blocks (+ 256 scratch rows)][C][2] fp64, as
  * written by the producing input-gradient launch (qea_conv_desc.bst_y), instead of a pass over da and y: finalize + the elementwise
- * pass only.  stat64 and relu_scale / relu_shift are required (what the producer used); workspace: 3 * C doubles. */
+ * pass only.  stat64 and relu_scale / relu_shift are required (what the producer used); workspace: 3 * C doubles.  As its two siblings it
+ * needs C % 4 == 0 and C / 4 <= 256 (one float4 column per thread) and answers QEA_ERR_INVALID otherwise, before any launch. */
 int qea_bn_bwd_from_partials(const double* partials, int32_t blocks, const float* da, int32_t ldda, const float* relu_scale,
                              const float* relu_shift, const float* y, int32_t ldy, int64_t M, int32_t C, const float* gamma,
                              const float* mean, const float* invstd, const double* stat64, int32_t training, float* dgamma, float* dbeta,

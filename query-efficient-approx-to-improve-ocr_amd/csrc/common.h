@@ -89,6 +89,14 @@ void qea_set_error(const char* fmt, ...);
 
 static inline int qea_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// grid of a grid-stride launch of 256-thread workgroups over n items, at most `cap` workgroups
+static inline int qea_grid_for(long long n, int cap = 4096) {
+  long long g = (n + 255) / 256;
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel; a refused reservation fails every launch of that kernel.
 // `who` names the entry point in the error text.
 template <auto Kernel>
@@ -133,6 +141,15 @@ __device__ __forceinline__ double qea_wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+// The finalize kernels give ONE WAVE to an output element e: lane l adds rows l, l + 64, ... of the nblk partial rows ws[row * stride + e]
+// in fp64, then the xor butterfly (every lane returns the sum).  A fixed order: bit-reproducible.  A single thread walking up to 1024
+// dependent L2 loads per element took ~200 us.
+template <class T>
+__device__ __forceinline__ double qea_wave_partial_sum(const T* __restrict__ ws, int nblk, size_t stride, size_t e) {
+  double s = 0;
+  for (int k = threadIdx.x & 63; k < nblk; k += 64) s += (double)ws[(size_t)k * stride + e];
+  return qea_wave_sum_d(s);
 }
 __device__ __forceinline__ float qea_wave_max(float v) {
 #pragma unroll

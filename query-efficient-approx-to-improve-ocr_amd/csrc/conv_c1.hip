@@ -231,9 +231,7 @@ __global__ void conv_c1_wgrad_finalize_kernel(const float* __restrict__ ws, int 
   // one wave per output element: lanes stride over the partial blocks
   const int e = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // tap*Co + co
   if (e >= 10 * Co) return;
-  double s = 0;
-  for (int b = threadIdx.x & 63; b < nblk; b += 64) s += (double)ws[(size_t)b * 10 * Co + e];
-  s = qea_wave_sum_d(s);
+  const double s = qea_wave_partial_sum(ws, nblk, (size_t)10 * Co, e);
   if ((threadIdx.x & 63) != 0) return;
   const int tap = e / Co, co = e - tap * Co;
   if (tap < 9) {
@@ -605,19 +603,10 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 __global__ void head_bwd_finalize_kernel(const double* __restrict__ ws, int nblk, int C, float* dw, float* db, int accumulate) {
   const int e = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (e > C) return;
-  double s = 0;
-  for (int b = threadIdx.x & 63; b < nblk; b += 64) s += ws[(size_t)b * (C + 1) + e];
-  s = qea_wave_sum_d(s);
+  const double s = qea_wave_partial_sum(ws, nblk, (size_t)C + 1, e);
   if ((threadIdx.x & 63) != 0) return;
   float* d = (e < C) ? dw + e : db;
   *d = accumulate ? *d + (float)s : (float)s;
-}
-
-int grid_for(long long n, int cap = 4096) {
-  long long g = (n + 255) / 256;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
 }
 
 }  // namespace
@@ -638,7 +627,7 @@ extern "C" int qea_conv_c1_fwd(const float* x, const float* w, const float* bias
     QEA_CHECK_LAUNCH();
     return QEA_OK;
   }
-  hipLaunchKernelGGL(conv_c1_fwd_kernel, dim3(grid_for(n, 8192)), dim3(256), (size_t)Co * 9 * sizeof(float), (hipStream_t)stream, x, w, bias, y,
+  hipLaunchKernelGGL(conv_c1_fwd_kernel, dim3(qea_grid_for(n, 8192)), dim3(256), (size_t)Co * 9 * sizeof(float), (hipStream_t)stream, x, w, bias, y,
                      ldy, B, H, W, Co, relu);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
@@ -739,7 +728,7 @@ extern "C" int qea_conv_c1_pool_bwd(const float* x, const float* w, const float*
   }
   float* part = (float*)wsb;
   hipStream_t s = (hipStream_t)stream;
-  const int rgrid = grid_for(NW, 8192);
+  const int rgrid = qea_grid_for(NW, 8192);
   if (dx) hipLaunchKernelGGL(c1_pool_route_kernel<true>, dim3(rgrid), dim3(256), 0, s, x, w, bias, dpool, lddp, idx, T, B, H, W);
   else hipLaunchKernelGGL(c1_pool_route_kernel<false>, dim3(rgrid), dim3(256), 0, s, x, w, bias, dpool, lddp, idx, T, B, H, W);
   if (dw) {
@@ -748,7 +737,7 @@ extern "C" int qea_conv_c1_pool_bwd(const float* x, const float* w, const float*
     hipLaunchKernelGGL(conv_c1_wgrad_finalize_kernel, dim3(qea_cdiv(10 * Co, 4)), dim3(256), 0, s, (const float*)part, (int)(blocks * 4), Co, dw, db,
                        accumulate);
   }
-  if (dx) hipLaunchKernelGGL(c1_pool_dx_kernel, dim3(grid_for((long long)B * H * W, 8192)), dim3(256), 0, s, (const float*)T, dx, B, H, W, 0);
+  if (dx) hipLaunchKernelGGL(c1_pool_dx_kernel, dim3(qea_grid_for((long long)B * H * W, 8192)), dim3(256), 0, s, (const float*)T, dx, B, H, W, 0);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -757,7 +746,7 @@ extern "C" int qea_conv_c1_dgrad(const float* dy, int32_t lddy, const float* w, 
                                  int32_t accumulate, void* stream) {
   QEA_REQUIRE(dy && w && dx && B > 0 && H > 0 && W > 0 && lddy % 4 == 0, "qea_conv_c1_dgrad: bad arguments");
   const long long n = (long long)B * H * W * (Co / 4);
-  const int grid = grid_for(n, 8192);
+  const int grid = qea_grid_for(n, 8192);
   hipStream_t s = (hipStream_t)stream;
   const int tiles_x = qea_cdiv(W, C1D_TW), tiles_y = qea_cdiv(H, C1D_TH);
   const long long tiles = (long long)B * tiles_x * tiles_y;
@@ -780,7 +769,7 @@ extern "C" int qea_conv_c1_dgrad(const float* dy, int32_t lddy, const float* w, 
 
 extern "C" int qea_head_fwd(const float* x, int32_t ldx, const float* w, const float* b, float* y, int64_t M, int32_t C, void* stream) {
   QEA_REQUIRE(x && w && b && y && M > 0 && ldx % 4 == 0, "qea_head_fwd: bad arguments");
-  const int grid = grid_for(M * (C / 4), 8192);
+  const int grid = qea_grid_for(M * (C / 4), 8192);
   hipStream_t s = (hipStream_t)stream;
   switch (C) {
     case 32: hipLaunchKernelGGL(head_fwd_kernel<8>, dim3(grid), dim3(256), 0, s, x, ldx, w, b, y, (long long)M); break;
@@ -793,14 +782,14 @@ extern "C" int qea_head_fwd(const float* x, int32_t ldx, const float* w, const f
 
 extern "C" size_t qea_head_bwd_workspace_bytes(int64_t M, int32_t C) {
   if (M <= 0 || C <= 0) return 0;
-  return (size_t)grid_for(M * (C / 4), 1024) * (C + 1) * sizeof(double);
+  return (size_t)qea_grid_for(M * (C / 4), 1024) * (C + 1) * sizeof(double);
 }
 
 extern "C" int qea_head_bwd(const float* x, int32_t ldx, const float* y, const float* dyy, const float* w, float* dx, int32_t lddx,
                             float* dw, float* db, int32_t accumulate, int64_t M, int32_t C, void* workspace, size_t workspace_bytes,
                             void* stream) {
   QEA_REQUIRE(x && y && dyy && w && dx && dw && db && M > 0 && ldx % 4 == 0 && lddx % 4 == 0, "qea_head_bwd: bad arguments");
-  const int grid = grid_for(M * (C / 4), 1024);
+  const int grid = qea_grid_for(M * (C / 4), 1024);
   QEA_REQUIRE(workspace && workspace_bytes >= (size_t)grid * (C + 1) * sizeof(double), "qea_head_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   switch (C) {

@@ -1057,11 +1057,8 @@ __device__ __forceinline__ f16x8 tr_pair128(const char* base) {   // this lane's
 __global__ void bias_finalize_kernel(const double* __restrict__ ws, int nblk, int R, float* __restrict__ out, int accumulate) {
   const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (c >= R) return;
-  const int lane = threadIdx.x & 63;
-  double a = 0;
-  for (int k = lane; k < nblk; k += 64) a += ws[(size_t)k * R + c];
-  a = qea_wave_sum_d(a);
-  if (lane == 0) out[c] = accumulate ? out[c] + (float)a : (float)a;
+  const double a = qea_wave_partial_sum(ws, nblk, R, c);
+  if ((threadIdx.x & 63) == 0) out[c] = accumulate ? out[c] + (float)a : (float)a;
 }
 
 template <int SW>

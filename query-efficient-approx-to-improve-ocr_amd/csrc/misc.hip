@@ -228,13 +228,6 @@ __global__ __launch_bounds__(ED_LANES) void edit_distance_kernel(const int* __re
   out[n] = edit_distance_lane(row, lane, gt_len[n], min(pred_len[n], ED_MAX), [g](int i) { return g[i]; }, [p](int j) { return p[j]; });
 }
 
-int grid_for(long long n, int cap = 4096) {
-  long long g = (n + 255) / 256;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // step += 1;  coef = {lr / (1 - beta1^step), sqrt(1 - beta2^step)}   (same fp64 formulas as the host path)
 __global__ void adam_coeff_kernel(float* step, float* coef, float lr, float beta1, float beta2) {
   const double t = (double)step[0] + 1.0;
@@ -250,7 +243,7 @@ extern "C" int qea_adam_step_capturable(float* p, const float* g, float* m, floa
   QEA_REQUIRE(p && g && m && v && step && coef && n > 0, "qea_adam_step_capturable: bad arguments");
   QEA_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "qea_adam_step_capturable: buffers must be 16-byte aligned");
   hipLaunchKernelGGL(adam_coeff_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, coef, lr, beta1, beta2);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, beta1, beta2, eps,
+  hipLaunchKernelGGL(adam_kernel, dim3(qea_grid_for(n / 4 + 1, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, beta1, beta2, eps,
                      weight_decay, 0.f, 1.f, grad_scale, (const float*)coef);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
@@ -262,7 +255,7 @@ extern "C" int qea_adam_step(float* p, const float* g, float* m, float* v, int64
   QEA_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "qea_adam_step: buffers must be 16-byte aligned");
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, beta1, beta2, eps,
+  hipLaunchKernelGGL(adam_kernel, dim3(qea_grid_for(n / 4 + 1, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, beta1, beta2, eps,
                      weight_decay, (float)((double)lr / bc1), (float)sqrt(bc2), grad_scale, (const float*)nullptr);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
@@ -271,7 +264,7 @@ extern "C" int qea_adam_step(float* p, const float* g, float* m, float* v, int64
 extern "C" int qea_jitter(const float* img, const float* sigma, float* out, float* noise_out, int32_t K, int32_t R, int32_t HW, float coef,
                           uint64_t seed, uint64_t offset, void* stream) {
   QEA_REQUIRE(img && sigma && out && K > 0 && R > 0 && HW > 0 && HW % 4 == 0, "qea_jitter: bad arguments (HW must be a multiple of 4)");
-  hipLaunchKernelGGL(jitter_kernel, dim3(grid_for((long long)R * K * (HW / 4))), dim3(256), 0, (hipStream_t)stream, img, sigma, out, noise_out,
+  hipLaunchKernelGGL(jitter_kernel, dim3(qea_grid_for((long long)R * K * (HW / 4))), dim3(256), 0, (hipStream_t)stream, img, sigma, out, noise_out,
                      K, R, HW, coef, (unsigned long long)seed, (unsigned long long)offset);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
@@ -279,7 +272,7 @@ extern "C" int qea_jitter(const float* img, const float* sigma, float* out, floa
 
 extern "C" int qea_jitter_apply(const float* img, const float* noise, float* out, int32_t K, int32_t R, int32_t HW, float coef, void* stream) {
   QEA_REQUIRE(img && noise && out && K > 0 && R > 0 && HW > 0, "qea_jitter_apply: bad arguments");
-  hipLaunchKernelGGL(jitter_apply_kernel, dim3(grid_for((long long)R * K * HW)), dim3(256), 0, (hipStream_t)stream, img, noise, out, K, R, HW,
+  hipLaunchKernelGGL(jitter_apply_kernel, dim3(qea_grid_for((long long)R * K * HW)), dim3(256), 0, (hipStream_t)stream, img, noise, out, K, R, HW,
                      coef);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
@@ -304,7 +297,7 @@ extern "C" int qea_topk_desc_stable(const float* keys, int32_t n, int32_t k, int
 extern "C" int qea_crop_pad_gather(const float* img, int32_t H, int32_t W, const int32_t* boxes, int32_t N, int32_t OH, int32_t OW, float* out,
                                    void* stream) {
   QEA_REQUIRE(img && boxes && out && H > 0 && W > 0 && N > 0 && OH > 0 && OW > 0, "qea_crop_pad_gather: bad arguments");
-  hipLaunchKernelGGL(crop_pad_gather_kernel, dim3(grid_for((long long)N * OH * OW)), dim3(256), 0, (hipStream_t)stream, img, H, W, boxes, N,
+  hipLaunchKernelGGL(crop_pad_gather_kernel, dim3(qea_grid_for((long long)N * OH * OW)), dim3(256), 0, (hipStream_t)stream, img, H, W, boxes, N,
                      OH, OW, out);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
@@ -313,7 +306,7 @@ extern "C" int qea_crop_pad_gather(const float* img, int32_t H, int32_t W, const
 extern "C" int qea_crop_pad_scatter(const float* dout, const int32_t* boxes, int32_t N, int32_t OH, int32_t OW, float* dimg, int32_t H,
                                     int32_t W, void* stream) {
   QEA_REQUIRE(dout && boxes && dimg && H > 0 && W > 0 && N > 0 && OH > 0 && OW > 0, "qea_crop_pad_scatter: bad arguments");
-  hipLaunchKernelGGL(crop_pad_scatter_kernel, dim3(grid_for((long long)N * OH * OW)), dim3(256), 0, (hipStream_t)stream, dout, boxes, N, OH, OW,
+  hipLaunchKernelGGL(crop_pad_scatter_kernel, dim3(qea_grid_for((long long)N * OH * OW)), dim3(256), 0, (hipStream_t)stream, dout, boxes, N, OH, OW,
                      dimg, H, W);
   QEA_CHECK_LAUNCH();
   return QEA_OK;

@@ -37,6 +37,64 @@ ColGeom col_geom(long long M, int C) {
 // backward recomputes from y agree bit for bit.
 __device__ __forceinline__ float bn_affine(float v, float sc, float sh) { return __fmaf_rn(v, sc, sh); }
 
+// The BatchNorm(+ReLU) backward, likewise in ONE place each for every kernel that evaluates it (colreduce_kernel<1>, bn_bwd_apply_kernel,
+// both forms of bn_bwd_pool_kernel):
+// dz = relu'(.) * d, the ReLU's output taken from the stored activation (has_a: av) or recomputed from y (remask); neither: no ReLU
+__device__ __forceinline__ float bn_masked_dz(float d, bool has_a, float av, bool remask = false, float yv = 0.f, float sc = 0.f, float sh = 0.f) {
+  if (has_a) return av > 0.f ? d : 0.f;
+  if (remask) return bn_affine(yv, sc, sh) > 0.f ? d : 0.f;
+  return d;
+}
+// s0 += dz, s1 += dz * xhat
+__device__ __forceinline__ void bn_bwd_acc(double& s0, double& s1, float dz, float yv, double mu, double is) {
+  s0 += (double)dz;
+  s1 += (double)dz * (((double)yv - mu) * is);
+}
+// dy = k0 * dz + k1 * y + k2, fp64 constants, one rounding (see bn_bwd_finalize_kernel / bn_bwd_apply_kernel)
+__device__ __forceinline__ float bn_dy(double c0, double c1, double c2, float dz, float yv) {
+  return (float)(c0 * (double)dz + (c1 * (double)yv + c2));
+}
+// mean and invstd of the 4 channels from c4 on: the unrounded stat64 when the caller kept it
+__device__ __forceinline__ void bn_load_mu_is(const double* __restrict__ stat64, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                              int C, int c4, double (&mu)[4], double (&is)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    mu[k] = stat64 ? stat64[c4 + k] : (double)mean[c4 + k];
+    is[k] = stat64 ? stat64[C + c4 + k] : (double)invstd[c4 + k];
+  }
+}
+// End of a reduction block: thread (rt, ct) leaves its 4 x 2 sums in sred [rt_n][C][2], then the rows are added in the order 0 .. rt_n-1
+// into row blockIdx.x of ws.
+__device__ __forceinline__ void block_partials_store(double* sred, const double (&s0)[4], const double (&s1)[4], int rt, int rt_n, int ct, int C,
+                                                     double* __restrict__ ws) {
+  if (rt < rt_n) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      sred[((size_t)rt * C + ct * 4 + k) * 2 + 0] = s0[k];
+      sred[((size_t)rt * C + ct * 4 + k) * 2 + 1] = s1[k];
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    double t0 = 0, t1 = 0;
+    for (int r = 0; r < rt_n; ++r) {
+      t0 += sred[((size_t)r * C + c) * 2 + 0];
+      t1 += sred[((size_t)r * C + c) * 2 + 1];
+    }
+    ws[((size_t)blockIdx.x * C + c) * 2 + 0] = t0;
+    ws[((size_t)blockIdx.x * C + c) * 2 + 1] = t1;
+  }
+}
+
+// The max-pool rule of all four pool kernels (window == stride): v replaces the running maximum m when it is larger or NaN, so the FIRST
+// maximum in (kh, kw) scan order wins and a NaN wins over everything (ATen's rule) ...
+__device__ __forceinline__ bool pool_take(float v, float m) { return v > m || v != v; }
+// ... and their window decode: pooled pixel op = (b, oh, ow) -> the input pixel of its window's first element; element (i2, j2) lies
+// i2 * W + j2 pixels further.  (b * H + oh * kh = (op / OW) * kh, because H = OH * kh.)
+__device__ __forceinline__ long long pool_window_origin(long long op, int OW, int W, int kh, int kw) {
+  return (op / OW) * kh * W + (op % OW) * kw;
+}
+
 // MODE 0: s0 = sum x, s1 = sum x^2                                 (BN statistics)
 // MODE 1: dz = da * relu'(.); s0 = sum dz, s1 = sum dz * (y - mean) * invstd   (BN backward)
 //         relu' from a > 0 when a is given, else from bn_affine(y, msc, msh) > 0 when msc is given (no read of a)
@@ -57,14 +115,12 @@ __global__ __launch_bounds__(RED_THREADS) void colreduce_kernel(const float* __r
     long long r1 = r0 + rows_per_block;
     if (r1 > M) r1 = M;
     double mu[4] = {0, 0, 0, 0}, is[4] = {0, 0, 0, 0};
-    f32x4 sc = {0.f, 0.f, 0.f, 0.f}, sh = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 sc = zero, sh = zero;
+    const bool remask = !a && msc;
     if (MODE == 1) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        mu[k] = stat64 ? stat64[ct * 4 + k] : (double)mean[ct * 4 + k];
-        is[k] = stat64 ? stat64[C + ct * 4 + k] : (double)invstd[ct * 4 + k];
-      }
-      if (!a && msc) {
+      bn_load_mu_is(stat64, mean, invstd, C, ct * 4, mu, is);
+      if (remask) {
         sc = *reinterpret_cast<const f32x4*>(msc + ct * 4);
         sh = *reinterpret_cast<const f32x4*>(msh + ct * 4);
       }
@@ -79,48 +135,22 @@ __global__ __launch_bounds__(RED_THREADS) void colreduce_kernel(const float* __r
           s1[k] += (double)v[k] * (double)v[k];
         }
       } else if (MODE == 1) {
-        f32x4 dz = v;
         const f32x4 yv = *reinterpret_cast<const f32x4*>(y + r * ldy + ct * 4);
-        if (a) {
-          const f32x4 av = *reinterpret_cast<const f32x4*>(a + r * lda + ct * 4);
+        const f32x4 av = a ? *reinterpret_cast<const f32x4*>(a + r * lda + ct * 4) : zero;
 #pragma unroll
-          for (int k = 0; k < 4; ++k) dz[k] = av[k] > 0.f ? dz[k] : 0.f;
-        } else if (msc) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) dz[k] = bn_affine(yv[k], sc[k], sh[k]) > 0.f ? dz[k] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          s0[k] += (double)dz[k];
-          s1[k] += (double)dz[k] * (((double)yv[k] - mu[k]) * is[k]);
-        }
+        for (int k = 0; k < 4; ++k)
+          bn_bwd_acc(s0[k], s1[k], bn_masked_dz(v[k], a, av[k], remask, yv[k], sc[k], sh[k]), yv[k], mu[k], is[k]);
       } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) s0[k] += (double)v[k];
       }
     }
   }
-  if (rt < rt_n) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      sred[((size_t)rt * C + ct * 4 + k) * 2 + 0] = s0[k];
-      sred[((size_t)rt * C + ct * 4 + k) * 2 + 1] = s1[k];
-    }
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    double t0 = 0, t1 = 0;
-    for (int r = 0; r < rt_n; ++r) {
-      t0 += sred[((size_t)r * C + c) * 2 + 0];
-      t1 += sred[((size_t)r * C + c) * 2 + 1];
-    }
-    ws[((size_t)blockIdx.x * C + c) * 2 + 0] = t0;
-    ws[((size_t)blockIdx.x * C + c) * 2 + 1] = t1;
-  }
+  block_partials_store(sred, s0, s1, rt, rt_n, ct, C, ws);
 }
 
-// Finalize kernels: ONE WAVE PER CHANNEL.  Lane l sums partial blocks l, l+64, ... then a wave
-// reduction; a single thread walking up to 1024 dependent L2 loads per channel took ~200 us.
+// Finalize kernels: ONE WAVE PER CHANNEL over the [nblk][C][2] partial rows, in the lane order of qea_wave_partial_sum but both sums in
+// one loop (two calls of the helper cost the finalize kernels 4 VGPRs / 4 SGPRs).
 __device__ __forceinline__ void partial_sums(const double* __restrict__ ws, int nblk, int C, int c, double& s, double& q) {
   const int lane = threadIdx.x & 63;
   double a = 0, b = 0;
@@ -267,10 +297,7 @@ __global__ __launch_bounds__(RED_THREADS) void bn_bwd_apply_kernel(const float* 
     f32x4 o;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      float d = dz[k];
-      if (a) d = av[k] > 0.f ? d : 0.f;
-      else if (remask) d = bn_affine(yv[k], sc[k], sh[k]) > 0.f ? d : 0.f;
-      o[k] = (float)(c0[k] * (double)d + (c1[k] * (double)yv[k] + c2[k]));
+      o[k] = bn_dy(c0[k], c1[k], c2[k], bn_masked_dz(dz[k], a, av[k], remask, yv[k], sc[k], sh[k]), yv[k]);
       am = qea_amax_acc(am, o[k]);
     }
     *reinterpret_cast<f32x4*>(dy + r * lddy + ct * 4) = o;
@@ -331,25 +358,21 @@ __global__ __launch_bounds__(RED_THREADS) void bn_bwd_pool_kernel(const float* _
   double mu[4] = {0, 0, 0, 0}, is[4] = {0, 0, 0, 0}, c0[4] = {0, 0, 0, 0}, c1[4] = {0, 0, 0, 0}, c2[4] = {0, 0, 0, 0};
   const f32x4 sc = *reinterpret_cast<const f32x4*>(msc + ct * 4);
   const f32x4 sh = *reinterpret_cast<const f32x4*>(msh + ct * 4);
+  if constexpr (APPLY) {
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (APPLY) {
+    for (int k = 0; k < 4; ++k) {
       c0[k] = k0[ct * 4 + k];
       c1[k] = k1[ct * 4 + k];
       c2[k] = k2[ct * 4 + k];
-    } else {
-      mu[k] = stat64 ? stat64[ct * 4 + k] : (double)mean[ct * 4 + k];
-      is[k] = stat64 ? stat64[C + ct * 4 + k] : (double)invstd[ct * 4 + k];
     }
+  } else {
+    bn_load_mu_is(stat64, mean, invstd, C, ct * 4, mu, is);
   }
   const long long w0 = (long long)blockIdx.x * win_per_block;
   long long w1 = w0 + win_per_block;
   if (w1 > NWIN) w1 = NWIN;
   for (long long wi = idle ? w1 : w0 + rt; wi < w1; wi += rt_n) {
-    const int ow = (int)(wi % OW);
-    const int oh = (int)((wi / OW) % OH);
-    const int b = (int)(wi / ((long long)OW * OH));
-    const long long r00 = ((long long)b * H + 2 * oh) * W + (long long)ow * KW;
+    const long long r00 = pool_window_origin(wi, OW, W, 2, KW);
     long long rows[NP];
 #pragma unroll
     for (int j = 0; j < NP; ++j) rows[j] = r00 + (j / KW) * (long long)W + (j % KW);
@@ -370,7 +393,7 @@ __global__ __launch_bounds__(RED_THREADS) void bn_bwd_pool_kernel(const float* _
       for (int k = 0; k < 4; ++k) {
         const float v = fmaxf(bn_affine(yv[j][k], sc[k], sh[k]), 0.f);
         av[j][k] = v;
-        if (v > m[k] || v != v) {
+        if (pool_take(v, m[k])) {
           m[k] = v;
           arg[k] = j;
         }
@@ -380,14 +403,13 @@ __global__ __launch_bounds__(RED_THREADS) void bn_bwd_pool_kernel(const float* _
       f32x4 o;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        float d = (arg[k] == j ? g[k] : 0.f) + dv[j][k];      // (qea_maxpool_bwd's accumulate: routed gradient + what the skip path left)
-        d = av[j][k] > 0.f ? d : 0.f;
+        // (qea_maxpool_bwd's accumulate: routed gradient + what the skip path left; the mask from the activation rebuilt above)
+        const float d = bn_masked_dz((arg[k] == j ? g[k] : 0.f) + dv[j][k], true, av[j][k]);
         if (APPLY) {
-          o[k] = (float)(c0[k] * (double)d + (c1[k] * (double)yv[j][k] + c2[k]));
+          o[k] = bn_dy(c0[k], c1[k], c2[k], d, yv[j][k]);
           am = qea_amax_acc(am, o[k]);
         } else {
-          s0[k] += (double)d;
-          s1[k] += (double)d * (((double)yv[j][k] - mu[k]) * is[k]);
+          bn_bwd_acc(s0[k], s1[k], d, yv[j][k], mu[k], is[k]);
         }
       }
       if (APPLY) *reinterpret_cast<f32x4*>(dy + rows[j] * lddy + ct * 4) = o;
@@ -396,23 +418,7 @@ __global__ __launch_bounds__(RED_THREADS) void bn_bwd_pool_kernel(const float* _
   if constexpr (APPLY) {
     qea_amax_commit_block(am, amax);
   } else {
-    if (!idle) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        sred[((size_t)rt * C + ct * 4 + k) * 2 + 0] = s0[k];
-        sred[((size_t)rt * C + ct * 4 + k) * 2 + 1] = s1[k];
-      }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-      double t0 = 0, t1 = 0;
-      for (int r = 0; r < rt_n; ++r) {
-        t0 += sred[((size_t)r * C + c) * 2 + 0];
-        t1 += sred[((size_t)r * C + c) * 2 + 1];
-      }
-      ws[((size_t)blockIdx.x * C + c) * 2 + 0] = t0;
-      ws[((size_t)blockIdx.x * C + c) * 2 + 1] = t1;
-    }
+    block_partials_store(sred, s0, s1, rt, rt_n, ct, C, ws);
   }
 }
 
@@ -425,16 +431,13 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ x, int ldx, float* 
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int ct = (int)(i % cols);
     const long long op = i / cols;
-    const int ow = (int)(op % OW);
-    const int oh = (int)((op / OW) % OH);
-    const int b = (int)(op / ((long long)OW * OH));
+    const long long ip0 = pool_window_origin(op, OW, W, kh, kw);
     f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     for (int i2 = 0; i2 < kh; ++i2)
       for (int j2 = 0; j2 < kw; ++j2) {
-        const long long ip = ((long long)b * H + oh * kh + i2) * W + ow * kw + j2;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + ip * ldx + ct * 4);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + (ip0 + i2 * W + j2) * ldx + ct * 4);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) m[k] = (v[k] > m[k] || v[k] != v[k]) ? v[k] : m[k];
+        for (int k = 0; k < 4; ++k) m[k] = pool_take(v[k], m[k]) ? v[k] : m[k];
       }
     *reinterpret_cast<f32x4*>(y + op * ldy + ct * 4) = m;
 #pragma unroll
@@ -456,14 +459,13 @@ __global__ void bn_apply_pool_kernel(const float* __restrict__ y, int ldy, float
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int ct = (int)(i % cols);
     const long long op = i / cols;
-    const int ow = (int)(op % OW);
-    const long long orow = op / OW;                         // b * OH + oh
+    const long long ip0 = pool_window_origin(op, OW, W, kh, kw);
     const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + ct * 4);
     const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + ct * 4);
     f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     for (int i2 = 0; i2 < kh; ++i2)
       for (int j2 = 0; j2 < kw; ++j2) {
-        const long long ip = (orow * kh + i2) * W + ow * kw + j2;
+        const long long ip = ip0 + i2 * W + j2;
         const f32x4 v = *reinterpret_cast<const f32x4*>(y + ip * ldy + ct * 4);
         f32x4 o;
 #pragma unroll
@@ -471,7 +473,7 @@ __global__ void bn_apply_pool_kernel(const float* __restrict__ y, int ldy, float
           o[k] = bn_affine(v[k], sc[k], sh[k]);
           if (relu) o[k] = fmaxf(o[k], 0.f);
           am = qea_amax_acc(am, o[k]);
-          m[k] = (o[k] > m[k] || o[k] != o[k]) ? o[k] : m[k];
+          m[k] = pool_take(o[k], m[k]) ? o[k] : m[k];
         }
         *reinterpret_cast<f32x4*>(a + ip * lda + ct * 4) = o;
       }
@@ -492,18 +494,15 @@ __global__ void maxpool_bwd_kernel(const float* __restrict__ x, int ldx, const f
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int ct = (int)(i % cols);
     const long long op = i / cols;
-    const int ow = (int)(op % OW);
-    const int oh = (int)((op / OW) % OH);
-    const int b = (int)(op / ((long long)OW * OH));
+    const long long ip0 = pool_window_origin(op, OW, W, kh, kw);
     f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     int arg[4] = {0, 0, 0, 0};
     for (int i2 = 0; i2 < kh; ++i2)
       for (int j2 = 0; j2 < kw; ++j2) {
-        const long long ip = ((long long)b * H + oh * kh + i2) * W + ow * kw + j2;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + ip * ldx + ct * 4);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + (ip0 + i2 * W + j2) * ldx + ct * 4);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-          if (v[k] > m[k] || v[k] != v[k]) {
+          if (pool_take(v[k], m[k])) {
             m[k] = v[k];
             arg[k] = i2 * kw + j2;
           }
@@ -511,7 +510,6 @@ __global__ void maxpool_bwd_kernel(const float* __restrict__ x, int ldx, const f
     const f32x4 g = *reinterpret_cast<const f32x4*>(dy + op * lddy + ct * 4);
     for (int i2 = 0; i2 < kh; ++i2)
       for (int j2 = 0; j2 < kw; ++j2) {
-        const long long ip = ((long long)b * H + oh * kh + i2) * W + ow * kw + j2;
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -519,7 +517,7 @@ __global__ void maxpool_bwd_kernel(const float* __restrict__ x, int ldx, const f
           if (relu_mask && !(m[k] > 0.f)) t = 0.f;
           o[k] = t;
         }
-        f32x4* dst = reinterpret_cast<f32x4*>(dx + ip * lddx + ct * 4);
+        f32x4* dst = reinterpret_cast<f32x4*>(dx + (ip0 + i2 * W + j2) * lddx + ct * 4);
         if (accumulate) o += *dst;
         *dst = o;
 #pragma unroll
@@ -560,25 +558,38 @@ __global__ void flip_transpose_kernel(const float* __restrict__ w, float* __rest
   }
 }
 
-int grid_for(long long n) {
-  long long g = (n + 255) / 256;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
+size_t ws_need(int rows, int consts, int C) { return ((size_t)rows * 2 + consts) * C * sizeof(double); }
+
+// The one argument check of the column kernels: C a multiple of 4 with at most one float4 column per thread, the strides (OR-ed
+// together by the caller) multiples of 4, and a workspace for the partial rows + `consts` per-channel fp64 vectors.  g != nullptr:
+// receives col_geom(M, C), whose grid is the number of partial rows; nullptr: the caller brings its own partials, none here.
+int check_cols(const char* who, long long M, int C, int strides, const void* ws, size_t ws_bytes, int consts, ColGeom* g) {
+  QEA_REQUIRE(M > 0 && C > 0 && C % 4 == 0 && C / 4 <= RED_THREADS, "%s: need C %% 4 == 0 and C <= %d (C=%d)", who, 4 * RED_THREADS, C);
+  QEA_REQUIRE(strides % 4 == 0, "%s: strides must be multiples of 4", who);
+  const int rows = g ? (*g = col_geom(M, C)).grid : 0;
+  QEA_REQUIRE(ws && ws_bytes >= ws_need(rows, consts, C), "%s: workspace too small (%zu bytes)", who, ws_need(rows, consts, C));
+  return QEA_OK;
 }
 
-int check_nc(const char* who, long long M, int C, size_t ws_bytes, void* ws, const ColGeom& g) {
-  QEA_REQUIRE(M > 0 && C > 0 && C % 4 == 0 && C / 4 <= RED_THREADS, "%s: need C %% 4 == 0 and C <= %d (C=%d)", who, 4 * RED_THREADS, C);
-  QEA_REQUIRE(ws && ws_bytes >= (size_t)g.grid * C * 2 * sizeof(double), "%s: workspace too small", who);
-  return QEA_OK;
+// Elementwise pass over `items` rows (or windows): the reduction's column-per-thread geometry with rt row-threads, about per_thread
+// items each, but up to 4096 workgroups (no partials to merge afterwards).
+struct ApplyGeom {
+  unsigned grid;
+  int per_block;
+};
+ApplyGeom apply_geom(long long items, int rt, int per_thread) {
+  long long grid = (items + (long long)rt * per_thread - 1) / ((long long)rt * per_thread);
+  if (grid > 4096) grid = 4096;
+  if (grid < 1) grid = 1;
+  const int per = (int)((items + grid - 1) / grid);
+  return {(unsigned)((items + per - 1) / per), per};
 }
 
 }  // namespace
 
 extern "C" size_t qea_colreduce_workspace_bytes(int64_t M, int32_t C) {
   if (M <= 0 || C <= 0 || C % 4) return 0;
-  const ColGeom g = col_geom(M, C);
-  return (size_t)g.grid * C * 2 * sizeof(double) + 3 * (size_t)C * sizeof(double);
+  return ws_need(col_geom(M, C).grid, 3, C);
 }
 
 extern "C" int qea_bn_train_stats(const float* y, int32_t ldy, int64_t M, int32_t C, const float* gamma, const float* beta, float eps,
@@ -586,10 +597,9 @@ extern "C" int qea_bn_train_stats(const float* y, int32_t ldy, int64_t M, int32_
                                   float* scale_out, float* shift_out, double* stat64, void* workspace, size_t workspace_bytes,
                                   void* stream) {
   QEA_REQUIRE(y && mean_out && invstd_out && scale_out && shift_out, "qea_bn_train_stats: null pointer");
-  const ColGeom g = col_geom(M, C);
-  int rc = check_nc("qea_bn_train_stats", M, C, workspace_bytes, workspace, g);
-  if (rc) return rc;
-  QEA_REQUIRE(ldy % 4 == 0 && ((uintptr_t)y & 15) == 0, "qea_bn_train_stats: alignment");
+  QEA_REQUIRE(((uintptr_t)y & 15) == 0, "qea_bn_train_stats: alignment");
+  ColGeom g;
+  if (int rc = check_cols("qea_bn_train_stats", M, C, ldy, workspace, workspace_bytes, 0, &g)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)g.rt * C * 2 * sizeof(double);
   hipLaunchKernelGGL(colreduce_kernel<0>, dim3(g.grid), dim3(RED_THREADS), lds, s, y, ldy, nullptr, 0, nullptr, 0, nullptr, nullptr,
@@ -608,7 +618,6 @@ extern "C" int qea_bn_train_stats(const float* y, int32_t ldy, int64_t M, int32_
 // instead of walking thousands of strided loads per lane (250 us -> a few us per BatchNorm layer).
 __global__ __launch_bounds__(256) void partials_reduce_kernel(const double* __restrict__ ws, int nblk, int C, int per, double* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) double sp[];   // [stripes][C][2]
-  const int stripes = 256 / C > 0 ? 256 / C : 1;               // C <= 256 per pass
   const int b0 = blockIdx.x * per;
   const int b1 = min(nblk, b0 + per);
   for (int cbase = 0; cbase < C; cbase += 256) {
@@ -637,8 +646,55 @@ __global__ __launch_bounds__(256) void partials_reduce_kernel(const double* __re
     }
     __syncthreads();
   }
-  (void)stripes;
 }
+
+namespace {
+
+// Many partial rows (above 2 * QEA_BN_PARTIAL_SCRATCH_ROWS) are folded in two order-fixed stages: partials_reduce_kernel sums
+// QEA_BN_PARTIAL_SCRATCH_ROWS ranges into the scratch rows the caller left behind the partials, and the finalize kernel reads those.
+void fold_partials(const double* partials, int blocks, int C, hipStream_t s, const double** src, int* nblk) {
+  *src = partials;
+  *nblk = blocks;
+  if (blocks <= QEA_BN_PARTIAL_SCRATCH_ROWS * 2) return;
+  const int per = qea_cdiv(blocks, QEA_BN_PARTIAL_SCRATCH_ROWS);
+  *nblk = qea_cdiv(blocks, per);
+  double* scratch = const_cast<double*>(partials) + (size_t)blocks * C * 2;
+  hipLaunchKernelGGL(partials_reduce_kernel, dim3(*nblk), dim3(256), (size_t)256 * 2 * sizeof(double), s, partials, blocks, C, per, scratch);
+  *src = scratch;
+}
+
+// ------------------------------------------------------------------ the BatchNorm backward after its reduction
+// The per-channel arguments every entry point hands through unchanged.
+struct BnChannels {
+  const float *gamma, *mean, *invstd;
+  const double* stat64;
+  int training;
+  float *dgamma, *dbeta;
+  int accumulate;
+};
+
+// What qea_bn_bwd, qea_bn_bwd_pool and qea_bn_bwd_from_partials share once `nrows` partial rows lie at `rows`: the finalize kernel (dgamma,
+// dbeta, and k0 | k1 | k2 as three [C] fp64 vectors from `k` on), then the entry point's elementwise kernel, launched by apply(k0, k1, k2).
+template <class Apply>
+int bn_bwd_tail(const double* rows, int nrows, double* k, long long M, int C, const BnChannels& ch, hipStream_t s, Apply apply) {
+  double *k0 = k, *k1 = k0 + C, *k2 = k1 + C;
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(qea_cdiv(C, 4)), dim3(256), 0, s, rows, nrows, C, M, ch.gamma, ch.mean, ch.invstd, ch.stat64,
+                     ch.training, ch.dgamma, ch.dbeta, ch.accumulate, k0, k1, k2);
+  apply(k0, k1, k2);
+  QEA_CHECK_LAUNCH();
+  return QEA_OK;
+}
+
+// the elementwise kernel of qea_bn_bwd and qea_bn_bwd_from_partials (a == nullptr)
+void bn_bwd_apply_launch(const float* da, int ldda, const float* a, int lda, const float* y, int ldy, float* dy, int lddy, long long M, int C,
+                         const float* relu_scale, const float* relu_shift, const double* k0, const double* k1, const double* k2, int rt,
+                         float* absmax_out, hipStream_t s) {
+  const ApplyGeom ag = apply_geom(M, rt, 8);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ag.grid), dim3(RED_THREADS), 0, s, da, ldda, a, lda, y, ldy, dy, lddy, M, C, relu_scale, relu_shift,
+                     k0, k1, k2, ag.per_block, rt, absmax_out);
+}
+
+}  // namespace
 
 extern "C" int qea_bn_train_stats_from_partials(const double* partials, int32_t blocks, int64_t M, int32_t C, const float* gamma,
                                                 const float* beta, float eps, float momentum, float* running_mean, float* running_var,
@@ -647,16 +703,9 @@ extern "C" int qea_bn_train_stats_from_partials(const double* partials, int32_t 
   QEA_REQUIRE(partials && blocks > 0 && M > 0 && C > 0 && mean_out && invstd_out && scale_out && shift_out,
               "qea_bn_train_stats_from_partials: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  const double* src = partials;
-  int nblk = blocks;
-  if (blocks > QEA_BN_PARTIAL_SCRATCH_ROWS * 2) {
-    // two stages: QEA_BN_PARTIAL_SCRATCH_ROWS ranges -> the scratch rows the caller left behind the partials
-    const int per = qea_cdiv(blocks, QEA_BN_PARTIAL_SCRATCH_ROWS);
-    nblk = qea_cdiv(blocks, per);
-    double* scratch = const_cast<double*>(partials) + (size_t)blocks * C * 2;
-    hipLaunchKernelGGL(partials_reduce_kernel, dim3(nblk), dim3(256), (size_t)256 * 2 * sizeof(double), s, partials, blocks, C, per, scratch);
-    src = scratch;
-  }
+  const double* src;
+  int nblk;
+  fold_partials(partials, blocks, C, s, &src, &nblk);
   hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(qea_cdiv(C, 4)), dim3(256), 0, s, src, nblk, C, (long long)M,
                      gamma, beta, eps, momentum, running_mean, running_var, mean_out, invstd_out, scale_out, shift_out, stat64);
   QEA_CHECK_LAUNCH();
@@ -676,7 +725,7 @@ extern "C" int qea_bn_eval_coeff(int32_t C, const float* gamma, const float* bet
 extern "C" int qea_bn_apply(const float* y, int32_t ldy, float* a, int32_t lda, int64_t M, int32_t C, const float* scale,
                             const float* shift, int32_t relu, float* absmax_out, void* stream) {
   QEA_REQUIRE(y && a && scale && shift && M > 0 && C > 0 && C % 4 == 0 && ldy % 4 == 0 && lda % 4 == 0, "qea_bn_apply: bad arguments");
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(M * (C / 4))), dim3(256), 0, (hipStream_t)stream, y, ldy, a, lda, (long long)M, C,
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(qea_grid_for(M * (C / 4))), dim3(256), 0, (hipStream_t)stream, y, ldy, a, lda, (long long)M, C,
                      scale, shift, relu, absmax_out);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
@@ -687,33 +736,19 @@ extern "C" int qea_bn_bwd(const float* da, int32_t ldda, const float* a, int32_t
                           float* dgamma, float* dbeta, int32_t accumulate_param_grads, float* dy, int32_t lddy, void* workspace,
                           size_t workspace_bytes, float* absmax_out, void* stream) {
   QEA_REQUIRE(da && y && mean && invstd && dy, "qea_bn_bwd: null pointer");
-  const ColGeom g = col_geom(M, C);
-  int rc = check_nc("qea_bn_bwd", M, C, workspace_bytes, workspace, g);
-  if (rc) return rc;
-  QEA_REQUIRE(workspace_bytes >= qea_colreduce_workspace_bytes(M, C), "qea_bn_bwd: workspace too small");
-  QEA_REQUIRE(ldda % 4 == 0 && ldy % 4 == 0 && lddy % 4 == 0 && (!a || lda % 4 == 0), "qea_bn_bwd: strides must be multiples of 4");
   QEA_REQUIRE(!a || !relu_scale, "qea_bn_bwd: give the ReLU mask either as a or as relu_scale/relu_shift, not both");
   QEA_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr), "qea_bn_bwd: relu_scale and relu_shift go together");
+  ColGeom g;
+  if (int rc = check_cols("qea_bn_bwd", M, C, ldda | ldy | lddy | (a ? lda : 0), workspace, workspace_bytes, 3, &g)) return rc;
   hipStream_t s = (hipStream_t)stream;
   double* ws = (double*)workspace;
-  double* k0 = ws + (size_t)g.grid * C * 2;
-  double* k1 = k0 + C;
-  double* k2 = k1 + C;
   const size_t lds = (size_t)g.rt * C * 2 * sizeof(double);
   hipLaunchKernelGGL(colreduce_kernel<1>, dim3(g.grid), dim3(RED_THREADS), lds, s, da, ldda, a, lda, y, ldy, mean, invstd, stat64,
                      relu_scale, relu_shift, (long long)M, C, g.rows_per_block, g.rt, ws);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(qea_cdiv(C, 4)), dim3(256), 0, s, (const double*)ws, g.grid, C, (long long)M, gamma,
-                     mean, invstd, stat64, training, dgamma, dbeta, accumulate_param_grads, k0, k1, k2);
-  // elementwise pass: same column-per-thread geometry, but up to 4096 workgroups (no partials to merge afterwards)
-  long long agrid = (M + (long long)g.rt * 8 - 1) / ((long long)g.rt * 8);
-  if (agrid > 4096) agrid = 4096;
-  if (agrid < 1) agrid = 1;
-  const int arows = (int)((M + agrid - 1) / agrid);
-  agrid = (M + arows - 1) / arows;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)agrid), dim3(RED_THREADS), 0, s, da, ldda, a, lda, y, ldy, dy, lddy, (long long)M,
-                     C, relu_scale, relu_shift, (const double*)k0, (const double*)k1, (const double*)k2, arows, g.rt, absmax_out);
-  QEA_CHECK_LAUNCH();
-  return QEA_OK;
+  return bn_bwd_tail(ws, g.grid, ws + (size_t)g.grid * C * 2, M, C, {gamma, mean, invstd, stat64, training, dgamma, dbeta, accumulate_param_grads}, s,
+                     [&](const double* k0, const double* k1, const double* k2) {
+                       bn_bwd_apply_launch(da, ldda, a, lda, y, ldy, dy, lddy, M, C, relu_scale, relu_shift, k0, k1, k2, g.rt, absmax_out, s);
+                     });
 }
 
 extern "C" int qea_bn_bwd_pool(const float* da, int32_t ldda, const float* dpool, int32_t lddp, int32_t kw, const float* relu_scale,
@@ -725,41 +760,30 @@ extern "C" int qea_bn_bwd_pool(const float* da, int32_t ldda, const float* dpool
   QEA_REQUIRE(B > 0 && H > 0 && W > 0 && H % 2 == 0 && (kw == 1 || kw == 2) && W % kw == 0, "qea_bn_bwd_pool: 2 x kw windows, kw in {1, 2}, H and W multiples");
   const long long M = (long long)B * H * W;
   const long long NWIN = M / (2 * kw);
+  ColGeom gm;                                               // qea_bn_bwd's geometry for M rows: the workspace is sized for it
+  if (int rc = check_cols("qea_bn_bwd_pool", M, C, ldy | lddy | lddp | (da ? ldda : 0), workspace, workspace_bytes, 3, &gm)) return rc;
   // (a window is 2 * kw rows of work: the reduction's blocks are sized as for that many rows, so that a small tensor — the reference's own
   // batch sizes — still spreads over the chip instead of walking its windows in 16 workgroups)
-  ColGeom g = col_geom(M, C);
+  ColGeom g = gm;
   g.rows_per_block = (g.rows_per_block + 2 * kw - 1) / (2 * kw);
   if (g.rows_per_block < 1) g.rows_per_block = 1;
   g.grid = (int)((NWIN + g.rows_per_block - 1) / g.rows_per_block);
-  int rc = check_nc("qea_bn_bwd_pool", M, C, workspace_bytes, workspace, g);
-  if (rc) return rc;
-  QEA_REQUIRE(workspace_bytes >= qea_colreduce_workspace_bytes(M, C) && g.grid <= col_geom(M, C).grid,
-              "qea_bn_bwd_pool: workspace too small (qea_colreduce_workspace_bytes(B * H * W, C))");
-  QEA_REQUIRE(ldy % 4 == 0 && lddy % 4 == 0 && lddp % 4 == 0 && (!da || ldda % 4 == 0), "qea_bn_bwd_pool: strides must be multiples of 4");
+  QEA_REQUIRE(g.grid <= gm.grid, "qea_bn_bwd_pool: more window blocks than partial rows in the workspace");
   hipStream_t s = (hipStream_t)stream;
   double* ws = (double*)workspace;
-  // (the constants sit behind the partial rows of qea_bn_bwd's geometry for M rows, which has at least as many blocks)
-  const ColGeom gm = col_geom(M, C);
-  double* k0 = ws + (size_t)(gm.grid > g.grid ? gm.grid : g.grid) * C * 2;
-  double* k1 = k0 + C;
-  double* k2 = k1 + C;
   const size_t lds = (size_t)g.rt * C * 2 * sizeof(double);
   auto red = kw == 2 ? bn_bwd_pool_kernel<2, false> : bn_bwd_pool_kernel<1, false>;
   hipLaunchKernelGGL(red, dim3(g.grid), dim3(RED_THREADS), lds, s, da, ldda, dpool, lddp, y, ldy, (float*)nullptr, 0, B, H, W, C, relu_scale, relu_shift,
                      mean, invstd, stat64, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, g.rows_per_block, g.rt, ws,
                      (float*)nullptr);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(qea_cdiv(C, 4)), dim3(256), 0, s, (const double*)ws, g.grid, C, M, gamma, mean, invstd, stat64, training,
-                     dgamma, dbeta, accumulate_param_grads, k0, k1, k2);
-  long long agrid = (NWIN + (long long)g.rt * 4 - 1) / ((long long)g.rt * 4);
-  if (agrid > 4096) agrid = 4096;
-  if (agrid < 1) agrid = 1;
-  const int awin = (int)((NWIN + agrid - 1) / agrid);
-  agrid = (NWIN + awin - 1) / awin;
-  auto app = kw == 2 ? bn_bwd_pool_kernel<2, true> : bn_bwd_pool_kernel<1, true>;
-  hipLaunchKernelGGL(app, dim3((unsigned)agrid), dim3(RED_THREADS), 0, s, da, ldda, dpool, lddp, y, ldy, dy, lddy, B, H, W, C, relu_scale, relu_shift, mean,
-                     invstd, stat64, (const double*)k0, (const double*)k1, (const double*)k2, awin, g.rt, (double*)nullptr, absmax_out);
-  QEA_CHECK_LAUNCH();
-  return QEA_OK;
+  // (the constants sit behind the gm.grid partial rows of qea_bn_bwd's geometry, which has at least as many blocks)
+  return bn_bwd_tail(ws, g.grid, ws + (size_t)gm.grid * C * 2, M, C, {gamma, mean, invstd, stat64, training, dgamma, dbeta, accumulate_param_grads}, s,
+                     [&](const double* k0, const double* k1, const double* k2) {
+                       const ApplyGeom ag = apply_geom(NWIN, g.rt, 4);
+                       auto app = kw == 2 ? bn_bwd_pool_kernel<2, true> : bn_bwd_pool_kernel<1, true>;
+                       hipLaunchKernelGGL(app, dim3(ag.grid), dim3(RED_THREADS), 0, s, da, ldda, dpool, lddp, y, ldy, dy, lddy, B, H, W, C, relu_scale,
+                                          relu_shift, mean, invstd, stat64, k0, k1, k2, ag.per_block, g.rt, (double*)nullptr, absmax_out);
+                     });
 }
 
 extern "C" int qea_bn_bwd_from_partials(const double* partials, int32_t blocks, const float* da, int32_t ldda, const float* relu_scale,
@@ -767,44 +791,25 @@ extern "C" int qea_bn_bwd_from_partials(const double* partials, int32_t blocks, 
                                         const float* mean, const float* invstd, const double* stat64, int32_t training, float* dgamma,
                                         float* dbeta, int32_t accumulate_param_grads, float* dy, int32_t lddy, void* workspace,
                                         size_t workspace_bytes, float* absmax_out, void* stream) {
-  QEA_REQUIRE(partials && blocks > 0 && da && y && mean && invstd && dy && stat64 && relu_scale && relu_shift && M > 0 && C > 0 && C % 4 == 0,
-              "qea_bn_bwd_from_partials: null pointer / bad size (stat64 and relu_scale / relu_shift are required)");
-  QEA_REQUIRE(ldda % 4 == 0 && ldy % 4 == 0 && lddy % 4 == 0, "qea_bn_bwd_from_partials: strides must be multiples of 4");
-  QEA_REQUIRE(workspace && workspace_bytes >= (size_t)3 * C * sizeof(double), "qea_bn_bwd_from_partials: workspace too small (3 * C doubles)");
-  const ColGeom g = col_geom(M, C);
+  QEA_REQUIRE(partials && blocks > 0 && da && y && mean && invstd && dy && stat64 && relu_scale && relu_shift,
+              "qea_bn_bwd_from_partials: null pointer / no blocks (stat64 and relu_scale / relu_shift are required)");
+  if (int rc = check_cols("qea_bn_bwd_from_partials", M, C, ldda | ldy | lddy, workspace, workspace_bytes, 3, nullptr)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  double* k0 = (double*)workspace;
-  double* k1 = k0 + C;
-  double* k2 = k1 + C;
-  const double* src = partials;
-  int nblk = blocks;
-  if (blocks > QEA_BN_PARTIAL_SCRATCH_ROWS * 2) {          // two stages, as qea_bn_train_stats_from_partials
-    const int per = qea_cdiv(blocks, QEA_BN_PARTIAL_SCRATCH_ROWS);
-    nblk = qea_cdiv(blocks, per);
-    double* scratch = const_cast<double*>(partials) + (size_t)blocks * C * 2;
-    hipLaunchKernelGGL(partials_reduce_kernel, dim3(nblk), dim3(256), (size_t)256 * 2 * sizeof(double), s, partials, blocks, C, per, scratch);
-    src = scratch;
-  }
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(qea_cdiv(C, 4)), dim3(256), 0, s, src, nblk, C, (long long)M, gamma, mean, invstd, stat64,
-                     training, dgamma, dbeta, accumulate_param_grads, k0, k1, k2);
-  long long agrid = (M + (long long)g.rt * 8 - 1) / ((long long)g.rt * 8);
-  if (agrid > 4096) agrid = 4096;
-  if (agrid < 1) agrid = 1;
-  const int arows = (int)((M + agrid - 1) / agrid);
-  agrid = (M + arows - 1) / arows;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)agrid), dim3(RED_THREADS), 0, s, da, ldda, (const float*)nullptr, 0, y, ldy, dy, lddy,
-                     (long long)M, C, relu_scale, relu_shift, (const double*)k0, (const double*)k1, (const double*)k2, arows, g.rt, absmax_out);
-  QEA_CHECK_LAUNCH();
-  return QEA_OK;
+  const double* src;
+  int nblk;
+  fold_partials(partials, blocks, C, s, &src, &nblk);
+  return bn_bwd_tail(src, nblk, (double*)workspace, M, C, {gamma, mean, invstd, stat64, training, dgamma, dbeta, accumulate_param_grads}, s,
+                     [&](const double* k0, const double* k1, const double* k2) {
+                       bn_bwd_apply_launch(da, ldda, nullptr, 0, y, ldy, dy, lddy, M, C, relu_scale, relu_shift, k0, k1, k2, col_geom(M, C).rt,
+                                           absmax_out, s);
+                     });
 }
 
 extern "C" int qea_colsum(const float* x, int32_t ldx, int64_t M, int32_t C, float* out, int32_t accumulate, void* workspace,
                           size_t workspace_bytes, void* stream) {
   QEA_REQUIRE(x && out, "qea_colsum: null pointer");
-  const ColGeom g = col_geom(M, C);
-  int rc = check_nc("qea_colsum", M, C, workspace_bytes, workspace, g);
-  if (rc) return rc;
-  QEA_REQUIRE(ldx % 4 == 0, "qea_colsum: ldx must be a multiple of 4");
+  ColGeom g;
+  if (int rc = check_cols("qea_colsum", M, C, ldx, workspace, workspace_bytes, 0, &g)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)g.rt * C * 2 * sizeof(double);
   hipLaunchKernelGGL(colreduce_kernel<2>, dim3(g.grid), dim3(RED_THREADS), lds, s, x, ldx, nullptr, 0, nullptr, 0, nullptr, nullptr,
@@ -819,7 +824,7 @@ extern "C" int qea_maxpool_fwd(const float* x, int32_t ldx, float* y, int32_t ld
   QEA_REQUIRE(x && y && B > 0 && C > 0 && C % 4 == 0 && kh > 0 && kw > 0 && H % kh == 0 && W % kw == 0 && ldx % 4 == 0 && ldy % 4 == 0,
               "qea_maxpool_fwd: bad arguments (H,W must be multiples of the window; C, ld multiples of 4)");
   const long long n = (long long)B * (H / kh) * (W / kw) * (C / 4);
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, B, H, W, C, kh, kw, absmax_out);
+  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(qea_grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, B, H, W, C, kh, kw, absmax_out);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -831,7 +836,7 @@ extern "C" int qea_bn_apply_pool(const float* y, int32_t ldy, float* a, int32_t 
                   ldy % 4 == 0 && lda % 4 == 0 && ldp % 4 == 0,
               "qea_bn_apply_pool: bad arguments (H,W must be multiples of the window; C, ld multiples of 4)");
   const long long n = (long long)B * (H / kh) * (W / kw) * (C / 4);
-  hipLaunchKernelGGL(bn_apply_pool_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, y, ldy, a, lda, pooled, ldp, B, H, W, C, scale, shift,
+  hipLaunchKernelGGL(bn_apply_pool_kernel, dim3(qea_grid_for(n)), dim3(256), 0, (hipStream_t)stream, y, ldy, a, lda, pooled, ldp, B, H, W, C, scale, shift,
                      relu, kh, kw, absmax_a, absmax_pooled);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
@@ -844,7 +849,7 @@ extern "C" int qea_maxpool_bwd(const float* x, int32_t ldx, const float* dy, int
                   lddy % 4 == 0 && lddx % 4 == 0,
               "qea_maxpool_bwd: bad arguments");
   const long long n = (long long)B * (H / kh) * (W / kw) * (C / 4);
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, ldx, dy, lddy, dx, lddx, B, H, W, C, kh,
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(qea_grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, ldx, dy, lddy, dx, lddx, B, H, W, C, kh,
                      kw, relu_mask, accumulate, absmax_out);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
@@ -859,7 +864,7 @@ extern "C" int qea_transpose2d(const float* in, float* out, int32_t R, int32_t C
 
 extern "C" int qea_filter_flip_transpose(const float* w, float* wt, int32_t Co, int32_t Ci, int32_t KH, int32_t KW, void* stream) {
   QEA_REQUIRE(w && wt && Co > 0 && Ci > 0 && KH > 0 && KW > 0, "qea_filter_flip_transpose: bad arguments");
-  hipLaunchKernelGGL(flip_transpose_kernel, dim3(grid_for((long long)Co * Ci * KH * KW)), dim3(256), 0, (hipStream_t)stream, w, wt, Co, Ci,
+  hipLaunchKernelGGL(flip_transpose_kernel, dim3(qea_grid_for((long long)Co * Ci * KH * KW)), dim3(256), 0, (hipStream_t)stream, w, wt, Co, Ci,
                      KH, KW);
   QEA_CHECK_LAUNCH();
   return QEA_OK;

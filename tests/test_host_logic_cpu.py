@@ -236,3 +236,22 @@ def test_f16_split_contract_in_numpy():
         assert bool((err <= H.split_element_gate(torch.from_numpy(x), 1.0).numpy()).all()) == inside, se_base
     # below the supported range (m < 2^-112) the scale stops at 2^126: the planes lose bits against m, silently
     assert f16_scale(2.0 ** -120) == np.float32(2.0) ** 126
+
+
+def test_colreduce_workspace_answers_equal_the_pinned_ones(golden_dir):
+    """qea_colreduce_workspace_bytes(M, C) = (blocks * 2 + 3) * C doubles is a function of col_geom(M, C) alone: the block count that fixes
+    the order of every fp64 column reduction.  Pinned (tests/golden/colreduce_workspace.json, written by
+    tools/colreduce_workspace_queries.py) before the three BatchNorm backward entry points were made to share one pipeline."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    try:
+        import colreduce_workspace_queries as Q
+    finally:
+        sys.path.pop(0)
+    pinned = json.load(open(os.path.join(golden_dir, "colreduce_workspace.json")))
+    assert pinned["axes"] == Q.AXES, "the grid changed: regenerate the golden file from the commit that pinned it"
+    got, want = Q.answers(), pinned["answers"]
+    assert len(want) == 8 and all(len(row) == 9 for row in want)
+    bad = [(m, c, want[i][j], got[i][j]) for i, m in enumerate(Q.AXES["M"]) for j, c in enumerate(Q.AXES["C"]) if want[i][j] != got[i][j]]
+    assert not bad, f"{len(bad)} answers moved (M, C, pinned, got): {bad[:5]}"
+    assert all(row[-1] == 0 for row in want) and all(v > 0 for row in want for v in row[:-1])      # C = 6: no multiple of 4

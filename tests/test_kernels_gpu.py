@@ -107,6 +107,142 @@ def test_bn_eval_fwd_bwd():
     assert rel_err(dgamma.cpu(), gr.grad) < 1e-5 and rel_err(dbeta.cpu(), br.grad) < 1e-5
 
 
+def _grid64(shape, g):
+    """random multiples of 2^-6 in [-4, 4]"""
+    return torch.randint(-256, 257, shape, generator=g).float() / 64
+
+
+def _ulp32(x):
+    """the fp32 unit in the last place at magnitude x (fp64 tensor)"""
+    _, e = torch.frexp(x.abs().clamp_min(2.0 ** -126))
+    return torch.ldexp(torch.ones_like(x), e - 24)
+
+
+def _exact_bn_bwd_reference(dz, y, gamma, M, init_g, init_b, accumulate):
+    """dz [M][C] already masked; mean 0.5, invstd 2: fp64 sums (exact on this data), float32 of them (+ what was there), and the fp64 dy
+    with the tolerance of (d): 4 fp32 ulps of the larger of |dy| and the largest term of k0 * dz + k1 * y + k2."""
+    dz, y, g = dz.double(), y.double(), gamma.double()
+    s, q = dz.sum(0), (dz * ((y - 0.5) * 2.0)).sum(0)
+    dbeta, dgamma = s.float(), q.float()
+    if accumulate:
+        dbeta, dgamma = init_b + dbeta, init_g + dgamma
+    m0, m1 = s / M, q / M
+    k0, k1, k2 = g * 2.0, -g * 2.0 * 2.0 * m1, g * 2.0 * (0.5 * 2.0 * m1 - m0)
+    dy = k0 * dz + k1 * y + k2
+    big = torch.stack([dy.abs(), (k0 * dz).abs(), (k1 * y).abs(), k2.abs().expand_as(dy)]).nan_to_num(nan=0.0).amax(0)
+    return dgamma, dbeta, dy, 4 * _ulp32(big)
+
+
+def _same_bits(u, v):
+    return torch.equal(u.cpu().view(torch.int32), v.cpu().view(torch.int32))
+
+
+def _from_partials_refuses_more_columns_than_threads():
+    """(e) C / 4 > 256: an error from the argument check, before any launch (the buffers are dummies of 64 floats)"""
+    from qea import _lib, ops
+    C, M = 2048, 4
+    f = torch.zeros(64, device="cuda")
+    d = torch.zeros(64, device="cuda", dtype=torch.float64)
+    with pytest.raises(_lib.QeaError, match="qea_bn_bwd_from_partials: need .* C <= 1024"):
+        ops.bn_bwd(f, C, None, 0, f, C, M, C, f, f, f, True, f, f, f, C, stat64=d, relu_scale=f, relu_shift=f, partials=(d, 3))
+    torch.cuda.synchronize()
+
+
+def test_bn_backward_forms_agree_on_exactly_summable_data():
+    """The BatchNorm(+ReLU) backward in its five forms — qea_bn_bwd with the activation, with the mask recomputed from y, from the
+    partials of a producer (few blocks; many blocks: the two-stage fold through the 256 scratch rows), and qea_bn_bwd_pool against
+    qea_maxpool_bwd(accumulate) + qea_bn_bwd — on data whose fp64 sums are exact in ANY order: da, dskip, dpool and y are multiples of
+    2^-6 in [-4, 4], mean = 0.5 and invstd = 2 exactly, so every term of sum dz and sum dz * xhat is a multiple of 2^-11 below 2^7 and a
+    sum over < 2^14 rows needs < 2^32 units.  Then (a) dgamma and dbeta agree BIT FOR BIT between the forms and with float32 of the CPU's
+    fp64 sums, overwriting or accumulating; (b) dy is bit-equal among the forms that run bn_bwd_apply_kernel; (c) dy of the pool form is
+    bit-equal to the two calls outside the NaN's channel; (d) every dy is within 4 fp32 ulps (one rounding to fp32 + contraction) of the
+    fp64 formula, the ulp taken at the larger of |dy| and the largest of its three terms; (e) qea_bn_bwd_from_partials refuses
+    C / 4 > 256.  Shapes: (12, 130) idle lanes (3 columns do not divide 256), (1024, 7) one row-thread, (64, 5) fewer rows than
+    row-threads, (32, 8197) several blocks with a ragged last one."""
+    from qea import ops
+    dev = "cuda"
+    g = torch.Generator().manual_seed(17)
+    for C, M in [(12, 130), (1024, 7), (64, 5), (32, 8197)]:
+        y, da = _grid64((M, C), g), _grid64((M, C), g)
+        gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
+        mean, invstd = torch.full((C,), 0.5), torch.full((C,), 2.0)
+        scale = gamma * invstd
+        shift = beta - mean * scale
+        st = torch.stack([mean.double(), invstd.double()]).to(dev)
+        yd, dad, gd, md, isd, scd, shd = (t.to(dev) for t in (y, da, gamma, mean, invstd, scale, shift))
+        a = torch.empty(M, C, device=dev)
+        ops.bn_apply(yd, C, a, C, M, C, scd, shd, relu=True)
+        dz = da * (a.cpu() > 0)
+        parts = []
+        for blocks in (3, 700):                              # 700 > 2 * 256: the two-stage fold; + the scratch rows, never read unwritten
+            P = torch.full((blocks + 256, C, 2), 1e300, dtype=torch.float64)
+            P[:blocks] = 0
+            P[:blocks].index_add_(0, torch.arange(M) % blocks, torch.stack([dz.double(), dz.double() * ((y.double() - 0.5) * 2.0)], -1))
+            parts.append((P.to(dev), blocks))
+        forms = [dict(a=a, lda=C), dict(a=None, lda=0, relu_scale=scd, relu_shift=shd)]
+        forms += [dict(a=None, lda=0, relu_scale=scd, relu_shift=shd, partials=p) for p in parts]
+        init_g, init_b = torch.randn(C, generator=g), torch.randn(C, generator=g)
+        for accumulate in (False, True):
+            rg, rb, rdy, tol = _exact_bn_bwd_reference(dz, y, gamma, M, init_g, init_b, accumulate)
+            outs = []
+            for kw in forms:
+                kw = dict(kw)
+                dg, db, dy = init_g.to(dev), init_b.to(dev), torch.empty(M, C, device=dev)
+                ops.bn_bwd(dad, C, kw.pop("a"), kw.pop("lda"), yd, C, M, C, gd, md, isd, True, dg, db, dy, C, accumulate=accumulate, stat64=st, **kw)
+                outs.append((dg, db, dy))
+            torch.cuda.synchronize()
+            for i, (dg, db, dy) in enumerate(outs):
+                assert _same_bits(dg, rg) and _same_bits(db, rb), (C, M, accumulate, i)                       # (a)
+                assert _same_bits(dy, outs[0][2]), (C, M, accumulate, i)                                     # (b)
+                err = (dy.cpu().double() - rdy).abs()
+                assert bool((err <= tol).all()), (C, M, accumulate, i, (err / tol).max().item())             # (d)
+    for Hh, kw, C in [(2, 1, 12), (2, 2, 64), (8, 1, 64), (8, 2, 12)]:
+        B, Ww = 3, 16
+        M, OW = B * Hh * Ww, Ww // kw
+        y = _grid64((B, Hh, Ww, C), g)
+        y[0, 0, 0:2, :8] = 0.25                              # ties inside a window, across and down: first in scan order wins
+        y[0, 0:2, 2, :8] = 0.25
+        y[1, Hh - 2:Hh, 4:6, 8:12] = -3.0                    # a window whose activations are all zero
+        y[2, Hh - 2, 6, 3] = float("nan")
+        y = y.view(M, C)
+        dskip, dpool = _grid64((M, C), g), _grid64((B * (Hh // 2) * OW, C), g)
+        gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.3
+        mean, invstd = torch.full((C,), 0.5), torch.full((C,), 2.0)
+        scale = gamma * invstd
+        shift = beta - mean * scale
+        st = torch.stack([mean.double(), invstd.double()]).to(dev)
+        yd, skd, dpd, gd, md, isd, scd, shd = (t.to(dev) for t in (y, dskip, dpool, gamma, mean, invstd, scale, shift))
+        a = torch.empty(M, C, device=dev)
+        ops.bn_apply(yd, C, a, C, M, C, scd, shd, relu=True)
+        ac = a.cpu().view(B, Hh, Ww, C).permute(0, 3, 1, 2).double().requires_grad_()
+        F.max_pool2d(ac, (2, kw)).backward(dpool.view(B, Hh // 2, OW, C).permute(0, 3, 1, 2).double())
+        dz = (ac.grad.permute(0, 2, 3, 1).reshape(M, C).float() + dskip) * (a.cpu() > 0)
+        clean = torch.ones(C, dtype=torch.bool)
+        clean[3] = False                                     # the NaN's channel: dz * xhat = 0 * NaN there
+        init_g, init_b = torch.randn(C, generator=g), torch.randn(C, generator=g)
+        for accumulate in (False, True):
+            rg, rb, rdy, tol = _exact_bn_bwd_reference(dz, y, gamma, M, init_g, init_b, accumulate)
+            outs = []
+            for fused in (False, True):
+                dg, db, dy = init_g.to(dev), init_b.to(dev), torch.empty(M, C, device=dev)
+                if fused:
+                    ops.bn_bwd_pool(skd, C, dpd, C, kw, yd, C, B, Hh, Ww, C, gd, md, isd, True, dg, db, dy, C, accumulate=accumulate, stat64=st,
+                                    relu_scale=scd, relu_shift=shd)
+                else:
+                    dad = skd.clone()
+                    ops.maxpool_bwd(a, C, dpd, C, dad, C, B, Hh, Ww, C, 2, kw, relu_mask=False, accumulate=True)
+                    ops.bn_bwd(dad, C, None, 0, yd, C, M, C, gd, md, isd, True, dg, db, dy, C, accumulate=accumulate, stat64=st, relu_scale=scd,
+                               relu_shift=shd)
+                outs.append((dg.cpu(), db.cpu(), dy.cpu()))
+            for i, (dg, db, dy) in enumerate(outs):
+                assert _same_bits(dg[clean], rg[clean]) and _same_bits(db, rb), (Hh, kw, C, accumulate, i)   # (a)
+                assert bool(dg[3].isnan()) and bool(rg[3].isnan())
+                err = (dy.double() - rdy).abs()[:, clean]
+                assert bool((err <= tol[:, clean]).all()), (Hh, kw, C, accumulate, i, (err / tol[:, clean]).max().item())   # (d)
+            assert _same_bits(outs[0][2][:, clean], outs[1][2][:, clean]), (Hh, kw, C, accumulate)           # (c)
+    _from_partials_refuses_more_columns_than_threads()
+
+
 # ----------------------------------------------------------------------------- pool / layout
 @pytest.mark.parametrize("kh,kw", [(2, 2), (2, 1)])
 def test_maxpool_fwd_bwd_with_ties(kh, kw):
