@@ -573,6 +573,25 @@ int qea_ctc_history_loss(const float* lp, int32_t ld_t, int32_t ld_n, const int3
                          int32_t blank, int32_t S_max, float* loss, float* grad, int32_t gld_t, int32_t gld_n, float* nll,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Minibatch assembly from a device-resident strip store (datasets/resident.py: ResidentStrips; --resident of area_cli.py and
+ * train_crnn.py).  The store holds the n strips of a dataset as 8-bit grey after the loader's own PIL decode (and thumbnail of
+ * oversize strips): strip s is h[s] rows of w[s] bytes, row-major without padding, at pixels + offset[s].  ONE launch writes the
+ * whole batch out[B][OH][OW] (fp32, 16-byte aligned): strip idx[b] on a white (1.0) ground,
+ *   QEA_STRIP_ANCHOR_CENTRE  left = (OW - w) / 2, top = (OH - h) / 2 (rounded down): transform_helper.PadWhite followed by the
+ *                            loader's float32(p) / 255
+ *   QEA_STRIP_ANCHOR_LEFT    left = 0, top as above: datasets/bucketing.pad_to_bucket
+ * and every strip byte p replaced by table[p].  `table` is 256 fp32 values on the device, built by the HOST as float32(p) / 255, so
+ * the batch equals the loader's bit for bit whatever the device compiler makes of a division.  Every element of `out` is written
+ * exactly once (no prior fill); one 16-byte store per lane, hence OW % 4 == 0.  A strip taller than OH or wider than OW is clipped
+ * to its first OH rows / OW columns; an idx[b] outside 0..n-1 gives an all-white image (the Python caller validates idx on the host
+ * first).  No workspace, no LDS, nothing synchronises.  Refused before the launch: a NULL pointer, n < 1, B outside 1..2^24, OH
+ * outside 1..4096, OW outside 4..16384 or not a multiple of 4, an unknown anchor, a misaligned `out`.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects the entry point by symbol.) */
+#define QEA_STRIP_ANCHOR_CENTRE 0
+#define QEA_STRIP_ANCHOR_LEFT 1
+int qea_strip_batch(const uint8_t* pixels, const int64_t* offset, const int32_t* h, const int32_t* w, int32_t n, const int64_t* idx,
+                    int32_t B, int32_t OH, int32_t OW, int32_t anchor, const float* table, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,13 @@ FLAGS = [
     ("--no_rebalance_topk", dict(action="store_true", help="[new] data-parallel runs only: process every global TopKCER winner on the rank "
                                                            "that owns it instead of dealing the winners out in equal slices (one all-reduce of "
                                                            "k x 16 KB images); always so with --inner_limit_skip (label histories stay with the owner)"), "a"),
+    ("--resident", dict(action="store_true", help="[new] decode every strip of the training and validation ImgDatasets once, keep the 8-bit pixels on "
+                                                  "the device and build each minibatch by one launch (datasets/resident.py) instead of the "
+                                                  "per-image PIL / numpy / host-to-device path; same batches, same order, same values.  The store reproduces PadWhite(input_size) + "
+                                                  "float32 / 255 only: a dataset with another transform is refused"), "a"),
+    ("--resident_pack", dict(help="[new] --resident: keep the decoded strips in this .npz pack file (the validation set's in PATH with "
+                                  "'.val' before the extension) and reuse it while the files' names, sizes and mtimes are unchanged"), "a"),
+    ("--resident_max_gb", dict(type=float, default=8, help="[new] --resident: refuse a pack larger than this many GB"), "a"),
 ]
 
 # the warm-up and evaluation drivers: "c" = train_crnn.py (:217-275), "e" = eval_crnn.py, "v" = eval_prep.py (their __main__ blocks).
@@ -100,6 +107,13 @@ FLAGS += [
     ("--graph", dict(action="store_true", help="[new] replay the warm-up step (CRNN -> CTC -> backward -> Adam) as ONE hipGraph per (batch size, "
                                                "width, target-length cap, lr); the first two steps of a shape run eagerly, single-process runs only"),
      "c"),
+    ("--resident", dict(action="store_true", help="[new] decode every strip of the training and validation ImgDatasets once, keep the 8-bit pixels on "
+                                                  "the device and build each minibatch by one launch (datasets/resident.py) instead of the "
+                                                  "per-image PIL / numpy / host-to-device path; same batches, same order, same values.  The store reproduces PadWhite(input_size) + "
+                                                  "float32 / 255 only: a dataset with another transform is refused"), "c"),
+    ("--resident_pack", dict(help="[new] --resident: keep the decoded strips in this .npz pack file (the validation set's in PATH with "
+                                  "'.val' before the extension) and reuse it while the files' names, sizes and mtimes are unchanged"), "c"),
+    ("--resident_max_gb", dict(type=float, default=8, help="[new] --resident: refuse a pack larger than this many GB"), "c"),
 ]
 
 # the dataset pruner: "r" = pruning/prune_dataset.py (its __main__ block, :88-106)

@@ -916,3 +916,26 @@ def ctc_history_loss(lp, input_lengths, lens, offs, chars, depth_n, weights, w_s
                                       ws.numel(), _stream()), "qea_ctc_history_loss")
     HISTORY_CTC_LAUNCHES["ctc"] += 3 if need_grad else 2
     return loss, grad, nll
+
+
+STRIP_ANCHORS = {"centre": 0, "left": 1}     # QEA_STRIP_ANCHOR_* of include/qea_hip.h
+STRIP_LAUNCHES = {"batch": 0}                # launches of csrc/strip_batch.hip issued through this module (tests, tools)
+
+
+def strip_batch(pixels, offset, h, w, idx, table, out, anchor="centre"):
+    """include/qea_hip.h: qea_strip_batch — the resident store's pixels (uint8), offset (int64 [n]), h / w (int32 [n]), the device
+    idx (int64 [B]) and the 256-entry fp32 table -> out [B][1][OH][OW] fp32, written whole by ONE launch on the current stream."""
+    if anchor not in STRIP_ANCHORS:
+        raise ValueError(f"unknown anchor {anchor!r}")
+    if (pixels.dtype != torch.uint8 or offset.dtype != torch.int64 or h.dtype != torch.int32 or w.dtype != torch.int32
+            or idx.dtype != torch.int64 or table.dtype != torch.float32 or out.dtype != torch.float32):
+        raise _lib.QeaError("strip_batch needs uint8 pixels, int64 offsets and indices, int32 heights and widths, an fp32 table and output")
+    if not all(t.is_contiguous() for t in (pixels, offset, h, w, idx, table, out)):
+        raise _lib.QeaError("strip_batch needs contiguous tensors")
+    n, B = offset.numel(), idx.numel()
+    if h.numel() != n or w.numel() != n or table.numel() != 256 or out.dim() != 4 or out.shape[0] != B or out.shape[1] != 1:
+        raise _lib.QeaError(f"strip_batch: {n} offsets, {h.numel()} / {w.numel()} sizes, a table of {table.numel()}, out {tuple(out.shape)} for "
+                            f"{B} indices")
+    _lib.check(_lib.lib().qea_strip_batch(_ptr(pixels), _ptr(offset), _ptr(h), _ptr(w), n, _ptr(idx), B, out.shape[2], out.shape[3],
+                                          STRIP_ANCHORS[anchor], _ptr(table), _ptr(out), _stream()), "qea_strip_batch")
+    STRIP_LAUNCHES["batch"] += 1

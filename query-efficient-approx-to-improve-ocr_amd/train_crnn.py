@@ -19,6 +19,8 @@ Differences from the reference, all deliberate:
   * [new] --synthetic_size N: synthetic strips (datasets/synthetic.py) instead of --data_base_path.
   * [new] --graph: the training step as one hipGraph replay per (batch, width, target-length cap, lr) — qea.graph.PhaseAGraphs with
     one replica group; Adam is built capturable, a StepLR change of the lr records a new graph.  Single process only.
+  * [new] --resident: the strips of the ImgDataset training set (and of the validation set, without --ocr) are decoded once and kept
+    on the device; every minibatch is one launch (datasets/resident.py).  Same batches, order, RNG draws and values.
 
 As in the preprocessor trainers, `backend` / `train_set` / `val_set` / `ocr` are injection seams for tests: the default backend is
 the HIP path (there is no CPU implementation); datasets are (image [1,32,W], ground-truth label, ...) samples.
@@ -79,8 +81,9 @@ class TrainCRNN:
         dataset, validation_set = self._datasets(args, train_set, val_set)
         print(f"Train Dataset - {dataset}")
         print(f"Validation Dataset - {validation_set}")
-        self.loader_train = torch.utils.data.DataLoader(dataset, batch_size=self.batch_size, drop_last=True, shuffle=True)
-        self.loader_validation = torch.utils.data.DataLoader(validation_set, batch_size=self.batch_size)
+        self.loader_train = self._loader(args, dataset, "training set", batch_size=self.batch_size, drop_last=True, shuffle=True)
+        # with --ocr the validation samples are relabelled by the OCR item by item: that set keeps the sample loader
+        self.loader_validation = self._loader(args if self.ocr is None else None, validation_set, "validation set", batch_size=self.batch_size)
         self.train_set_size = len(self.loader_train.dataset)
         self.val_set_size = len(self.loader_validation.dataset)
         print(f"Train Set size - {self.train_set_size}, Val Set Size - {self.val_set_size}")
@@ -101,6 +104,16 @@ class TrainCRNN:
             self.crnn_model, self.optimizer_crnn, self.primary_loss_fn = self.model, self.optimizer, self.loss_function
             self._step_crnn = self.optimizer.step
             self.graphs = PhaseAGraphs(self)
+
+    def _loader(self, args, dataset, what, **kw):
+        if not getattr(args, "resident", False):
+            return torch.utils.data.DataLoader(dataset, **kw)
+        # [new] --resident: the strips decoded once and kept on the device, the same index batches
+        if getattr(args, "synthetic_size", None):
+            from qea._lib import QeaError
+            raise QeaError("--resident keeps ImgDataset strips on the device: it does not go with --synthetic_size")
+        from datasets.resident import resident_args, resident_loader
+        return resident_loader(dataset, self.input_size, self.device, what=what, **resident_args(args, what), **kw)
 
     def _datasets(self, args, train_set, val_set):
         """(training set of clean strips, validation set).  Training labels are the datasets' (ground truth) unless --ocr is given,

@@ -12,6 +12,9 @@ files and the whole-module checkpoints (:391-410), and returns (best_val_acc, be
 
 Under torch.distributed every rank runs this loop on its own shard of the dataset (additive:
 a single process behaves exactly like the reference).
+
+[new] --resident: ImgDataset training and validation sets are decoded once and kept on the device; the loaders keep torch's
+sampling and build every minibatch in one launch (datasets/resident.py) — same batches, order, RNG draws and values.
 """
 import os
 
@@ -44,6 +47,10 @@ class TrainNNPrep(TrainerCore):
         self.per_shard_topk = bool(getattr(args, "per_shard_topk", False))
         self.rebalance_topk = not bool(getattr(args, "no_rebalance_topk", False))
         self.select_before_clean = bool(getattr(args, "select_before_clean", False))
+        if getattr(args, "resident", False) and (widths is not None or getattr(args, "synthetic_size", None)):
+            from qea._lib import QeaError
+            raise QeaError("--resident keeps ImgDataset strips of one width on the device: it goes neither with per-sample widths (the "
+                           "bucketed path) nor with --synthetic_size")
         if widths is not None:                                # [new] variable-width lines: one width bucket per batch
             # the bucket batches are formed over the WHOLE (rank-identical) list and dealt round-robin, so every rank
             # runs the same number of steps (qea.dist.deal_batches)
@@ -56,15 +63,23 @@ class TrainNNPrep(TrainerCore):
             # data parallel: cut the (identically seeded) permutation to whole global batches, one group of batch_size per rank
             # and step: every rank runs the same number of optimiser steps (a rank with fewer would strand the others in RCCL)
             tr_idx = qdist.equal_shards(tr_idx, self.batch_size)
-            self.loader_train = torch.utils.data.DataLoader(train_set, batch_size=self.batch_size, drop_last=True,
-                                                            sampler=torch.utils.data.SubsetRandomSampler(tr_idx))
+            self.loader_train = self._loader(args, train_set, "training set", batch_size=self.batch_size, drop_last=True,
+                                             sampler=torch.utils.data.SubsetRandomSampler(tr_idx))
         va_idx = torch.randperm(len(val_set))[: self.val_subset_size]
-        self.loader_validation = torch.utils.data.DataLoader(val_set, batch_size=self.batch_size, drop_last=True,
-                                                             sampler=torch.utils.data.SubsetRandomSampler(va_idx))
+        self.loader_validation = self._loader(args, val_set, "validation set", batch_size=self.batch_size, drop_last=True,
+                                              sampler=torch.utils.data.SubsetRandomSampler(va_idx))
         self.train_set_size, self.val_set_size = len(train_set), len(val_set)
         self.lr_scheduler = args.lr_scheduler
         if self.lr_scheduler == "cosine":
             self.scheduler_crnn = torch.optim.lr_scheduler.CosineAnnealingLR(self.optimizer_crnn, T_max=self.max_epochs)
+
+    def _loader(self, args, dataset, what, **kw):
+        if not getattr(args, "resident", False):
+            return torch.utils.data.DataLoader(dataset, **kw)
+        # [new] --resident: the strips decoded once and kept on the device, the same index batches (under data parallelism every rank
+        # packs the whole set and takes its own indices)
+        from datasets.resident import resident_args, resident_loader
+        return resident_loader(dataset, self.input_size, self.device, what=what, **resident_args(args, what), **kw)
 
     def _default_datasets(self, args):
         n = getattr(args, "synthetic_size", None)
