@@ -592,6 +592,34 @@ int qea_ctc_history_loss(const float* lp, int32_t ld_t, int32_t ld_n, const int3
 int qea_strip_batch(const uint8_t* pixels, const int64_t* offset, const int32_t* h, const int32_t* w, int32_t n, const int64_t* idx,
                     int32_t B, int32_t OH, int32_t OW, int32_t anchor, const float* table, float* out, void* stream);
 
+/* The two minibatch samplers that pick on per-strip estimates (--minibatch_subset rangeCER / uniformEntropy).
+ *
+ * qea_spread_pick — the range sampling of CerRangeSampler.query (selection_utils.py:129-134) and sampleUsingEstimates
+ *   (selection_utils.py:52-57), the k serial picks in ONE launch of one workgroup, bit-identical to the host loop for finite inputs:
+ *   left = a private fp32 copy of est[0..n) (est is not written); for i = 0..k-1: j = the LOWEST index that minimises
+ *   fabsf(pts[i] - left[j]) (one fp32 subtraction, then the absolute value: no fma, no wider type; torch.argmin's first-index
+ *   rule), idx[i] = j (int64), left[j] = 100.0f.  The reference's sentinel is kept as it is: with k > n every estimate is 100
+ *   after n picks and index 0 repeats; an estimate >= 100 competes with the sentinel on equal terms.  `pts` is built by the host
+ *   exactly as before ((max - min) * torch.rand(k) + min in fp32), so the CPU generator is consumed as before.  est and pts must
+ *   be finite (the Python caller sends anything else to the host loop); n, k in 1..QEA_SPREAD_MAX_N.  `left` lives in LDS up to
+ *   QEA_SPREAD_LDS_MAX_N estimates; above, in `workspace` (16-byte aligned, qea_spread_pick_workspace_bytes(n) bytes — 0 for an
+ *   n that needs none, where `workspace` may be NULL).  The form is chosen by n alone: one wave up to QEA_SPREAD_WAVE_MAX_N, four
+ *   waves up to QEA_SPREAD_LDS4_MAX_N, sixteen above (thresholds measured: profiles/samplers.json, csrc/sampling.hip).  Nothing synchronises.
+ *
+ * qea_seq_entropy — update_entropies + calc_entropy (selection_utils.py:10-27) for a whole batch in one launch, one wave per
+ *   strip: lp holds log-probs, element (t,b,c) at t*ld_t + b*ld_n + c (any non-negative strides: the CRNN's 96-column rows, a
+ *   [:, a:b, :] slice);  out[b] = fp32( mean_t( -sum_c p log(p + 1e-6) ) / log(num_classes) ),  p = exp(lp[t,b,c]), evaluated in
+ *   fp64 and rounded once.  lp = -inf contributes 0.  num_classes is the reference's constant 95 whatever C is.  T * C <= 2^30.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects these three by symbol.) */
+#define QEA_SPREAD_WAVE_MAX_N 1536
+#define QEA_SPREAD_LDS4_MAX_N 24576
+#define QEA_SPREAD_LDS_MAX_N 32768
+#define QEA_SPREAD_MAX_N (1 << 24)
+size_t qea_spread_pick_workspace_bytes(int32_t n);
+int qea_spread_pick(const float* est, int32_t n, const float* pts, int32_t k, int64_t* idx, void* workspace, void* stream);
+int qea_seq_entropy(const float* lp, int64_t ld_t, int64_t ld_n, int32_t T, int32_t B, int32_t C, int32_t num_classes, float* out,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,7 +49,9 @@ FLAGS = [
     ("--lr_scheduler", dict(choices=["cosine"], help="Learning-rate scheduler for the CRNN"), "a"),
     # ---- new (additive) ----
     ("--synthetic_size", dict(type=int, help="[new] train on N synthetic samples instead of reading --data_base_path"), "pa"),
-    ("--select_before_clean", dict(action="store_true", help="[new] Phase A: pick the TopKCER / random subset FIRST and run the cleaner only on "
+    ("--entropies_path", dict(help="[new] --minibatch_subset uniformEntropy: start from this name -> entropy table (the cers/entropies.json "
+                                   "an earlier run wrote) instead of an empty one, where every strip counts as entropy 1.0"), "pa"),
+    ("--select_before_clean", dict(action="store_true", help="[new] Phase A: pick the TopKCER / rangeCER / uniformEntropy / random subset FIRST and run the cleaner only on "
                                                              "the picked images (the pick depends on names and CERs alone; eval-mode BatchNorm "
                                                              "makes every image's output independent of the rest of the minibatch)"), "a"),
     ("--per_shard_topk", dict(action="store_true", help="[new] data-parallel runs only: pick the TopKCER subset per GPU shard instead of "

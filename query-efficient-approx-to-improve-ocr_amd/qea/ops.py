@@ -939,3 +939,43 @@ def strip_batch(pixels, offset, h, w, idx, table, out, anchor="centre"):
     _lib.check(_lib.lib().qea_strip_batch(_ptr(pixels), _ptr(offset), _ptr(h), _ptr(w), n, _ptr(idx), B, out.shape[2], out.shape[3],
                                           STRIP_ANCHORS[anchor], _ptr(table), _ptr(out), _stream()), "qea_strip_batch")
     STRIP_LAUNCHES["batch"] += 1
+
+
+SPREAD_WAVE_MAX_N, SPREAD_LDS4_MAX_N, SPREAD_LDS_MAX_N, SPREAD_MAX_N = 1536, 24576, 32768, 1 << 24    # QEA_SPREAD_* of include/qea_hip.h
+SAMPLER_LAUNCHES = {"spread": 0, "entropy": 0}    # launches of csrc/sampling.hip issued through this module (tests, tools)
+ENTROPY_NUM_CLASSES = 95                          # calc_entropy's constant (selection_utils.py:10), whatever the width of the scores
+
+
+def spread_pick(est, pts):
+    """include/qea_hip.h: qea_spread_pick — est [n] / pts [k] (CUDA fp32, FINITE: the caller checks) -> idx [k] int64 on the device:
+    the k serial picks of the range samplers in one launch.  Nothing synchronises."""
+    if not (est.is_cuda and pts.is_cuda) or est.dtype != torch.float32 or pts.dtype != torch.float32 or est.dim() != 1 or pts.dim() != 1:
+        raise _lib.QeaError("spread_pick needs two one-dimensional CUDA float32 tensors (the host loop of selection_utils is the CPU path)")
+    n, k = est.numel(), pts.numel()
+    if not (1 <= n <= SPREAD_MAX_N and 1 <= k <= SPREAD_MAX_N):
+        raise _lib.QeaError(f"spread_pick: n={n}, k={k} outside 1..{SPREAD_MAX_N}")
+    est, pts = est.contiguous(), pts.contiguous()
+    L = _lib.lib()
+    idx = torch.empty(k, dtype=torch.int64, device=est.device)
+    nbytes = L.qea_spread_pick_workspace_bytes(n)
+    ws = workspace(nbytes, est.device) if nbytes else None
+    _lib.check(L.qea_spread_pick(_ptr(est), n, _ptr(pts), k, _ptr(idx), ws.data_ptr() if ws is not None else None, _stream()), "qea_spread_pick")
+    SAMPLER_LAUNCHES["spread"] += 1
+    return idx
+
+
+def seq_entropy(scores):
+    """include/qea_hip.h: qea_seq_entropy — scores [T][B][C] CUDA fp32 log-probs with a unit class stride (any T and B strides: the
+    CRNN's 96-column rows, a [:, a:b, :] slice) -> [B] fp32 normalised mean entropies on the device, one launch."""
+    if not scores.is_cuda or scores.dtype != torch.float32 or scores.dim() != 3:
+        raise _lib.QeaError("seq_entropy needs a CUDA float32 tensor [T][B][C] (selection_utils.update_entropies keeps the host path)")
+    T, B, Cc = scores.shape
+    if Cc > 1 and scores.stride(2) != 1 or scores.stride(0) < 0 or scores.stride(1) < 0:
+        scores = scores.contiguous()
+    out = torch.empty(B, dtype=torch.float32, device=scores.device)
+    if T == 0 or B == 0 or Cc == 0:
+        raise _lib.QeaError(f"seq_entropy: empty scores {tuple(scores.shape)}")
+    _lib.check(_lib.lib().qea_seq_entropy(_ptr(scores), scores.stride(0), scores.stride(1), T, B, Cc, ENTROPY_NUM_CLASSES, _ptr(out), _stream()),
+               "qea_seq_entropy")
+    SAMPLER_LAUNCHES["entropy"] += 1
+    return out

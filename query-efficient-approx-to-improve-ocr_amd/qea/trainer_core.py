@@ -123,6 +123,11 @@ class TrainerCore:
                 self.cers = json.load(f)
             self.selected_samples = {k: [False] * self.max_epochs for k in self.cers}
         self.tracked_labels = {name: [] for name in self.cers} if self.cers else {}
+        # [new] --entropies_path: the uniformEntropy sampler's table (name -> normalised mean entropy), as cers/entropies.json holds it
+        self.entropies = dict()
+        if getattr(args, "entropies_path", None):
+            with open(args.entropies_path, "r") as f:
+                self.entropies = json.load(f)
 
         self.char_to_index, self.index_to_char, self.vocab_size = get_char_maps(properties.char_set)
         self.input_size = properties.input_size
@@ -160,12 +165,19 @@ class TrainerCore:
             self.phase_a_graphs = PhaseAGraphs(self)
 
     def _make_sampler(self, needs_cers):
-        from selection_utils import datasampler_factory
+        """Every factory class with the arguments it needs (the reference builds them all as cls(self.cers) or cls(),
+        train_nn_area.py:72-77, which raises for uniformEntropy and the two global samplers)."""
+        import selection_utils as su
         if not self.selection_method:
             self.sampler = None
             return
-        cls = datasampler_factory(self.selection_method)
-        self.sampler = cls(self.cers) if needs_cers else cls()
+        cls = su.datasampler_factory(self.selection_method)
+        if issubclass(cls, su.UniformEntropySampler):
+            self.sampler = cls(self.entropies, self.cers or {})
+        elif issubclass(cls, su._GlobalSampler):
+            self.sampler = cls(self.cers or {}, self._num_bb_samples(len(self.cers or {})))
+        else:
+            self.sampler = cls(self.cers) if needs_cers else cls()
 
     # ---- reference helpers (train_nn_patch.py:158-191) ----
     def _call_model(self, images, labels):
@@ -310,3 +322,11 @@ class TrainerCore:
             preds = pred_to_string(scores, labels, self.index_to_char)
             cers = [compare_labels([p], [l])[1] for p, l in zip(preds, labels)]
         self.sampler.update_cer(cers, names)
+
+    def _update_entropies(self, scores, names):
+        """[new] the same Phase-B scores and names as _update_cers, for a sampler that keeps entropies (uniformEntropy): the reference's
+        update_entropies (selection_utils.py:20-27), which nothing there ever calls."""
+        if not (self.selection_method and len(names) and hasattr(self.sampler, "update_entropies")):
+            return
+        from selection_utils import update_entropies
+        update_entropies(self, scores, names)

@@ -4,7 +4,12 @@
 
 TopKCERSampler ranks on the GPU (qea_topk_desc_stable: descending CER, ties in ascending index
 order) when the images live there; the reference's `torch.argsort(descending=True)` leaves the order
-of tied CERs to the sort implementation, this one pins it to the stable order."""
+of tied CERs to the sort implementation, this one pins it to the stable order.
+
+The range samplers (rangeCER, uniformEntropy) run their serial picks on the GPU too (qea_spread_pick: one launch, bit-identical to
+the host loop) once the minibatch is large enough to pay for a launch and a read-back; QEA_SAMPLER=host keeps the loop.  The
+entropies of uniformEntropy come from qea_seq_entropy for CUDA scores: one [B] copy back instead of [T,B,C]."""
+import os
 import random
 
 import numpy as np
@@ -17,8 +22,15 @@ def calc_entropy(probs, num_classes=95):
 
 
 def update_entropies(self, crnn_scores, names):
-    probs = torch.exp(crnn_scores.detach()).cpu()
-    ents = [calc_entropy(probs[:, i, :]).mean().item() for i in range(probs.shape[1])]
+    """The reference's update_entropies (:20-27): the normalised mean entropy of every strip's [T,C] scores into the sampler's table.
+    CUDA scores: one launch and one [B] copy back (fp64 evaluation rounded once); CPU tensors: the reference's loop."""
+    scores = crnn_scores.detach()
+    if scores.is_cuda and scores.dtype == torch.float32 and scores.numel():
+        from qea import ops
+        ents = ops.seq_entropy(scores).tolist()
+    else:
+        probs = torch.exp(scores).cpu()
+        ents = [calc_entropy(probs[:, i, :]).mean().item() for i in range(probs.shape[1])]
     self.sampler.update_entropies(ents, names)
 
 
@@ -42,20 +54,45 @@ def _desc_stable_topk(values, k, device):
     return torch.from_numpy(np.argsort(-keys.numpy(), kind="stable")[:k].astype(np.int64))
 
 
-def _spread_pick(values, num_samples):
-    """The reference's range sampling (:41-57, :122-135): draw `num_samples` points uniformly over
-    [min, max] of the estimates and take, without replacement, the sample nearest to each."""
-    est = torch.tensor(values)
-    if est.shape[0] == 0:
-        return torch.tensor([], dtype=torch.long)
-    pts = (est.max() - est.min()) * torch.rand(num_samples) + est.min()
+# Smallest n * k at which the device pick is taken.  tools/bench_samplers.py (profiles/samplers.json) times the host loop against
+# upload + launch + read-back at (n, k) = (20, 19), (64, 60), (512, 486), (2048, 1945): host 0.13 / 0.37 / 3.0 / 13.8 ms, device
+# 0.09 / 0.12 / 0.46 / 2.2 ms on an MI355X box.  The device path won at every measured size, so this is the smallest of them; below
+# it nothing was measured and the loop stays.
+SPREAD_DEVICE_MIN_NK = 20 * 19
+
+
+def _spread_pick_host(est, pts):
+    """the specification: the reference's loop (:52-57, :129-134)"""
     left = est.clone()
-    idx = torch.zeros(num_samples, dtype=torch.long)
+    idx = torch.zeros(pts.shape[0], dtype=torch.long)
     for i, p in enumerate(pts):
         j = torch.argmin(torch.abs(p - left))
         idx[i] = j
         left[j] = 100
     return idx
+
+
+def _spread_pick(values, num_samples, rand=None, device=None):
+    """The reference's range sampling (:41-57, :122-135): draw `num_samples` points uniformly over
+    [min, max] of the estimates and take, without replacement, the sample nearest to each.
+    `rand`: a pre-drawn uniform vector in place of torch.rand(num_samples) (tests).  `device`: where the images live; on a CUDA device,
+    for finite fp32 inputs of at least SPREAD_DEVICE_MIN_NK estimate-point pairs and unless QEA_SAMPLER=host, the picks run as one
+    launch (qea_spread_pick) with the same result bit for bit.  The points are drawn on the host either way."""
+    est = torch.tensor(values)
+    if est.shape[0] == 0:
+        return torch.tensor([], dtype=torch.long)
+    pts = (est.max() - est.min()) * (torch.rand(num_samples) if rand is None else rand) + est.min()
+    n, k = est.shape[0], pts.shape[0]
+    if (device is not None and device.type == "cuda" and os.environ.get("QEA_SAMPLER", "device") != "host" and n * k >= SPREAD_DEVICE_MIN_NK
+            and est.dtype == torch.float32 and pts.dtype == torch.float32 and bool(torch.isfinite(est).all()) and bool(torch.isfinite(pts).all())):
+        from qea import ops
+        if n <= ops.SPREAD_MAX_N and k <= ops.SPREAD_MAX_N:
+            return ops.spread_pick(est.to(device), pts.to(device)).cpu()
+    return _spread_pick_host(est, pts)
+
+
+def _device_of(images):
+    return images.device if torch.is_tensor(images) else None
 
 
 class DataSampler:
@@ -79,6 +116,8 @@ class DataSampler:
 
 
 class RandomSampler(DataSampler):
+    content_free = True     # the pick is a permutation draw: names, estimates and images do not enter
+
     def query(self, images, labels, num_samples, names=None):
         return self._take(images, labels, torch.randperm(images.shape[0])[:num_samples])
 
@@ -88,8 +127,10 @@ class CerRangeSampler(DataSampler):
         super().__init__(cers)
         self.discount_factor = discount_factor
 
+    content_free = True     # the pick depends on names, CERs and RNG draws only
+
     def query(self, images, labels, num_samples, names):
-        return self._take(images, labels, _spread_pick(_known(names, self.cers), num_samples))
+        return self._take(images, labels, _spread_pick(_known(names, self.cers), num_samples, device=_device_of(images)))
 
 
 class TopKCERSampler(DataSampler):
@@ -117,17 +158,26 @@ class TopKCERSampler(DataSampler):
 
 
 class UniformEntropySampler(DataSampler):
+    """Range sampling over the CRNN's own uncertainty: the normalised mean entropy of a strip's scores (update_entropies), which
+    needs neither black-box queries nor a --cers_ocr_path file.
+    A strip without an estimate yet counts as entropy 1.0, the normalised maximum: nothing is known about it.  So the estimate list
+    always has one entry per strip and the returned indices address the minibatch itself (the reference's `if name in estimates`
+    compaction would index the wrong images as soon as one name is missing; it is not reproduced here).  With every name known the
+    picks are exactly the reference's sampleUsingEstimates on the same RNG state.  In a first epoch every estimate is 1.0, every
+    drawn point is 1.0 and the pick is the first num_samples strips of the minibatch: deterministic, no warm-up needed."""
+    UNKNOWN = 1.0
+    content_free = True     # the pick depends on names, entropies and RNG draws only
+
     def __init__(self, entropies, cers):
         super().__init__(cers)
-        self.entropies = entropies
+        self.entropies = entropies if entropies is not None else dict()
 
     def query(self, images, labels, num_samples, names):
-        return self._take(images, labels, _spread_pick(_known(names, self.entropies), num_samples))
+        est = [self.entropies.get(n, self.UNKNOWN) for n in names]
+        return self._take(images, labels, _spread_pick(est, num_samples, device=_device_of(images)))
 
     def update_entropies(self, ents, names):
-        for n, e in zip(names, ents):
-            if n not in self.entropies:
-                print(f"Sample not present - {n}")
+        for n, e in zip(names, ents):                    # (a first sighting is the normal case here: no "Sample not present" line)
             self.entropies[n] = e
 
 

@@ -182,6 +182,7 @@ class TrainNNPrep(TrainerCore):
                     loss.backward()
                     self._step_prep()
                 self._update_cers(scores, labels, names)
+                self._update_entropies(scores, names)
                 training_loss += loss.item()
                 if step % 100 == 0:
                     print(f"Epoch: {epoch}, Iteration: {step} => {loss.item()}")

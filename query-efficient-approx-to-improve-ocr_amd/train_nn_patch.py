@@ -180,6 +180,7 @@ class TrainNNPrep(TrainerCore):
                         loss = self._get_loss(sc, y, pred_size, y_size, img_all[i])
                         total = loss if total is None else total + loss
                         self._update_cers(sc, labels, self._strip_names(labels, names[i]))
+                        self._update_entropies(sc, self._strip_names(labels, names[i]))
                         training_loss += loss.item()
                         if step % 100 == 0:
                             print("Iteration: %d => %f" % (step, loss.item()))
@@ -193,6 +194,7 @@ class TrainNNPrep(TrainerCore):
                     loss = self._get_loss(scores, y, pred_size, y_size, img_out)
                     loss.backward()
                     self._update_cers(scores, labels, self._strip_names(labels, names[0]))
+                    self._update_entropies(scores, self._strip_names(labels, names[0]))
                     training_loss += loss.item()
                     if step % 100 == 0:
                         print("Iteration: %d => %f" % (step, loss.item()))

@@ -215,6 +215,8 @@ def save_all_jsons(self, epoch):
     save_json(self.tracked_labels, os.path.join(self.tracked_labels_path, "tracked_labels_current.json"))
     save_json(self.selected_samples, os.path.join(self.selectedsamples_path, "selected_samples_current.json"))
     save_json(self.sampler.all_cers, os.path.join(self.cers_base_path, "all_cers.json"))
+    if hasattr(self.sampler, "entropies"):               # [new] uniformEntropy: the sampler's current table, readable back through --entropies_path
+        save_json(self.sampler.entropies, os.path.join(self.cers_base_path, "entropies.json"))
 
 
 def save_img(images, name, dir, nrow=8):
