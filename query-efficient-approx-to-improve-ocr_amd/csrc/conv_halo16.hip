@@ -23,8 +23,8 @@ namespace {
 //    per wave cycle, 0.0 with this one: profiles/r04_halo_lab_pmc.json);
 //  * out-of-image halo pixels are LOADED from a zero-filled 16 bytes instead of selected to zero behind the load: the select made
 //    hipcc wait for the whole gather right after issuing it;
-//  * filter planes in the order [n-block][chunk][step = tap * 2 + ks][plane][16-channel group][lane][8] (qea_pack_frag_planes_f16
-//    writes this order for C_in % 64 == 0): lane l of group g holds filter row g * 16 + (l & 15), channels ks * 32 + 8 (l >> 4) + j.
+//  * filter planes in the 16-row order that qea_pack_frag_planes_f16 writes for C_in % 64 == 0 (written down in weight_forms.hip,
+//    rows16_frag): lane l of group g holds filter row g * 16 + (l & 15), channels ks * 32 + 8 (l >> 4) + j.
 // Accumulator map: tile (row i, half row xh, channel group g2), register r of lane l = pixel xh * 16 + 4 (l >> 4) + r of tile row i,
 // channel g2 * 16 + (l & 15) of the wave's 32.  Element index e = (xh * 2 + g2) * 4 + r below.
 // ---------------------------------------------------------------------------------------------

@@ -904,7 +904,7 @@ int launch_halo(const ConvArgs& a, hipStream_t s) {
 // and splits every input element once per tap.  Here the (TH+2) x 34 input halo of a TH x 32 pixel tile is gathered ONCE,
 // split ONCE into the three bf16 planes and kept in LDS for all nine taps and all channel slices; the filter comes from its
 // cached planes in MFMA-fragment order (qea_pack_frag_planes: one coalesced 1 KiB wave load per fragment, L1/L2-resident,
-// next step's fragments in flight under this step's MFMAs); six v_mfma_f32_32x32x16_bf16 per product in the order of the
+// next step's fragments in flight under this step's MFMAs; the 32-row order, written down in weight_forms.hip); six v_mfma_f32_32x32x16_bf16 per product in the order of the
 // other split kernels.  LDS rows = pixels x C_in bf16, the 16-byte slots of pixel p stored at slot ^ ((p >> s) & m) so
 // that the 16 pixels of a ds_read_b128 lane group fall on distinct slots of the 256-byte bank row.
 // ---------------------------------------------------------------------------------------------
@@ -1331,102 +1331,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_bf3_wg
   if constexpr (PKW != 0) qea_amax_commit_block(pm, pamax);
 }
 
-// w [N][9][Cin] fp32 -> fragment-ordered planes [chunk][step = tap*KS + cs][plane][nj][lane][8 bf16], chunk width CW (32 or 64
-// channels), KS = CW / 16: lane (n = nj*32 + (lane & 31), half = lane >> 5) holds channels chunk*CW + cs*16 + 8*half + j of filter
-// row n at `tap`
-__global__ void pack_frag_planes_kernel(const float* __restrict__ w, __bf16* __restrict__ dst, int N, int Cin, int CW) {
-  const int NB = N > 128 ? 128 : N;                            // output channels per n-block (one workgroup column)
-  const int KSr = CW / 16, WNr = NB / 32, chunks = Cin / CW;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;         // (n-block, chunk, step, nj, lane)
-  if (i >= (N / NB) * chunks * 9 * KSr * WNr * 64) return;
-  const int lane = i & 63;
-  const int nj = (i >> 6) % WNr;
-  const int gst = (i >> 6) / WNr;                              // (n-block, chunk, step) flattened
-  const int nbk = gst / (chunks * 9 * KSr);
-  const int chunk = (gst / (9 * KSr)) % chunks, st = gst % (9 * KSr);
-  const int tap = st / KSr, cs = st % KSr;
-  const int n = nbk * NB + nj * 32 + (lane & 31);
-  const float* src = w + ((size_t)n * 9 + tap) * Cin + chunk * CW + cs * 16 + 8 * (lane >> 5);
-  const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
-  bf16x4 h0, m0, l0, h1, m1, l1;
-  qea_split3(v0, h0, m0, l0);
-  qea_split3(v1, h1, m1, l1);
-  bf16x8 pl[3];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    pl[0][k] = h0[k]; pl[0][k + 4] = h1[k];
-    pl[1][k] = m0[k]; pl[1][k + 4] = m1[k];
-    pl[2][k] = l0[k]; pl[2][k + 4] = l1[k];
-  }
-#pragma unroll
-  for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(dst + ((((size_t)gst * 3 + p) * WNr + nj) * 64 + lane) * 8) = pl[p];
-}
-
-// the fp16 two-plane form of pack_frag_planes_kernel: [n-block][chunk][step][plane h, l][nj][lane][8 fp16] of the filter SCALED by
-// s_w (qea_f16_scale of the filter's abs-max `wmax`), followed — at element offset N * 9 * Cin * 2 — by one float: 1 / s_w
-__global__ void pack_frag_planes_f16_kernel(const float* __restrict__ w, _Float16* __restrict__ dst, int N, int Cin, int CW,
-                                            const float* __restrict__ wmax) {
-  const int NB = N > 128 ? 128 : N;
-  const int KSr = CW / 16, WNr = NB / 32, chunks = Cin / CW;
-  float sw, inv;
-  qea_f16_scale(wmax[0], sw, inv);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;         // (n-block, chunk, step, nj, lane)
-  if (i == 0) reinterpret_cast<float*>(dst + (size_t)N * 9 * Cin * 2)[0] = inv;
-  if (i >= (N / NB) * chunks * 9 * KSr * WNr * 64) return;
-  const int lane = i & 63;
-  const int nj = (i >> 6) % WNr;
-  const int gst = (i >> 6) / WNr;
-  const int nbk = gst / (chunks * 9 * KSr);
-  const int chunk = (gst / (9 * KSr)) % chunks, st = gst % (9 * KSr);
-  const int tap = st / KSr, cs = st % KSr;
-  const int n = nbk * NB + nj * 32 + (lane & 31);
-  const float* src = w + ((size_t)n * 9 + tap) * Cin + chunk * CW + cs * 16 + 8 * (lane >> 5);
-  const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
-  f16x4 h0, l0, h1, l1;
-  qea_split2_f16(v0, sw, h0, l0);
-  qea_split2_f16(v1, sw, h1, l1);
-  f16x8 pl[2];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    pl[0][k] = h0[k]; pl[0][k + 4] = h1[k];
-    pl[1][k] = l0[k]; pl[1][k + 4] = l1[k];
-  }
-#pragma unroll
-  for (int p = 0; p < 2; ++p) *reinterpret_cast<f16x8*>(dst + ((((size_t)gst * 2 + p) * WNr + nj) * 64 + lane) * 8) = pl[p];
-}
-
-// ... and for 64-channel chunks (C_in % 64 == 0) in the order of conv3x3_halo_m16_kernel: [n-block][chunk][step = tap * 2 + ks][plane][16-channel
-// group][lane][8 fp16]: lane l of group g holds filter row n-block * NB + g * 16 + (l & 15), channels chunk * 64 + ks * 32 + 8 (l >> 4) + j
-__global__ void pack_frag_planes_f16_m16_kernel(const float* __restrict__ w, _Float16* __restrict__ dst, int N, int Cin, const float* __restrict__ wmax) {
-  const int NB = N > 128 ? 128 : N;
-  const int NGr = NB / 16, chunks = Cin / 64;
-  float sw, inv;
-  qea_f16_scale(wmax[0], sw, inv);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;         // (n-block, chunk, step, group, lane)
-  if (i == 0) reinterpret_cast<float*>(dst + (size_t)N * 9 * Cin * 2)[0] = inv;
-  if (i >= (N / NB) * chunks * 18 * NGr * 64) return;
-  const int lane = i & 63;
-  const int ng = (i >> 6) % NGr;
-  const int gst = (i >> 6) / NGr;                              // (n-block, chunk, step) flattened
-  const int nbk = gst / (chunks * 18);
-  const int chunk = (gst / 18) % chunks, st = gst % 18;
-  const int tap = st / 2, ks = st % 2;
-  const int n = nbk * NB + ng * 16 + (lane & 15);
-  const float* src = w + ((size_t)n * 9 + tap) * Cin + chunk * 64 + ks * 32 + 8 * (lane >> 4);
-  const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
-  f16x4 h0, l0, h1, l1;
-  qea_split2_f16(v0, sw, h0, l0);
-  qea_split2_f16(v1, sw, h1, l1);
-  f16x8 pl[2];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    pl[0][k] = h0[k]; pl[0][k + 4] = h1[k];
-    pl[1][k] = l0[k]; pl[1][k + 4] = l1[k];
-  }
-#pragma unroll
-  for (int p = 0; p < 2; ++p) *reinterpret_cast<f16x8*>(dst + ((((size_t)gst * 2 + p) * NGr + ng) * 64 + lane) * 8) = pl[p];
-}
-
 template <int CIN, int COUT, int TH, bool STATS, int IMW = 0, int NPL = 3, int PKW = 0, bool BST = false>
 int launch_halo_bf3_(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = IMW ? (size_t)NPL * (TH + 1) * (32 / IMW) * (IMW + 2) * CIN * 2 : (size_t)NPL * (TH + 2) * 34 * CIN * 2;
@@ -1851,36 +1755,6 @@ extern "C" int qea_split_planes_f16(const float* x, int32_t ld, int64_t M, int32
   const long long blocks = (total + 255) / 256;
   QEA_REQUIRE(blocks < 0x7fffffffLL, "qea_split_planes_f16: too large");
   hipLaunchKernelGGL(split_planes_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ld, (long long)M, C, xmax, (_Float16*)planes);
-  QEA_CHECK_LAUNCH();
-  return QEA_OK;
-}
-
-extern "C" size_t qea_pack_frag_planes_bytes(int32_t N, int32_t Cin) { return (size_t)N * 9 * Cin * 6; }
-
-extern "C" int qea_pack_frag_planes(const float* w, int32_t N, int32_t Cin, void* planes, void* stream) {
-  QEA_REQUIRE(w && planes && (N == 32 || N == 64 || (N > 0 && N % 128 == 0)) && (Cin == 32 || (Cin % 64 == 0 && Cin <= 512)),
-              "qea_pack_frag_planes: N in {32, 64, 128k}, Cin = 32 or a multiple of 64 up to 512");
-  const int total = 9 * (Cin / 16) * (N / 32) * 64;
-  hipLaunchKernelGGL(pack_frag_planes_kernel, dim3(qea_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, (__bf16*)planes, N, Cin,
-                     Cin == 32 ? 32 : 64);
-  QEA_CHECK_LAUNCH();
-  return QEA_OK;
-}
-
-extern "C" size_t qea_pack_frag_planes_f16_bytes(int32_t N, int32_t Cin) { return (size_t)N * 9 * Cin * 4 + 16; }
-
-extern "C" int qea_pack_frag_planes_f16(const float* w, int32_t N, int32_t Cin, const float* wmax, void* planes, void* stream) {
-  QEA_REQUIRE(w && planes && wmax && (N == 32 || N == 64 || (N > 0 && N % 128 == 0)) && (Cin == 32 || (Cin % 64 == 0 && Cin <= 512)),
-              "qea_pack_frag_planes_f16: N in {32, 64, 128k}, Cin = 32 or a multiple of 64 up to 512");
-  if (Cin % 64 == 0) {                                     // 64-channel chunks: the order of conv3x3_halo_m16_kernel (16x16x32 MFMA)
-    const int total16 = 9 * (Cin / 32) * (N / 16) * 64;
-    hipLaunchKernelGGL(pack_frag_planes_f16_m16_kernel, dim3(qea_cdiv(total16, 256)), dim3(256), 0, (hipStream_t)stream, w, (_Float16*)planes, N, Cin, wmax);
-    QEA_CHECK_LAUNCH();
-    return QEA_OK;
-  }
-  const int total = 9 * (Cin / 16) * (N / 32) * 64;
-  hipLaunchKernelGGL(pack_frag_planes_f16_kernel, dim3(qea_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, (_Float16*)planes, N, Cin,
-                     Cin == 32 ? 32 : 64, wmax);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

@@ -8,7 +8,7 @@
 // a time: eight 16-byte loads per thread in flight, split ONCE into the two fp16 planes in LDS (rows of 128 B, 16-byte slots
 // XOR-swizzled as in the LDS-halo conv), the next chunk — or the next work item's first chunk — gathered into registers under this
 // chunk's MFMAs; the filter comes from its cached fragment-order planes (qea_pack_frag_planes_f16_1x1, L2-resident), one step
-// ahead of its MFMAs.  Four waves side by side over NB = 128 or 256 output channels, each wave all four 32-row blocks; three
+// ahead of its MFMAs; their layout is written down in weight_forms.hip.  Four waves side by side over NB = 128 or 256 output channels, each wave all four 32-row blocks; three
 // v_mfma_f32_32x32x16_f16 per product (lh, hl, hh), fp32 accumulate, exact un-scaling, then the shared epilogue (bias, ReLU,
 // NHWC / TBC / transposed-conv scatter, producer-carried abs-max).  Persistent grid, two workgroups per CU.
 //
@@ -247,37 +247,6 @@ int launch_(const ConvArgs& a, hipStream_t s) {
   return QEA_OK;
 }
 
-// w [N][K] fp32 -> [128-column block][chunk][cs][plane h, l][nj4][lane][8 fp16] of the filter scaled by s_w (qea_f16_scale of `wmax`),
-// followed, at element offset N * K * 2, by one float: 1 / s_w.  Lane (n = 32 nj + (lane & 31), half = lane >> 5) holds channels
-// 64 chunk + 16 cs + 8 half + 0..7 of filter row n.
-__global__ void pack_frag_planes_f16_1x1_kernel(const float* __restrict__ w, _Float16* __restrict__ dst, int N, int K, const float* __restrict__ wmax) {
-  const int chunks = K / 64;
-  float sw, inv;
-  qea_f16_scale(wmax[0], sw, inv);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;       // (column block, chunk, cs, nj, lane)
-  if (i == 0) reinterpret_cast<float*>(dst + (size_t)N * K * 2)[0] = inv;
-  if (i >= (N / 128) * chunks * 4 * 4 * 64) return;
-  const int lane = i & 63;
-  const int nj = (i >> 6) & 3;
-  const int gst = i >> 8;                                    // (column block, chunk, cs) flattened
-  const int nbk = gst / (chunks * 4);
-  const int chunk = (gst >> 2) % chunks, cs = gst & 3;
-  const int n = nbk * 128 + nj * 32 + (lane & 31);
-  const float* src = w + (size_t)n * K + chunk * 64 + cs * 16 + 8 * (lane >> 5);
-  const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
-  f16x4 h0, l0, h1, l1;
-  qea_split2_f16(v0, sw, h0, l0);
-  qea_split2_f16(v1, sw, h1, l1);
-  f16x8 pl[2];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    pl[0][k] = h0[k]; pl[0][k + 4] = h1[k];
-    pl[1][k] = l0[k]; pl[1][k + 4] = l1[k];
-  }
-#pragma unroll
-  for (int q = 0; q < 2; ++q) *reinterpret_cast<f16x8*>(dst + ((((size_t)gst * 2 + q) * 4 + nj) * 64 + lane) * 8) = pl[q];
-}
-
 }  // namespace
 
 int qea_conv::launch_gemm1x1_f16(const ConvArgs& a, hipStream_t s) {
@@ -286,16 +255,4 @@ int qea_conv::launch_gemm1x1_f16(const ConvArgs& a, hipStream_t s) {
   //  N 512 K 2048 488.2 / 533.4 / 521.1; 128-channel chunks and a 2 x 2 wave layout were slower: profiles/r03_gemm1x1_experiment.txt)
   if (a.N % 256 == 0 && (long long)qea_cdiv(a.M, 128) * (a.N / 256) >= 1024) return launch_<64, 1, 2>(a, s);
   return launch_<64, 1, 1>(a, s);
-}
-
-extern "C" size_t qea_pack_frag_planes_f16_1x1_bytes(int32_t N, int32_t K) { return (size_t)N * K * 4 + 16; }
-
-extern "C" int qea_pack_frag_planes_f16_1x1(const float* w, int32_t N, int32_t K, const float* wmax, void* planes, void* stream) {
-  QEA_REQUIRE(w && planes && wmax && N > 0 && N % 128 == 0 && K > 0 && K % 64 == 0 && (long long)N * K * 4 < 0x7fffffffLL,
-              "qea_pack_frag_planes_f16_1x1: N a multiple of 128, K a multiple of 64");
-  QEA_REQUIRE(((uintptr_t)w & 15) == 0 && ((uintptr_t)planes & 15) == 0, "qea_pack_frag_planes_f16_1x1: pointers must be 16-byte aligned");
-  const int total = (N / 128) * (K / 64) * 4 * 4 * 64;
-  hipLaunchKernelGGL(pack_frag_planes_f16_1x1_kernel, dim3(qea_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, (_Float16*)planes, N, K, wmax);
-  QEA_CHECK_LAUNCH();
-  return QEA_OK;
 }

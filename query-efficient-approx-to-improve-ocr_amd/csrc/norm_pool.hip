@@ -543,21 +543,6 @@ __global__ void transpose_kernel(const float* __restrict__ in, float* __restrict
   }
 }
 
-// conv weight [Co][KH][KW][Ci] -> input-gradient filter [Ci][KH][KW][Co] with taps flipped
-__global__ void flip_transpose_kernel(const float* __restrict__ w, float* __restrict__ wt, int Co, int Ci, int KH, int KW) {
-  const long long n = (long long)Co * KH * KW * Ci;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    // i indexes wt: (ci, kh', kw', co), co fastest
-    const int co = (int)(i % Co);
-    long long r = i / Co;
-    const int kw2 = (int)(r % KW);
-    r /= KW;
-    const int kh2 = (int)(r % KH);
-    const int ci = (int)(r / KH);
-    wt[i] = w[(((size_t)co * KH + (KH - 1 - kh2)) * KW + (KW - 1 - kw2)) * Ci + ci];
-  }
-}
-
 size_t ws_need(int rows, int consts, int C) { return ((size_t)rows * 2 + consts) * C * sizeof(double); }
 
 // The one argument check of the column kernels: C a multiple of 4 with at most one float4 column per thread, the strides (OR-ed
@@ -858,14 +843,6 @@ extern "C" int qea_maxpool_bwd(const float* x, int32_t ldx, const float* dy, int
 extern "C" int qea_transpose2d(const float* in, float* out, int32_t R, int32_t Cc, void* stream) {
   QEA_REQUIRE(in && out && R > 0 && Cc > 0, "qea_transpose2d: bad arguments");
   hipLaunchKernelGGL(transpose_kernel, dim3(qea_cdiv(Cc, 32), qea_cdiv(R, 32)), dim3(256), 0, (hipStream_t)stream, in, out, R, Cc);
-  QEA_CHECK_LAUNCH();
-  return QEA_OK;
-}
-
-extern "C" int qea_filter_flip_transpose(const float* w, float* wt, int32_t Co, int32_t Ci, int32_t KH, int32_t KW, void* stream) {
-  QEA_REQUIRE(w && wt && Co > 0 && Ci > 0 && KH > 0 && KW > 0, "qea_filter_flip_transpose: bad arguments");
-  hipLaunchKernelGGL(flip_transpose_kernel, dim3(qea_grid_for((long long)Co * Ci * KH * KW)), dim3(256), 0, (hipStream_t)stream, w, wt, Co, Ci,
-                     KH, KW);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

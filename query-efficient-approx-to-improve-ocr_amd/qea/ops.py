@@ -143,32 +143,56 @@ def weight_cached(kind, w, build, also=(), extra=None, batch=None):
     return val
 
 
-# ---- derived forms of one model in ONE launch (round 4).  A form that qea_weight_forms_multi can make registers a FormJob under its
-# cache key; the first miss after a weight update then builds every stale registered form of the SAME group whose weight lives in the
-# same flat parameter buffer (= the same model) with one launch, and the later requests of the step hit the cache.  Groups: "flip"
-# (flip-transposed filters) and "pack" (fragment planes; a pack of a flipped filter asks for the flipped filter first, which runs
-# the flip group).  Forms outside a flat buffer (tests, ad-hoc weights) keep their single launches.
+# ---- derived forms of one model in ONE launch (round 4).  A form that qea_weight_forms_multi can make is described ONCE, by a FormJob.
+# On a miss weight_cached hands the record of an aligned CUDA weight to _batched_forms, which registers it under its cache key and
+# builds it with the multi entry — together with every other stale registered form of the SAME group whose weight lives in the same
+# flat parameter buffer (= the same model), so the later requests of the step hit the cache; a weight outside a flat buffer is a launch
+# of one job.  FormJob.build (the form's single entry point) runs where nothing is cached or batched: QEA_BATCH_FORMS=0, the cache off,
+# a capture without a token, an unaligned or ad-hoc filter.  Groups: "flip" (flip-transposed filters) and "pack" (fragment planes; a
+# pack of a flipped filter asks for the flipped filter first, which runs the flip group).
 BATCH_FORMS = {"on": os.environ.get("QEA_BATCH_FORMS", "1") != "0"}
 _form_jobs = {}
 
 
 class FormJob:
-    """plain data (no reference to the weight: a registered job must not keep its tensor alive).  srck: "self" = the weight itself,
-    "flipT" = its flip-transposed form (dims of the 3x3 pack: N, Cin of the input-gradient conv); out: shape or byte count;
-    amax: (ld, M, Cc) of the filter_absmax call, or None."""
+    """plain data (no reference to the weight: a registered job must not keep its tensor alive).  kind, dims: of qea_wform_job;
+    srck: what the form is made from — "self" = the weight itself, "flipT" = its flip-transposed form (dims of the 3x3 pack: N, Cin of
+    the input-gradient conv), None = a tensor only the caller can derive (never batched); out: shape or byte count;
+    amax: (ld, M, Cc) of the abs-max pass over the weight (srck None: over the caller's tensor), or None."""
     __slots__ = ("group", "kind", "dims", "srck", "out", "amax", "wref", "also")
 
     def __init__(self, group, kind, dims, srck, out, amax):
         self.group, self.kind, self.dims, self.srck, self.out, self.amax = group, kind, dims, srck, out, amax
 
-    def source(self, w):
-        return w if self.srck == "self" else flip_transposed(w, self.dims[1], self.dims[0], 3, 3)
+    def parts(self, w, given=None):
+        """-> (source, output, abs-max or None).  w: the model weight the form is cached with, None for an ad-hoc filter; given: the
+        source where the caller holds it — required when w or srck is None, nobody else can derive it then."""
+        if given is not None:
+            src = given
+        elif self.srck == "self":
+            src = w
+        else:
+            assert self.srck == "flipT" and w is not None, "a form without a derivable source needs the source"
+            src = flip_transposed(w, self.dims[1], self.dims[0], 3, 3)
+        out = torch.empty(self.out, device=src.device) if isinstance(self.out, tuple) else torch.empty(self.out, dtype=torch.uint8, device=src.device)
+        if self.amax is None:
+            return src, out, None
+        if w is None:
+            return src, out, absmax(src, *self.amax)
+        # ONE rule: of the model weight (the flipped filter holds the same elements), of the source where it is not derived by srck
+        return src, out, filter_absmax((self.srck, w), w if self.srck else src, *self.amax)
 
-    def alloc(self, w):
-        return torch.empty(self.out, device=w.device) if isinstance(self.out, tuple) else torch.empty(self.out, dtype=torch.uint8, device=w.device)
-
-    def scale(self, w):
-        return None if self.amax is None else filter_absmax((self.srck, w), w, *self.amax)
+    def build(self, w, given=None):
+        """this form alone, through its single entry point"""
+        L = _lib.lib()
+        src, out, am = self.parts(w, given)
+        if self.kind == 0:
+            filter_flip_transpose(src, out, *self.dims)
+        elif self.kind == 1:
+            _lib.check(L.qea_pack_frag_planes_f16(_ptr(src), self.dims[0], self.dims[1], _ptr(am), out.data_ptr(), _stream()), "qea_pack_frag_planes_f16")
+        else:
+            _lib.check(L.qea_pack_frag_planes_f16_1x1(_ptr(src), self.dims[0], self.dims[1], _ptr(am), out.data_ptr(), _stream()), "qea_pack_frag_planes_f16_1x1")
+        return out
 
 
 def _cache_ver(w, also, token, extra=None):
@@ -201,7 +225,7 @@ def _batched_forms(key, w, also, job, token):
     jobs = (_lib.WformJob * len(todo))()
     outs, keep = [], []
     for i, (_k, wi, _a, ji) in enumerate(todo):
-        src, out, am = ji.source(wi), ji.alloc(wi), ji.scale(wi)
+        src, out, am = ji.parts(wi)
         keep.append((src, am))
         outs.append(out)
         jobs[i].src, jobs[i].dst, jobs[i].amax, jobs[i].kind = src.data_ptr(), out.data_ptr(), (am.data_ptr() if am is not None else None), ji.kind
@@ -214,11 +238,8 @@ def _batched_forms(key, w, also, job, token):
 
 def flip_transposed(w, Co, Ci, KH, KW):
     """wt[ci][KH-1-kh][KW-1-kw][co] = w[co][kh][kw][ci]: the filter of the input-gradient convolution (cached)."""
-    def build():
-        wt = torch.empty(Ci, KH, KW, Co, device=w.device)
-        filter_flip_transpose(w, wt, Co, Ci, KH, KW)
-        return wt
-    return weight_cached(("flipT", Co, Ci, KH, KW), w, build, batch=FormJob("flip", 0, (Co, Ci, KH, KW), "self", (Ci, KH, KW, Co), None))
+    job = FormJob("flip", 0, (Co, Ci, KH, KW), "self", (Ci, KH, KW, Co), None)
+    return weight_cached(("flipT", Co, Ci, KH, KW), w, lambda: job.build(w), batch=job)
 
 
 def transposed(w, R, Cc):
@@ -228,6 +249,32 @@ def transposed(w, R, Cc):
         transpose2d(w, out, R, Cc)
         return out
     return weight_cached(("T", R, Cc), w, build)
+
+
+def _frag_planes_f16(d, kind, x, w, w_src, x_amax):
+    """conv_igemm on a tile that reads the filter from fp16 fragment planes (kind 1: 3x3 LDS-halo kernel, kind 2: 1x1 LDS tile):
+    points `d` at the cached planes of `w` and at the input's abs-max; returns both tensors (the caller holds them over the launch).
+    The planes are batchable when `w` is a model's weight itself or its flip-transposed form (the input-gradient filter: the flipped
+    filter, itself a cached form, is asked for first, which builds all stale flipped filters of the model in one launch)."""
+    L = _lib.lib()
+    N, Cin = d.N, d.Cin
+    K = 9 * Cin if kind == 1 else Cin
+    srck, amax = None, (K, N, K)
+    if w_src is not None and len(w_src) == 2:
+        if w_src[0] == "fwd" and w_src[1].data_ptr() == w.data_ptr():
+            srck = "self"
+        elif kind == 1 and w_src[0] == "flipT" and d.KH == 3 and d.KW == 3:
+            srck, amax = "flipT", (9 * N, Cin, 9 * N)
+    job = FormJob("pack", kind, (N, Cin, 0, 0), srck, (L.qea_pack_frag_planes_f16_bytes if kind == 1 else L.qea_pack_frag_planes_f16_1x1_bytes)(N, Cin), amax)
+    if w_src is None:
+        frag = job.build(None, w)
+    else:
+        frag = weight_cached(("fragf16" if kind == 1 else "frag1x1", w_src[0], N, Cin), w_src[1], lambda: job.build(w_src[1], w),
+                             also=tuple(w_src[2]) if len(w_src) > 2 else (), batch=job if srck else None)
+    # the input's abs-max: carried by the tensor's producer (x_amax), else one pass over the input here
+    xmax = x_amax if x_amax is not None else absmax(x, d.ldx, d.B * d.H * d.W, Cin)
+    d.w_frag_planes, d.x_absmax = frag.data_ptr(), xmax.data_ptr()
+    return frag, xmax
 
 
 def conv_igemm(x, w, y, *, B, H, W, Cin, OH, OW, N, KH, KW, pad=(0, 0), stride=(1, 1), ldx, ldy,
@@ -256,46 +303,17 @@ def conv_igemm(x, w, y, *, B, H, W, Cin, OH, OW, N, KH, KW, pad=(0, 0), stride=(
     wants = L.qea_conv_igemm_wants_frag_planes(C.byref(d)) if PRESPLIT["on"] else 0
     if wants == 2 and SPLIT_F16["on"] and x_planes is None and w_planes is None:
         # 1x1 GEMM on the 128-row LDS tile (tile 26, fp16 split only): filter [N][K] in fragment-order fp16 planes (cached)
-        def build():
-            out = torch.empty(L.qea_pack_frag_planes_f16_1x1_bytes(N, Cin), dtype=torch.uint8, device=x.device)
-            wmax = filter_absmax(w_src, w, Cin, N, Cin)
-            _lib.check(L.qea_pack_frag_planes_f16_1x1(_ptr(w), N, Cin, _ptr(wmax), out.data_ptr(), _stream()), "qea_pack_frag_planes_f16_1x1")
-            return out
-        job = None
-        if w_src is not None and w_src[0] == "fwd" and len(w_src) == 2 and w_src[1].data_ptr() == w.data_ptr():
-            job = FormJob("pack", 2, (N, Cin, 0, 0), "self", L.qea_pack_frag_planes_f16_1x1_bytes(N, Cin), (Cin, N, Cin))
-        frag = weight_cached(("frag1x1", w_src[0], N, Cin), w_src[1], build, also=tuple(w_src[2]) if len(w_src) > 2 else (), batch=job) if w_src is not None else build()
-        d.w_frag_planes = frag.data_ptr()
-        xmax = x_amax if x_amax is not None else absmax(x, ldx, B * H * W, Cin)
-        d.x_absmax = xmax.data_ptr()
-    elif wants == 1:
+        frag, xmax = _frag_planes_f16(d, 2, x, w, w_src, x_amax)
+    elif wants == 1 and SPLIT_F16["on"]:
         # 3x3 layer on the split LDS-halo kernel: its filter in fragment-order planes (a few hundred KB, cached)
-        f16 = SPLIT_F16["on"]
-
+        frag, xmax = _frag_planes_f16(d, 1, x, w, w_src, x_amax)
+    elif wants == 1:
         def build():
-            if f16:
-                out = torch.empty(L.qea_pack_frag_planes_f16_bytes(N, Cin), dtype=torch.uint8, device=x.device)
-                wmax = filter_absmax(w_src, w, 9 * Cin, N, 9 * Cin)
-                _lib.check(L.qea_pack_frag_planes_f16(_ptr(w), N, Cin, _ptr(wmax), out.data_ptr(), _stream()), "qea_pack_frag_planes_f16")
-                return out
             out = torch.empty(L.qea_pack_frag_planes_bytes(N, Cin), dtype=torch.uint8, device=x.device)
             _lib.check(L.qea_pack_frag_planes(_ptr(w), N, Cin, out.data_ptr(), _stream()), "qea_pack_frag_planes")
             return out
-        job = None
-        if f16 and w_src is not None and len(w_src) == 2 and KH == 3 and KW == 3:
-            nb = L.qea_pack_frag_planes_f16_bytes(N, Cin)
-            if w_src[0] == "fwd" and w_src[1].data_ptr() == w.data_ptr():
-                job = FormJob("pack", 1, (N, Cin, 0, 0), "self", nb, (9 * Cin, N, 9 * Cin))
-            elif w_src[0] == "flipT":
-                # the input-gradient filter: planes of the flip-transposed weight (itself a cached form: asked for first, which
-                # builds all stale flipped filters of the model in one launch)
-                job = FormJob("pack", 1, (N, Cin, 0, 0), "flipT", nb, (9 * N, Cin, 9 * N))
-        frag = weight_cached(("fragf16" if f16 else "frag", w_src[0], N, Cin), w_src[1], build, also=tuple(w_src[2]) if len(w_src) > 2 else (), batch=job) if w_src is not None else build()
+        frag = weight_cached(("frag", w_src[0], N, Cin), w_src[1], build, also=tuple(w_src[2]) if len(w_src) > 2 else ()) if w_src is not None else build()
         d.w_frag_planes = frag.data_ptr()
-        if f16:
-            # the input's abs-max: carried by the tensor's producer (x_amax), else one pass over the input here
-            xmax = x_amax if x_amax is not None else absmax(x, ldx, B * H * W, Cin)
-            d.x_absmax = xmax.data_ptr()
     elif PRESPLIT["on"] and Cin % 16 == 0 and L.qea_conv_igemm_uses_split_bf16(C.byref(d)):
         K = KH * KW * Cin
         if N * K * 6 < (1 << 31) - 256:

@@ -2,6 +2,7 @@
 autograd, on seeded inputs.  Integer / index results bit-exact, fp32 within stated tolerances."""
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -384,9 +385,12 @@ def test_head_fwd_bwd():
 
 
 # ----------------------------------------------------------------------------- derived weight forms, several per launch
-def test_weight_forms_multi_equals_the_single_launches():
+def test_weight_forms_multi_equals_the_single_launches(golden_dir):
     """qea_weight_forms_multi (csrc/weight_forms.hip): flip-transposed filters, 3x3 fragment planes (both chunk orders) and 1x1
-    fragment planes of several layers in ONE launch each group — the same bytes as the single calls."""
+    fragment planes of several layers in ONE launch each group — the same bytes as the single calls.  Both run the same device bodies, so
+    the bytes themselves are pinned too: tools/weight_form_digests.py's cases (every branch of the index maps, one shape per kind
+    beyond the multi kernel's grid, single entries and the multi entry in two job orders) against the digests recorded before the
+    bodies were merged (tests/golden/weight_form_digests.json)."""
     import ctypes as C
     from qea import _lib, ops
     L = _lib.lib()
@@ -444,6 +448,17 @@ def test_weight_forms_multi_equals_the_single_launches():
     for a, b in zip(single, multi):
         assert torch.equal(a, b)
     assert L.qea_weight_forms_multi(jobs, 65, st) < 0          # more than 64 jobs: refused, not truncated
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    try:
+        import weight_form_digests as D
+    finally:
+        sys.path.pop(0)
+    pinned = json.load(open(os.path.join(golden_dir, "weight_form_digests.json")))
+    assert pinned["cases"] == D.CASES, "the cases changed: regenerate the golden file from the commit that pinned it"
+    got = D.digests()
+    assert sorted(got) == sorted(pinned["sha256"]) and len(got) == 49
+    moved = [k for k in sorted(got) if got[k] != pinned["sha256"][k]]
+    assert not moved, f"{len(moved)} of {len(got)} derived forms changed their bytes: {moved}"
 
 
 # ----------------------------------------------------------------------------- LSTM
