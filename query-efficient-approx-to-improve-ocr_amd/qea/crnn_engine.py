@@ -10,11 +10,9 @@ their autograd, including the NaN scrub of CRNN.backward_hook (:30-32).
 """
 import torch
 
-from . import ops
+from . import batchnorm, ops
 from .params import ensure_flat
 
-BN_EPS = 1e-5
-BN_MOMENTUM = 0.1
 FUSE_POOL = True      # tests flip this: conv1 + ReLU + pool and BatchNorm2 apply + ReLU + pool as one pass each (same bits)
 HID = 256
 
@@ -48,23 +46,11 @@ class CRNNEngine:
         if H != 32 or W % 4:
             raise ValueError(f"CRNN input must be [B,1,32,W] with W % 4 == 0, got {H}x{W}")
         c = self.cp
-        # groups: an int (equal groups) or a sequence of per-group SAMPLE counts (ragged groups, round 4: the strips of several
-        # documents in one pass, each document its own BatchNorm batch as in the reference's one-document-per-call loop)
-        if isinstance(groups, int):
-            if B % groups:
-                raise ValueError(f"batch {B} is not a multiple of groups={groups}")
-            sizes = [B // groups] * groups
-        else:
-            sizes = [int(v) for v in groups]
-            if sum(sizes) != B or any(v <= 0 for v in sizes):
-                raise ValueError(f"group sizes {sizes} do not partition the batch of {B}")
-            groups = len(sizes)
-        starts = [sum(sizes[:i]) for i in range(groups)]
-        ctx = {"x": x, "B": B, "H": H, "W": W, "bn_training": bn_training, "groups": groups, "group_sizes": sizes} if need_grad else None
+        parts = batchnorm.partition(groups, B)            # groups: an int (equal groups) or per-group sample counts (ragged, round 4)
+        ctx = {"x": x, "B": B, "H": H, "W": W, "parts": parts} if need_grad else None
 
         # producer-carried abs-max of every tensor a split-fp16 conv / wgrad launch consumes (amx[name]; None when that split is off)
-        pool_ = ops.amax_pool(dev)
-        slot = (lambda: pool_.slot()) if pool_ is not None else (lambda: None)
+        slot = ops.amax_pool(dev)
         amx = {}
         # conv1 (C_in = 1) + ReLU, pool 2x2
         # (round 4: the backward rebuilds this activation from x, qea_conv_c1_pool_bwd — it is written only where something still reads it)
@@ -113,36 +99,21 @@ class CRNNEngine:
             ops.conv_igemm(cur, P[c + name + ".weight"], y, B=B, H=h, W=w, Cin=cin, OH=h, OW=w, N=512, KH=3, KW=3, pad=(1, 1),
                            ldx=cin, ldy=512, bias=P[c + name + ".bias"], w_src=("fwd", P[c + name + ".weight"]), x_amax=amx[cur_name])
             amx["a" + name[-1]] = slot()
-            G = groups if bn_training else 1
-            gb = [(starts[gi], sizes[gi]) for gi in range(G)] if bn_training else [(0, B)]     # (first sample, samples) of every group
-            coef = torch.empty(G, 4, 512, device=dev)
-            stat64 = torch.empty(G, 2, 512, device=dev, dtype=torch.float64) if (bn_training and need_grad) else None
             a = torch.empty(M, 512, device=dev)
-            for gi in range(G):
-                b0, bg = gb[gi]
-                Mg = bg * h * w
-                yg, ag = y[b0 * h * w:(b0 + bg) * h * w], a[b0 * h * w:(b0 + bg) * h * w]
-                if bn_training:
-                    ops.bn_train_stats(yg, 512, Mg, 512, P[c + bn + ".weight"], P[c + bn + ".bias"], BN_EPS, BN_MOMENTUM,
-                                       Bf[c + bn + ".running_mean"], Bf[c + bn + ".running_var"], coef[gi, 0], coef[gi, 1], coef[gi, 2],
-                                       coef[gi, 3], stat64[gi] if stat64 is not None else None)
-                else:
-                    ops.bn_eval_coeff(512, P[c + bn + ".weight"], P[c + bn + ".bias"], Bf[c + bn + ".running_mean"],
-                                      Bf[c + bn + ".running_var"], BN_EPS, None, coef[gi, 0], coef[gi, 1], coef[gi, 2], coef[gi, 3])
-                if name == "conv6" and FUSE_POOL:
-                    # BatchNorm apply + ReLU + the (2,1) max-pool behind it in one pass (bit-identical; p6 is allocated here)
-                    if gi == 0:
-                        p6 = torch.empty(B * (h // 2) * w, 512, device=dev)
-                        amx["p6"] = slot()
-                    ops.bn_apply_pool(yg, 512, ag, 512, p6[b0 * (h // 2) * w:(b0 + bg) * (h // 2) * w], 512, bg, h, w, 512, coef[gi, 2],
-                                      coef[gi, 3], 2, 1, relu=True, amax=amx["a" + name[-1]], pooled_amax=amx["p6"])
-                else:
-                    ops.bn_apply(yg, 512, ag, 512, Mg, 512, coef[gi, 2], coef[gi, 3], relu=True, amax=amx["a" + name[-1]])
-            acts["y" + name[-1]], acts["coef" + name[-1]], acts["a" + name[-1]], acts["st" + name[-1]] = y, coef, a, stat64
+            pool = None
+            if name == "conv6" and FUSE_POOL:
+                # BatchNorm apply + ReLU + the (2,1) max-pool behind it in one pass (bit-identical; p6 is allocated here)
+                p6 = torch.empty(B * (h // 2) * w, 512, device=dev)
+                amx["p6"] = slot()
+                pool = (p6, 512, 2, 1, amx["p6"])
+            acts["bn" + name[-1]], _ = batchnorm.forward(y, a, 512, h, w, 512, P[c + bn + ".weight"], P[c + bn + ".bias"],
+                                                         Bf[c + bn + ".running_mean"], Bf[c + bn + ".running_var"], bn_training, parts,
+                                                         need_grad, amax=amx["a" + name[-1]], pool=pool)
+            acts["a" + name[-1]], acts["y" + name[-1]] = a, y     # (y: the conv output under the name the trace tools tap)
             dims[name] = (h, w)
             cur, cur_name = a, "a" + name[-1]
         if bn_training:
-            fs.ibuf.add_(groups)                                   # num_batches_tracked: one per group, as sequential calls
+            fs.ibuf.add_(len(parts))                                # num_batches_tracked: one per group, as sequential calls
         amx["seq"] = slot()
         if not FUSE_POOL:
             p6 = torch.empty(B * (h // 2) * w, 512, device=dev)
@@ -182,7 +153,7 @@ class CRNNEngine:
             # that read y take it from here — left by the one-launch layer kernel itself, else one pass
             y_amax = slot()
             if not ops.lstm_layer_fwd_any(gates, cst, y, pf, split, T, B, y_amax=y_amax):
-                y_amax = ops.absmax(y, 512, T * B, 512) if pool_ is not None else None
+                y_amax = ops.absmax(y, 512, T * B, 512) if slot.on else None
             lstm.append({"x": xin, "gates": gates, "c": cst, "y": y, "pb": pb, "split": split, "x_amax": xin_amax, "y_amax": y_amax})
             xin = y
         # Linear + log_softmax (vocab padded to a multiple of 32 columns; pad columns stay 0)
@@ -206,7 +177,7 @@ class CRNNEngine:
         G = {n: p.grad for n, p in P.items()}
         dev = dlp.device
         full = None
-        if ctx.get("grad_group", -1) >= 0 and ctx["groups"] > 1:
+        if ctx.get("grad_group", -1) >= 0 and len(ctx["parts"]) > 1:
             # only ONE replica group receives a gradient (CRNN.forward(backward_group=g) detached the others): run the whole
             # backward on that group's samples.  Batch-major activations are row slices; the [T][B][..] sequence buffers are copied.
             full = (ctx["B"], ctx["x"])
@@ -216,17 +187,13 @@ class CRNNEngine:
         vp, V = self.vpad, self.vocab
         c = self.cp
         TB = T * B
-        side = self.__dict__.get("_side")
-        if side is None or side.side is not None and side.side.device != dev:
-            side = ops.SideStream(dev)
-            self._side = side
+        side = ops.SideStream.of(self, dev)
 
         g = dlp.contiguous().view(TB, V)
         dlogits = torch.empty(TB, vp, device=dev)
         ops.log_softmax_bwd(g, V, ctx["lp"], vp, dlogits, vp, TB, V, vp, nan_scrub)
-        pool_ = ops.amax_pool(dev)                                # abs-max slots of this pass (None: the fp16 split is off)
-        slot = (lambda: pool_.slot()) if pool_ is not None else (lambda: None)
-        f16 = pool_ is not None                                   # the split-fp16 GEMMs below want their operands' abs-max
+        slot = ops.amax_pool(dev)                                 # abs-max slots of this pass (None: the fp16 split is off)
+        f16 = slot.on                                             # the split-fp16 GEMMs below want their operands' abs-max
         dl_amax = ops.absmax(dlogits, vp, TB, vp) if f16 else None
 
         # Linear
@@ -323,36 +290,15 @@ class CRNNEngine:
         if not FUSE_POOL_BWD:
             da = torch.empty(B * h * w, 512, device=dev)
             ops.maxpool_bwd(acts["a6"], 512, dp6, 512, da, 512, B, h, w, 512, 2, 1, relu_mask=False)
-        bn_training = ctx["bn_training"]
         amx = ctx.get("amx", {})                                  # forward tensors' abs-max (a replica-group slice keeps its tensor's bound)
         for name, bn, cin, src in (("conv6", "batchnorm2", 512, "a5"), ("conv5", "batchnorm1", 256, "p4")):
             M = B * h * w
-            k = name[-1]
-            coef = acts["coef" + k]
             dy_ = torch.empty(M, 512, device=dev)
             dy_amax = slot()
-            NG = coef.shape[0]
-            gsz = ctx.get("group_sizes") if NG > 1 else None
-            if gsz is None or len(gsz) != NG:
-                gsz = [B // NG] * NG
-            for gi in range(NG):
-                b0 = sum(gsz[:gi])
-                Mg = gsz[gi] * h * w
-                sl = slice(b0 * h * w, b0 * h * w + Mg)
-                st = acts["st" + k]
-                if da is None:
-                    # conv6's output went through the (2,1) pool only: its backward rides in the two passes of BatchNorm2's (qea_bn_bwd_pool)
-                    Bg = gsz[gi]
-                    psl = slice(b0 * (h // 2) * w, (b0 + Bg) * (h // 2) * w)
-                    ops.bn_bwd_pool(None, 0, dp6[psl], 512, 1, acts["y" + k][sl], 512, Bg, h, w, 512, P[c + bn + ".weight"], coef[gi, 0],
-                                    coef[gi, 1], bn_training, G[c + bn + ".weight"] if param_grads else None,
-                                    G[c + bn + ".bias"] if param_grads else None, dy_[sl], 512, accumulate=True,
-                                    stat64=st[gi] if st is not None else None, relu_scale=coef[gi, 2], relu_shift=coef[gi, 3], amax=dy_amax)
-                    continue
-                ops.bn_bwd(da[sl], 512, None, 0, acts["y" + k][sl], 512, Mg, 512, P[c + bn + ".weight"], coef[gi, 0],
-                           coef[gi, 1], bn_training, G[c + bn + ".weight"] if param_grads else None,
-                           G[c + bn + ".bias"] if param_grads else None, dy_[sl], 512, accumulate=True,
-                           stat64=st[gi] if st is not None else None, relu_scale=coef[gi, 2], relu_shift=coef[gi, 3], amax=dy_amax)
+            # da None: conv6's output went through the (2,1) pool only, whose backward rides in the two passes of BatchNorm2's (qea_bn_bwd_pool)
+            batchnorm.backward(acts["bn" + name[-1]], da, 512 if da is not None else 0, dy_, P[c + bn + ".weight"],
+                               G[c + bn + ".weight"] if param_grads else None, G[c + bn + ".bias"] if param_grads else None, amax=dy_amax,
+                               pool=(dp6, 512, 1) if da is None else None)
             if param_grads:
                 def bn_conv_grads(dy_=dy_, name=name, src=src, cin=cin, M=M, dy_amax=dy_amax):
                     # (the bias gradient = column sums of dy rides with the weight gradient's staging waves where the kernel has it)
@@ -417,28 +363,25 @@ class CRNNEngine:
                 ops.conv_c1_dgrad(dy1, 64, P[c + "conv1.weight"], dx, B, H, W, 64)
         side.join()
         if full is not None and dx is not None:
-            Bf, g, k = full[0], ctx["_g"], B
-            dxf = torch.zeros(Bf, 1, H, W, device=dev)
-            dxf[g * k:(g + 1) * k].copy_(dx)
+            dxf = torch.zeros(full[0], 1, H, W, device=dev)
+            dxf[ctx["_b0"]:ctx["_b0"] + B].copy_(dx)
             dx = dxf
         return dx
 
     @staticmethod
     def _group_slice(ctx, dlp):
         """The saved context and the output gradient restricted to replica group g = ctx["grad_group"]."""
-        g, R, B = ctx["grad_group"], ctx["groups"], ctx["B"]
-        k = B // R
-        b0 = g * k
+        g, B = ctx["grad_group"], ctx["B"]
+        b0, k = ctx["parts"][g]
         T = ctx["T"]
-        dims = ctx["dims"]
         sub = dict(ctx)
-        sub.update(B=k, groups=1, group_sizes=[k], grad_group=-1, _g=g, x=ctx["x"][b0:b0 + k])
+        sub.update(B=k, parts=[(0, k)], grad_group=-1, _b0=b0, x=ctx["x"][b0:b0 + k])
         acts = {}
         for name, t in ctx["acts"].items():
             if t is None:
                 acts[name] = None
-            elif name.startswith("coef") or name.startswith("st"):
-                acts[name] = t[g:g + 1] if t.shape[0] == R else t        # per-group BN coefficients / fp64 statistics
+            elif isinstance(t, batchnorm.Stage):
+                acts[name] = t.restricted(b0, k)
             else:
                 rows = t.shape[0] // B                                   # pixels per sample at this layer
                 acts[name] = t[b0 * rows:(b0 + k) * rows]

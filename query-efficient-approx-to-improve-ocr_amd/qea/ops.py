@@ -420,11 +420,14 @@ def mfma_mode():
 class AmaxPool:
     """Zero-filled 4-byte slots for producer-carried abs-max values: one allocation + one memset per forward / backward pass."""
 
-    def __init__(self, device, n=192):
-        self.buf = torch.zeros(n, device=device)
+    def __init__(self, device, n=192, on=True):
+        self.on = on
+        self.buf = torch.zeros(n, device=device) if on else None
         self.used = 0
 
-    def slot(self):
+    def __call__(self):
+        if not self.on:
+            return None
         if self.used == self.buf.numel():
             self.buf = torch.zeros(self.buf.numel(), device=self.buf.device)
             self.used = 0
@@ -433,8 +436,8 @@ class AmaxPool:
 
 
 def amax_pool(device):
-    """-> AmaxPool when the fp16 split is active (its launches want abs-max values), else None (producers then skip the atomics)"""
-    return AmaxPool(device) if (SPLIT_F16["on"] and mfma_mode() == "split_f16") else None
+    """-> slot(): the next abs-max slot of this pass when the fp16 split is active (slot.on), else None (producers then skip the atomics)"""
+    return AmaxPool(device, on=SPLIT_F16["on"] and mfma_mode() == "split_f16")
 
 
 def filter_absmax(w_src, w, ld, M, Cc):
@@ -493,6 +496,14 @@ class SideStream:
 
     def __init__(self, device):
         self.side = torch.cuda.Stream(device)
+
+    @classmethod
+    def of(cls, owner, device):
+        """owner's side stream on `device`, made on first use and kept as owner._side"""
+        side = owner.__dict__.get("_side")
+        if side is None or side.side is not None and side.side.device != device:
+            side = owner._side = cls(device)
+        return side
 
     @property
     def enabled(self):

@@ -255,3 +255,16 @@ def test_colreduce_workspace_answers_equal_the_pinned_ones(golden_dir):
     bad = [(m, c, want[i][j], got[i][j]) for i, m in enumerate(Q.AXES["M"]) for j, c in enumerate(Q.AXES["C"]) if want[i][j] != got[i][j]]
     assert not bad, f"{len(bad)} answers moved (M, C, pinned, got): {bad[:5]}"
     assert all(row[-1] == 0 for row in want) and all(v > 0 for row in want for v in row[:-1])      # C = 6: no multiple of 4
+
+
+def test_batchnorm_partition():
+    """qea.batchnorm.partition: the (first sample, samples) list of equal and of ragged statistics groups, and what it refuses."""
+    import pytest
+    from qea.batchnorm import partition
+    assert partition(3, 12) == [(0, 4), (4, 4), (8, 4)]
+    assert partition([3, 3, 5, 5, 2], 18) == [(0, 3), (3, 3), (6, 5), (11, 5), (16, 2)]
+    assert partition((3, 1, 2), 6) == [(0, 3), (3, 1), (4, 2)]
+    assert partition(1, 7) == [(0, 7)] and partition([7], 7) == [(0, 7)]
+    for bad in (5, [3, 3], [4, 0, 3], [8, -1], 0, -2):           # not a multiple, another sum, a zero / negative size, groups < 1
+        with pytest.raises(ValueError):
+            partition(bad, 7)
