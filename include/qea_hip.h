@@ -592,6 +592,31 @@ int qea_ctc_history_loss(const float* lp, int32_t ld_t, int32_t ld_n, const int3
 int qea_strip_batch(const uint8_t* pixels, const int64_t* offset, const int32_t* h, const int32_t* w, int32_t n, const int64_t* idx,
                     int32_t B, int32_t OH, int32_t OW, int32_t anchor, const float* table, float* out, void* stream);
 
+/* All text strips of a step cut out of its documents in ONE launch, and their gradient put back in ONE launch (csrc/doc_crops.hip;
+ * datasets/resident.py: ResidentDocuments.crops; --resident of patch_cli.py).  The reference cuts them one document at a time
+ * (utils.py:118-141 over the samples of datasets/patch_dataset.py:14-129).
+ *   box [n_boxes][4] int32 = (x0, y0, x1, y1) of every word box of the store, clipped to the canvas; the boxes of document d are rows
+ *   box_first[d] .. box_first[d+1]-1 (box_first int32 [n_docs+1]).  A step holds N images [N][H][W] fp32, image n being document
+ *   doc[n] (int64 [N]); its S strips are all boxes of its documents, in document order and then box order:
+ *   strip_first int32 [N+1] = prefix sums of the chosen documents' box counts, strip_first[N] = S.
+ * qea_doc_crops_gather — out[S][OH][OW]: for every strip bit for bit what qea_crop_pad_gather gives for that image and box (the crop
+ *   centred on white 1.0; a crop larger than the target loses its extra pixel on the left / top).  Every element is written, one
+ *   16-byte store per lane: OW % 4 == 0, `out` 16-byte aligned.  A strip whose document or box does not exist is all white.
+ * qea_doc_crops_scatter — the backward, in gather form and WITHOUT atomics: dimg[n][y][x] = the sum over the boxes of document doc[n]
+ *   that cover (x, y), in ASCENDING box order starting from 0, of the dout element that read it; 0 where no box does.  accumulate = 1
+ *   adds that sum to what dimg holds.  Every element of dimg is written exactly once (no prior fill), one 16-byte store per lane:
+ *   W % 4 == 0, `dimg` 16-byte aligned.  The result is fixed by the inputs; for boxes that do not overlap it equals a zero fill
+ *   followed by qea_crop_pad_scatter per document, bit for bit.  6 KB of LDS (the boxes culled against a workgroup's 16 x 64 tile).
+ * Nothing synchronises, no workspace.  Refused before the launch: a NULL pointer, n_docs or n_boxes < 1, N outside 1..2^16, H outside
+ * 1..8192, W or OW outside 4..8192 or not a multiple of 4, S outside 1..2^24, OH outside 1..4096, a misaligned out / dimg.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects these two by symbol.) */
+int qea_doc_crops_gather(const float* imgs, int32_t N, int32_t H, int32_t W, const int32_t* box, const int32_t* box_first, int32_t n_docs,
+                         int32_t n_boxes, const int64_t* doc, const int32_t* strip_first, int32_t S, int32_t OH, int32_t OW, float* out,
+                         void* stream);
+int qea_doc_crops_scatter(const float* dout, int32_t S, int32_t OH, int32_t OW, const int32_t* box, const int32_t* box_first,
+                          int32_t n_docs, int32_t n_boxes, const int64_t* doc, const int32_t* strip_first, float* dimg, int32_t N, int32_t H,
+                          int32_t W, int32_t accumulate, void* stream);
+
 /* The two minibatch samplers that pick on per-strip estimates (--minibatch_subset rangeCER / uniformEntropy).
  *
  * qea_spread_pick — the range sampling of CerRangeSampler.query (selection_utils.py:129-134) and sampleUsingEstimates

@@ -15,6 +15,17 @@ has BEFORE the pad (the decode and the thumbnail stay in PIL, so the pixels are 
   ResidentStrips.load_or_build(dataset, size, pack_path)   the same through one .npz pack file with a signature of the file list
   ResidentLoader      a torch DataLoader over the INDICES (same sampler arguments, so the same batches, order and RNG draws as the
                       loader it replaces) whose batches come out as (images on the device, labels, names[, indices])
+
+The same for the document flow (--resident of patch_cli.py), whose sample path also re-reads and re-parses every document's .json:
+
+  ResidentDocuments(dataset, device)      a PatchDataset's documents as the dataset has them before its white pad (pixels / offset /
+                                          h / w as above) and, per document, the box dicts of the dataset's own coord_loader; box
+                                          int32 [total][4] (clipped to the canvas) and box_first int32 [n+1] on the device
+      .batch(rows)                        fp32 [N,1,400,512] = torch.stack([dataset[i][0] for i in rows]): qea_strip_batch again
+      .crops(images, rows, oh, ow)        ALL boxes of those documents cut out of `images` and centred on white: one launch forward
+                                          and one order-fixed launch without atomics backward (csrc/doc_crops.hip); numpy on the host
+  ResidentDocuments.load_or_build         the pack file; its signature also covers every .json
+  ResidentDocLoader                       the index DataLoader again; yields [images, DocBoxes (box lists that name store and rows), paths]
 """
 import hashlib
 import json
@@ -278,3 +289,326 @@ def resident_loader(dataset, size, device, pack_path=None, max_gb=8.0, what="dat
             raise QeaError(f"--resident: the {what}'s transform does not give PadWhite(({store.H}, {store.W})) followed by float32 / 255 "
                            f"(sample {i} differs from the resident batch); the store would train on other pixels")
     return ResidentLoader(dataset, store, **loader_kw)
+
+
+# ----------------------------------------------------------------------------- documents (patch_cli.py --resident)
+DOC_PACK_FORMAT = 1
+
+
+def _doc_geometry(dataset, path, w, h):
+    """PatchDataset.__getitem__'s (top, left, sx, sy) of a w x h document and the branch it takes: "fit", "cut" (oversize in one
+    dimension: ImageOps.expand with a negative border keeps the central pixels) or "resize"."""
+    H, W = dataset.size
+    if h <= H or w <= W:
+        return (H - h) // 2, (W - w) // 2, 1, 1, "cut" if (h > H or w > W) else "fit"
+    if dataset.resize_images:
+        return 0, 0, W / w, H / h, "resize"
+    raise QeaError(f"--resident: {path} is {h}x{w}, larger than the {H}x{W} canvas in both dimensions, and the dataset does not resize: "
+                   "its sample is an unpadded image that no batch can hold")
+
+
+def _decode_doc(dataset, path):
+    """The dataset's decode of one document up to, not including, the white pad -> (uint8 [h', w'], source (h, w))."""
+    H, W = dataset.size
+    image = Image.open(path).convert("L")
+    w, h = image.size
+    top, left, _, _, how = _doc_geometry(dataset, path, w, h)
+    if how == "resize":
+        return np.asarray(image.resize((W, H), Image.BILINEAR), dtype=np.uint8), (h, w)
+    a = np.asarray(image, dtype=np.uint8)
+    if how == "cut":                                  # the slice a negative border leaves: source rows -top .. -top+H-1 (columns alike)
+        y0, x0 = max(0, -top), max(0, -left)
+        a = a[y0:y0 + H, x0:x0 + W]
+    return np.ascontiguousarray(a), (h, w)
+
+
+def _doc_signature(dataset):
+    """_signature's rows of every image AND of its .json, with the canvas and the dataset's resize flag."""
+    files = list(dataset.files)
+    root = os.path.commonpath([os.path.dirname(os.path.abspath(f)) for f in files]) if files else ""
+    rows = []
+    for f in files:
+        for g in (f, f.rsplit(".", 1)[0] + ".json"):
+            st = os.stat(g)
+            rows.append([os.path.relpath(os.path.abspath(g), root), st.st_size, st.st_mtime_ns])
+    return hashlib.sha256(json.dumps({"format": DOC_PACK_FORMAT, "size": list(dataset.size), "resize": bool(dataset.resize_images),
+                                      "files": rows}).encode()).hexdigest()
+
+
+class DocBoxes(list):
+    """The box lists of a batch of documents (what PatchDataset.collate yields as its second entry) that also says where they came
+    from: `store` (a ResidentDocuments) and `rows` (the store row of each document), so utils.get_text_stacks can cut all their strips
+    from the store's device tables.  Indexing and iterating it give the plain lists."""
+
+    def __init__(self, lists, store, rows):
+        super().__init__(lists)
+        self.store, self.rows = store, [int(r) for r in rows]
+
+
+class ResidentDocuments:
+    """Every document of a PatchDataset (pad=True) decoded ONCE: pixels as the dataset has them before the white pad, boxes as its
+    coord_loader returns them.  batch(rows) is torch.stack([dataset[i][0] for i in rows]) bit for bit; crops(images, rows, oh, ow)
+    cuts all boxes of those documents out of `images`.  device="cpu": numpy tables and the numpy specification of both."""
+
+    def __init__(self, dataset, device="cpu", max_gb=8.0, _packed=None):
+        from datasets.patch_dataset import PatchDataset
+        if not isinstance(dataset, PatchDataset):
+            raise QeaError(f"ResidentDocuments packs a PatchDataset, not a {type(dataset).__name__}")
+        if not dataset.pad:
+            raise QeaError("ResidentDocuments needs a PatchDataset with pad=True: unpadded documents have no common canvas")
+        self.dataset = dataset
+        self.H, self.W = dataset.size
+        self.device = torch.device(device)
+        if self.device.type not in ("cpu", "cuda"):
+            raise QeaError(f"ResidentDocuments: device {device!r} is neither cpu nor cuda")
+        self.max_gb = float(max_gb)
+        self.paths = list(dataset.files)
+        self.n = len(self.paths)
+        if not self.n:
+            raise QeaError("ResidentDocuments: the dataset lists no document")
+        t0 = time.perf_counter()
+        if _packed is None:
+            pixels, offset, h, w, src = self._pack()
+        else:
+            pixels, offset, h, w, src = _packed
+            self._guard(pixels.size)
+        self.nbytes = int(pixels.size)
+        self._host = (pixels, offset, h, w, src)                              # what a pack file holds
+        self.boxes, self.branch = [], []
+        for f, (sh, sw) in zip(self.paths, src.tolist()):
+            top, left, sx, sy, how = _doc_geometry(dataset, f, sw, sh)
+            self.boxes.append(dataset.coord_loader(f, top, left, sx, sy))     # filtering, shifting and the placeholder stay the dataset's
+            self.branch.append(how)
+        self.n_boxes = np.array([len(b) for b in self.boxes], dtype=np.int32)
+        box_first = np.zeros(self.n + 1, dtype=np.int32)
+        np.cumsum(self.n_boxes, out=box_first[1:])
+        # get_text_stack's clipping of its CUDA branch
+        box = np.array([[max(0, b["x_min"]), max(0, b["y_min"]), min(self.W, b["x_max"]), min(self.H, b["y_max"])]
+                        for boxes in self.boxes for b in boxes], dtype=np.int32).reshape(-1, 4)
+        self.build_seconds = time.perf_counter() - t0
+        table = norm_table()
+        if self.device.type == "cuda":
+            from qea import _lib
+            _lib.lib()                                                        # a missing kernel is an error here, not at the first batch
+            up = lambda a: torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(self.device)
+            self.pixels, self.offset, self.h, self.w, self.table = up(pixels), up(offset), up(h), up(w), up(table)
+            self.box, self.box_first = up(box), up(box_first)
+        else:
+            self.pixels, self.offset, self.h, self.w, self.table, self.box, self.box_first = pixels, offset, h, w, table, box, box_first
+        self._host_box, self._host_box_first = box, box_first
+        self._self_check()
+
+    def __len__(self):
+        return self.n
+
+    _guard = ResidentStrips._guard
+
+    def _pack(self):
+        chunks, total = [], 0
+        offset = np.zeros(self.n, dtype=np.int64)
+        h = np.zeros(self.n, dtype=np.int32)
+        w = np.zeros(self.n, dtype=np.int32)
+        src = np.zeros((self.n, 2), dtype=np.int32)
+        for i, f in enumerate(self.paths):
+            a, src[i] = _decode_doc(self.dataset, f)
+            offset[i], h[i], w[i] = total, a.shape[0], a.shape[1]
+            chunks.append(a.reshape(-1))
+            total += a.size
+            self._guard(total)                                                # refuse as soon as the limit is passed, not after the decode
+        return np.concatenate(chunks), offset, h, w, src
+
+    def _self_check(self):
+        """The store against the dataset's own samples: the first and the last document and every one stored through an oversize
+        branch (the cut and the resize are re-done here, not taken from PIL's pad)."""
+        rows = sorted({0, self.n - 1} | {i for i, how in enumerate(self.branch) if how != "fit"})
+        for i in rows:
+            sample = self.dataset[i]
+            ours = self.batch([i])[0].cpu()
+            if not torch.is_tensor(sample[0]) or sample[0].shape != ours.shape or not torch.equal(sample[0], ours):
+                raise QeaError(f"--resident: document {self.paths[i]} comes out of the store with other pixels than out of the dataset")
+            if sample[1] != self.boxes[i]:
+                raise QeaError(f"--resident: document {self.paths[i]} comes out of the store with other boxes than out of the dataset")
+
+    # ---- the pack file ----
+    @classmethod
+    def load_or_build(cls, dataset, pack_path, device="cpu", max_gb=8.0):
+        """The store of `dataset` through the pack file at `pack_path` (.npz: pixels, offset, h, w, src, paths, signature).  A pack
+        whose signature is not this dataset's (an image or a .json added, removed, resized or rewritten, another canvas or format) is
+        never used: the store is rebuilt from the files and the pack overwritten.  Boxes are not packed: they are read from the
+        .json files by the dataset's coord_loader either way."""
+        sig = _doc_signature(dataset)
+        packed = None
+        if pack_path and os.path.exists(pack_path):
+            try:
+                with np.load(pack_path, allow_pickle=False) as z:
+                    if str(z["signature"]) == sig and len(z["offset"]) == len(dataset.files):
+                        packed = (z["pixels"], z["offset"], z["h"], z["w"], z["src"])
+            except (OSError, ValueError, KeyError):
+                packed = None                                                 # unreadable or foreign file: rebuild
+        store = cls(dataset, device=device, max_gb=max_gb, _packed=packed)
+        store.from_pack = packed is not None
+        if packed is None and pack_path:
+            store.save(pack_path, sig)
+        return store
+
+    def save(self, pack_path, signature=None):
+        pixels, offset, h, w, src = self._host
+        tmp = f"{pack_path}.tmp{os.getpid()}"
+        os.makedirs(os.path.dirname(os.path.abspath(pack_path)), exist_ok=True)
+        with open(tmp, "wb") as f:
+            np.savez(f, pixels=pixels, offset=offset, h=h, w=w, src=src, paths=np.array(self.paths, dtype=str),
+                     signature=np.array(signature or ""), size=np.array([self.H, self.W], dtype=np.int32))
+        os.replace(tmp, pack_path)
+
+    # ---- batches ----
+    def _rows(self, rows, what):
+        if isinstance(rows, torch.Tensor):
+            rows = rows.cpu().numpy()
+        rows = np.ascontiguousarray(np.asarray(list(rows) if not isinstance(rows, np.ndarray) else rows).reshape(-1)).astype(np.int64, copy=False)
+        if rows.size == 0:
+            raise ValueError(f"ResidentDocuments.{what}: no rows")
+        if int(rows.min()) < 0 or int(rows.max()) >= self.n:
+            raise ValueError(f"ResidentDocuments.{what}: rows {int(rows.min())}..{int(rows.max())} outside 0..{self.n - 1}")
+        return rows
+
+    def batch(self, rows):
+        """fp32 [N,1,H,W] on the store's device: documents `rows` centred on the white canvas, the dataset's own samples bit for bit.
+        On the device one launch of qea_strip_batch (OH = H, OW = W, centre anchor)."""
+        rows = self._rows(rows, "batch")
+        shape = (rows.size, 1, self.H, self.W)
+        if self.device.type == "cuda":
+            from qea import ops
+            pinned = torch.empty(rows.size, dtype=torch.int64, pin_memory=True)   # a fresh block per call, see ResidentStrips.batch
+            pinned.numpy()[:] = rows
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            ops.strip_batch(self.pixels, self.offset, self.h, self.w, pinned.to(self.device, non_blocking=True), self.table, out, "centre")
+            return out
+        res = np.ones(shape, dtype=np.float32)
+        for b, s in enumerate(rows):
+            h, w = int(self.h[s]), int(self.w[s])
+            top, left = (self.H - h) // 2, (self.W - w) // 2
+            res[b, 0, top:top + h, left:left + w] = self.table[self.pixels[self.offset[s]: self.offset[s] + h * w].reshape(h, w)]
+        return torch.from_numpy(res)
+
+    def strip_tables(self, rows):
+        """(doc int64 [N], strip_first int32 [N+1]) of a step on documents `rows`, as host arrays."""
+        rows = self._rows(rows, "crops")
+        first = np.zeros(rows.size + 1, dtype=np.int32)
+        np.cumsum(self.n_boxes[rows], out=first[1:])
+        return rows, first
+
+    def labels(self, rows):
+        """[[label of every box] per document]: the second result of get_text_stack, per document."""
+        return [[b["label"] for b in self.boxes[int(r)]] for r in rows]
+
+    def crops(self, images, rows, oh, ow):
+        """All boxes of documents `rows` cut out of images [N,1,H,W] (image n = document rows[n]) and centred on white oh x ow:
+        [S,1,oh,ow], document after document, box after box; differentiable in `images`.  Device store: one launch forward
+        (qea_doc_crops_gather) and one backward (qea_doc_crops_scatter, no atomics).  Host store: the numpy specification."""
+        doc, first = self.strip_tables(rows)
+        if images.dim() != 4 or images.shape[0] != doc.size or tuple(images.shape[1:]) != (1, self.H, self.W):
+            raise ValueError(f"ResidentDocuments.crops: images {tuple(images.shape)} for {doc.size} documents on a {self.H}x{self.W} canvas")
+        if ow < 4 or ow % 4:
+            raise ValueError(f"ResidentDocuments.crops: ow={ow} must be a positive multiple of 4")
+        if self.device.type == "cuda":
+            if not images.is_cuda:
+                raise ValueError("ResidentDocuments.crops: a device store cuts device images")
+            # doc and strip_first in ONE pinned block and one non-blocking copy (fresh per call, see ResidentStrips.batch)
+            N = doc.size
+            pinned = torch.empty(8 * N + 4 * (N + 1), dtype=torch.uint8, pin_memory=True)
+            pinned[:8 * N].view(torch.int64).numpy()[:] = doc
+            pinned[8 * N:].view(torch.int32).numpy()[:] = first
+            dev = pinned.to(images.device, non_blocking=True)
+            from utils import _DocCrops
+            return _DocCrops.apply(images, self, dev[:8 * N].view(torch.int64), dev[8 * N:].view(torch.int32), int(first[-1]), int(oh), int(ow))
+        if images.is_cuda:
+            raise ValueError("ResidentDocuments.crops: a host store cuts host images")
+        return _DocCropsHost.apply(images, self._host_box, self._host_box_first, doc, first, int(oh), int(ow))
+
+
+def doc_crops_spec(imgs, box, box_first, doc, first, oh, ow):
+    """numpy specification of qea_doc_crops_gather: imgs fp32 [N,H,W] -> [S,oh,ow]."""
+    N, H, W = imgs.shape
+    out = np.ones((int(first[-1]), oh, ow), dtype=np.float32)
+    for n in range(N):
+        for j in range(int(first[n + 1] - first[n])):
+            x0, y0, x1, y1 = (int(v) for v in box[box_first[doc[n]] + j])
+            x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, W), min(y1, H)
+            cw, ch = x1 - x0, y1 - y0
+            left, top = (ow - cw) // 2, (oh - ch) // 2
+            for oy in range(max(0, top), min(oh, top + ch)):
+                a, b = max(0, left), min(ow, left + cw)
+                if b > a:
+                    out[first[n] + j, oy, a:b] = imgs[n, y0 + oy - top, x0 + a - left: x0 + b - left]
+    return out
+
+
+def doc_crops_backward_spec(dout, box, box_first, doc, first, H, W, dimg=None):
+    """numpy specification of qea_doc_crops_scatter: dout fp32 [S,oh,ow] -> [N,H,W]; every pixel is the fp32 sum, in ascending box
+    order from 0, of the dout elements that read it, added to `dimg` when that is given (accumulate)."""
+    S, oh, ow = dout.shape
+    N = len(doc)
+    acc = np.zeros((N, H, W), dtype=np.float32)
+    for n in range(N):
+        for j in range(int(first[n + 1] - first[n])):
+            x0, y0, x1, y1 = (int(v) for v in box[box_first[doc[n]] + j])
+            x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, W), min(y1, H)
+            cw, ch = x1 - x0, y1 - y0
+            left, top = (ow - cw) // 2, (oh - ch) // 2
+            a, b = max(0, left), min(ow, left + cw)
+            for oy in range(max(0, top), min(oh, top + ch)):
+                if b > a:
+                    acc[n, y0 + oy - top, x0 + a - left: x0 + b - left] += dout[first[n] + j, oy, a:b]
+    return acc if dimg is None else (dimg + acc).astype(np.float32)
+
+
+class _DocCropsHost(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, images, box, box_first, doc, first, oh, ow):
+        ctx.tables = (box, box_first, doc, first, images.shape)
+        return torch.from_numpy(doc_crops_spec(images.detach().numpy()[:, 0], box, box_first, doc, first, oh, ow))[:, None]
+
+    @staticmethod
+    def backward(ctx, dout):
+        box, box_first, doc, first, shape = ctx.tables
+        d = doc_crops_backward_spec(dout.contiguous().numpy()[:, 0], box, box_first, doc, first, shape[2], shape[3])
+        return torch.from_numpy(d)[:, None], None, None, None, None, None, None
+
+
+class ResidentDocLoader:
+    """The DataLoader of a PatchDataset whose documents sit in `store`, with the sampling left to torch (see ResidentLoader): a
+    DataLoader over the indices with the caller's batch_size / drop_last / sampler / shuffle draws the same index batches, in the same
+    order and with the same use of the global generator, as DataLoader(dataset, collate_fn=PatchDataset.collate, ...).  Each batch is
+    [images on the store's device, DocBoxes (the box lists, with the store and the rows), paths (if include_name)]."""
+
+    def __init__(self, dataset, store, **loader_kw):
+        if store.dataset is not dataset and list(dataset.files) != store.paths:
+            raise QeaError("ResidentDocLoader: the store was not built from this dataset")
+        if loader_kw.get("num_workers") or "collate_fn" in loader_kw or "batch_sampler" in loader_kw:
+            raise QeaError("ResidentDocLoader takes batch_size, drop_last and sampler or shuffle only")
+        self.dataset, self.store = dataset, store
+        self.include_name = dataset.include_name
+        self._indices = torch.utils.data.DataLoader(_Indices(len(dataset)), **loader_kw)
+        self.batch_size, self.sampler = self._indices.batch_size, self._indices.sampler
+
+    def __len__(self):
+        return len(self._indices)
+
+    def __iter__(self):
+        for indices in self._indices:
+            rows = indices.numpy().reshape(-1)
+            out = [self.store.batch(rows), DocBoxes([self.store.boxes[i] for i in rows], self.store, rows)]
+            if self.include_name:
+                out.append([self.store.paths[i] for i in rows])
+            yield out
+
+
+def resident_documents(dataset, device, pack_path=None, max_gb=8.0, what="dataset"):
+    """--resident of patch_cli.py: the ResidentDocuments of `dataset` (through the pack file when one is named).  The store checks
+    itself against the dataset's own samples at construction.  Refuses what has no resident form."""
+    from datasets.patch_dataset import PatchDataset
+    if not isinstance(dataset, PatchDataset):
+        raise QeaError(f"--resident needs a PatchDataset as {what}, not a {type(dataset).__name__}")
+    if pack_path:
+        return ResidentDocuments.load_or_build(dataset, pack_path, device=device, max_gb=max_gb)
+    return ResidentDocuments(dataset, device=device, max_gb=max_gb)

@@ -74,6 +74,14 @@ FLAGS = [
     ("--resident_pack", dict(help="[new] --resident: keep the decoded strips in this .npz pack file (the validation set's in PATH with "
                                   "'.val' before the extension) and reuse it while the files' names, sizes and mtimes are unchanged"), "a"),
     ("--resident_max_gb", dict(type=float, default=8, help="[new] --resident: refuse a pack larger than this many GB"), "a"),
+    ("--resident", dict(action="store_true", help="[new] decode every document of the training and validation PatchDatasets once, keep the 8-bit pixels "
+                                                  "and the word boxes on the device, build each batch of documents by one launch and cut all strips of a "
+                                                  "step by one launch (datasets/resident.py) instead of the per-document PIL / json / host-to-device "
+                                                  "path; same batches, same order, same values.  The store reproduces PatchDataset's white 400x512 "
+                                                  "canvas + float32 / 255 only: any other training set is refused"), "p"),
+    ("--resident_pack", dict(help="[new] --resident: keep the decoded documents in this .npz pack file (the validation set's in PATH with "
+                                  "'.val' before the extension) and reuse it while the files' names, sizes and mtimes are unchanged"), "p"),
+    ("--resident_max_gb", dict(type=float, default=8, help="[new] --resident: refuse a pack larger than this many GB"), "p"),
 ]
 
 # the warm-up and evaluation drivers: "c" = train_crnn.py (:217-275), "e" = eval_crnn.py, "v" = eval_prep.py (their __main__ blocks).

@@ -970,6 +970,54 @@ def strip_batch(pixels, offset, h, w, idx, table, out, anchor="centre"):
     STRIP_LAUNCHES["batch"] += 1
 
 
+DOC_LAUNCHES = {"gather": 0, "scatter": 0}    # launches of csrc/doc_crops.hip issued through this module (tests, tools)
+
+
+def _doc_tables(who, box, box_first, doc, strip_first, imgs, strips):
+    """The argument checks the two entry points of csrc/doc_crops.hip share; -> (N, H, W, n_docs, n_boxes, S, OH, OW)."""
+    tensors = (box, box_first, doc, strip_first, imgs, strips)
+    if (box.dtype != torch.int32 or box_first.dtype != torch.int32 or doc.dtype != torch.int64 or strip_first.dtype != torch.int32
+            or imgs.dtype != torch.float32 or strips.dtype != torch.float32):
+        raise _lib.QeaError(f"{who} needs int32 boxes, box_first and strip_first, int64 doc, fp32 images and strips")
+    if not all(t.is_cuda and t.device == imgs.device for t in tensors):
+        raise _lib.QeaError(f"{who} needs all its tensors on one CUDA device")
+    if not all(t.is_contiguous() for t in tensors):
+        raise _lib.QeaError(f"{who} needs contiguous tensors")
+    if imgs.dim() == 4 and imgs.shape[1] == 1:
+        N, _, H, W = imgs.shape
+    elif imgs.dim() == 3:
+        N, H, W = imgs.shape
+    else:
+        raise _lib.QeaError(f"{who}: images {tuple(imgs.shape)} are neither [N,1,H,W] nor [N,H,W]")
+    if strips.dim() != 4 or strips.shape[1] != 1:
+        raise _lib.QeaError(f"{who}: strips {tuple(strips.shape)} are not [S,1,OH,OW]")
+    S, _, OH, OW = strips.shape
+    n_docs = box_first.numel() - 1
+    if box.dim() != 2 or box.shape[1] != 4 or n_docs < 1 or doc.numel() != N or strip_first.numel() != N + 1:
+        raise _lib.QeaError(f"{who}: boxes {tuple(box.shape)}, {box_first.numel()} box_first, {doc.numel()} doc and {strip_first.numel()} "
+                            f"strip_first entries for {N} images")
+    return N, H, W, n_docs, box.shape[0], S, OH, OW
+
+
+def doc_crops_gather(imgs, box, box_first, doc, strip_first, out):
+    """include/qea_hip.h: qea_doc_crops_gather — imgs [N,1,H,W] fp32, the store's box / box_first, doc (int64 [N]) and strip_first
+    (int32 [N+1]) -> out [S,1,OH,OW], every strip of the step, written whole by ONE launch on the current stream."""
+    N, H, W, n_docs, n_boxes, S, OH, OW = _doc_tables("doc_crops_gather", box, box_first, doc, strip_first, imgs, out)
+    _lib.check(_lib.lib().qea_doc_crops_gather(_ptr(imgs), N, H, W, _ptr(box), _ptr(box_first), n_docs, n_boxes, _ptr(doc), _ptr(strip_first),
+                                               S, OH, OW, _ptr(out), _stream()), "qea_doc_crops_gather")
+    DOC_LAUNCHES["gather"] += 1
+
+
+def doc_crops_scatter(dout, box, box_first, doc, strip_first, dimg, accumulate=False):
+    """include/qea_hip.h: qea_doc_crops_scatter — dout [S,1,OH,OW] -> dimg [N,1,H,W], written whole (or added to, `accumulate`) by ONE
+    launch without atomics: per pixel the sum over the covering boxes in ascending box order."""
+    N, H, W, n_docs, n_boxes, S, OH, OW = _doc_tables("doc_crops_scatter", box, box_first, doc, strip_first, dimg, dout)
+    _lib.check(_lib.lib().qea_doc_crops_scatter(_ptr(dout), S, OH, OW, _ptr(box), _ptr(box_first), n_docs, n_boxes, _ptr(doc),
+                                                _ptr(strip_first), _ptr(dimg), N, H, W, int(bool(accumulate)), _stream()),
+               "qea_doc_crops_scatter")
+    DOC_LAUNCHES["scatter"] += 1
+
+
 SPREAD_WAVE_MAX_N, SPREAD_LDS4_MAX_N, SPREAD_LDS_MAX_N, SPREAD_MAX_N = 1536, 24576, 32768, 1 << 24    # QEA_SPREAD_* of include/qea_hip.h
 SAMPLER_LAUNCHES = {"spread": 0, "entropy": 0}    # launches of csrc/sampling.hip issued through this module (tests, tools)
 ENTROPY_NUM_CLASSES = 95                          # calc_entropy's constant (selection_utils.py:10), whatever the width of the scores

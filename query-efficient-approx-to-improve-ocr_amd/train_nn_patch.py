@@ -10,6 +10,10 @@ with a scatter-add backward) before the CRNN; the loader batch is one document.
            [all-reduce CRNN grads]; Adam(CRNN)
   Phase B per document: UNet(train) -> crops -> CRNN(BN eval) -> CTC(GT) + scalar*MSE(document, 1) ->
            backward; [all-reduce UNet (+CRNN if --update_CRNN) grads]; Adam
+
+[new] --resident: PatchDataset training and validation sets are decoded once and kept on the device with their word boxes; the loader
+keeps torch's sampling and builds every batch of documents in one launch, and all strips of a cleaner output are cut in one launch
+(datasets/resident.py, utils.get_text_stacks) — same batches, order, RNG draws and values.
 """
 import os
 
@@ -20,7 +24,7 @@ from qea import dist as qdist
 from qea.trainer_core import TrainerCore
 from tracking_utils import add_labels_to_history, call_crnn, generate_ctc_target_batches, weighted_ctc_loss
 from transform_helper import AddGaussianNoice
-from utils import compare_labels, get_pruning_sampler, get_text_stack, handle_optuna_trial, pred_to_string, save_img
+from utils import compare_labels, get_pruning_sampler, get_text_stack, get_text_stacks, handle_optuna_trial, pred_to_string, save_img
 
 
 class TrainNNPrep(TrainerCore):
@@ -53,12 +57,39 @@ class TrainNNPrep(TrainerCore):
         idx = qdist.equal_shards(idx, self.batch_size)          # data parallel: the same number of steps on every rank
         self._train_idx = idx
         self._collate = collate
-        self.loader_train = torch.utils.data.DataLoader(train_set, batch_size=self.batch_size, drop_last=True, collate_fn=collate,
-                                                        sampler=torch.utils.data.SubsetRandomSampler(idx))
+        self.store_train = self.store_val = None
+        if getattr(args, "resident", False):
+            # [new] --resident: the documents decoded once and kept on the device with their boxes, the same index batches (under data
+            # parallelism every rank packs the whole set and takes its own indices)
+            from qea._lib import QeaError
+            if getattr(args, "synthetic_size", None):
+                raise QeaError("--resident keeps PatchDataset documents on the device: it does not go with --synthetic_size")
+            from datasets.resident import resident_args, resident_documents
+            self.store_train = resident_documents(train_set, self.device, what="training set", **resident_args(args, "training set"))
+            self.store_val = resident_documents(val_set, self.device, what="validation set", **resident_args(args, "validation set"))
+        self.loader_train = self._loader(idx)
         self.train_set_size, self.val_set_size = len(idx), len(val_set)
         self.num_subset_images = int(args.image_prop * self.train_set_size) if args.image_prop else None
         if self.cers:
             self.all_cers = {name: [] for name in self.cers}
+
+    def _loader(self, idx):
+        kw = dict(batch_size=self.batch_size, drop_last=True, sampler=torch.utils.data.SubsetRandomSampler(idx))
+        if self.store_train is None:
+            return torch.utils.data.DataLoader(self.dataset, collate_fn=self._collate, **kw)
+        from datasets.resident import ResidentDocLoader
+        return ResidentDocLoader(self.dataset, self.store_train, **kw)
+
+    def _cut(self, outs, box_lists):
+        """([(crops, labels)] per document, the crops of all documents as one tensor) of the cleaner outputs `outs` [N,1,H,W].  Box
+        lists of a resident store: ALL strips in one launch (and one for their gradient), split per document; else get_text_stack
+        per document, concatenated."""
+        crops, labels = get_text_stacks(outs, box_lists, self.input_size)
+        res, a = [], 0
+        for names in labels:
+            res.append((crops[a:a + len(names)], names))
+            a += len(names)
+        return res, crops
 
     def _default_datasets(self, args):
         n = getattr(args, "synthetic_size", None)
@@ -86,8 +117,7 @@ class TrainNNPrep(TrainerCore):
                 # a fresh subset of THIS rank's documents per epoch (train_nn_patch.py:209-218); the draw is rank-identical
                 # and every shard has the same length, so the step counts stay equal
                 sub = self._train_idx[torch.randperm(self.train_set_size)[: self.num_subset_images]]
-                self.loader_train = torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size, drop_last=True, collate_fn=self._collate,
-                                                                sampler=torch.utils.data.SubsetRandomSampler(sub))
+                self.loader_train = self._loader(sub)
             for images, labels_dicts, names in self.loader_train:
                 # ---------------- Phase A ----------------
                 self._set_phase_a()
@@ -95,7 +125,8 @@ class TrainNNPrep(TrainerCore):
                 n_docs = len(labels_dicts)
                 X_all = (images if torch.is_tensor(images) else torch.stack(list(images))).to(self.device)
                 with torch.no_grad():                            # eval-mode BatchNorm: a document's output does not depend on its batch
-                    preds_all = self.prep_model(X_all) if n_docs > 1 else None
+                    preds_all = self.prep_model(X_all) if (n_docs > 1 or self.store_train is not None) else None
+                    cuts_a = self._cut(preds_all, labels_dicts)[0] if self.store_train is not None else None
                 # [new] the CRNN side of Phase A for the N documents in one pass (ragged BatchNorm groups) where nothing per document has to
                 # happen in between: HIP path, more than one replica, no label-history pass (--inner_limit_skip runs per document)
                 batched_a = (n_docs > 1 and self.backend.gpu_jitter and self.inner_limit > 1 and not self.inner_limit_skip
@@ -103,8 +134,11 @@ class TrainNNPrep(TrainerCore):
                 pending = []
                 for i in range(n_docs):
                     with torch.no_grad():
-                        pred = preds_all[i] if preds_all is not None else self.prep_model(X_all[i:i + 1])[0]
-                        crops_all, labels = get_text_stack(pred, labels_dicts[i], self.input_size)
+                        if cuts_a is not None:                   # [new] --resident: cut above, all documents in one launch
+                            crops_all, labels = cuts_a[i]
+                        else:
+                            pred = preds_all[i] if preds_all is not None else self.prep_model(X_all[i:i + 1])[0]
+                            crops_all, labels = get_text_stack(pred, labels_dicts[i], self.input_size)
                     n_strips = crops_all.shape[0]
                     strip_names = self._strip_names(labels, names[i])
                     local = self.selection_method and epoch >= self.warmup_epochs and "global" not in self.selection_method
@@ -167,8 +201,11 @@ class TrainNNPrep(TrainerCore):
                     # values of N sequential passes), ONE CRNN pass over all their strips (BatchNorm in eval mode: batch-independent);
                     # the N per-document losses of :327-328 are summed and back-propagated once = the accumulated gradients of :329
                     img_all = self.prep_model(X_all, bn_groups=n_docs)
-                    stacks = [get_text_stack(img_all[i], labels_dicts[i], self.input_size) for i in range(n_docs)]
-                    crops = torch.cat([c for c, _ in stacks])
+                    if self.store_train is not None:             # [new] --resident: one launch, and one for the gradient
+                        stacks, crops = self._cut(img_all, labels_dicts)
+                    else:
+                        stacks = [get_text_stack(img_all[i], labels_dicts[i], self.input_size) for i in range(n_docs)]
+                        crops = torch.cat([c for c, _ in stacks])
                     scores = self.crnn_model(crops)
                     total, a = None, 0
                     for i, (c, labels) in enumerate(stacks):
@@ -188,8 +225,12 @@ class TrainNNPrep(TrainerCore):
                         a = b
                     total.backward()
                 else:
-                    img_out = self.prep_model(X_all)[0]
-                    crops, labels = get_text_stack(img_out, labels_dicts[0], self.input_size)
+                    img_all = self.prep_model(X_all)
+                    img_out = img_all[0]
+                    if self.store_train is not None:             # [new] --resident
+                        (crops, labels), = self._cut(img_all, labels_dicts)[0]
+                    else:
+                        crops, labels = get_text_stack(img_out, labels_dicts[0], self.input_size)
                     scores, y, pred_size, y_size = self._call_model(crops, labels)
                     loss = self._get_loss(scores, y, pred_size, y_size, img_out)
                     loss.backward()
@@ -220,12 +261,20 @@ class TrainNNPrep(TrainerCore):
         val_loss, n_strips, last = 0.0, 0, None
         with torch.no_grad():
             for k in range(len(self.validation_set)):
-                item = self.validation_set[k]
-                image, boxes = item[0], item[1]
-                if not boxes:
-                    continue
-                img_out = self.prep_model(image.unsqueeze(0).to(self.device))[0]
-                crops, labels = get_text_stack(img_out, boxes, self.input_size)
+                if self.store_val is not None:                   # [new] --resident: the stored document and boxes, one launch each
+                    from datasets.resident import DocBoxes
+                    if not self.store_val.boxes[k]:
+                        continue
+                    img_all = self.prep_model(self.store_val.batch([k]))
+                    img_out = img_all[0]
+                    (crops, labels), = self._cut(img_all, DocBoxes([self.store_val.boxes[k]], self.store_val, [k]))[0]
+                else:
+                    item = self.validation_set[k]
+                    image, boxes = item[0], item[1]
+                    if not boxes:
+                        continue
+                    img_out = self.prep_model(image.unsqueeze(0).to(self.device))[0]
+                    crops, labels = get_text_stack(img_out, boxes, self.input_size)
                 scores, y, pred_size, y_size = self._call_model(crops, labels)
                 val_loss += self._get_loss(scores, y, pred_size, y_size, img_out).item()
                 preds = pred_to_string(scores, labels, self.index_to_char)

@@ -131,6 +131,28 @@ class _CropPad(torch.autograd.Function):
         return dimg, None, None, None, None
 
 
+class _DocCrops(torch.autograd.Function):
+    """[new] All strips of a step out of a device-resident document store (datasets.resident.ResidentDocuments.crops): one launch
+    forward, one order-fixed launch without atomics backward (csrc/doc_crops.hip)."""
+
+    @staticmethod
+    def forward(ctx, images, store, doc, strip_first, S, oh, ow):
+        from qea import ops
+        out = torch.empty(S, 1, oh, ow, dtype=torch.float32, device=images.device)
+        ops.doc_crops_gather(images.contiguous(), store.box, store.box_first, doc, strip_first, out)
+        ctx.save_for_backward(doc, strip_first)
+        ctx.store, ctx.shape = store, tuple(images.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from qea import ops
+        doc, strip_first = ctx.saved_tensors
+        dimg = torch.empty(ctx.shape, dtype=torch.float32, device=dout.device)      # written whole by the launch: no fill
+        ops.doc_crops_scatter(dout.contiguous(), ctx.store.box, ctx.store.box_first, doc, strip_first, dimg)
+        return dimg, None, None, None, None, None, None
+
+
 def padder(crop, h, w):
     _, c_h, c_w = crop.shape
     left, top = (w - c_w) // 2, (h - c_h) // 2
@@ -148,6 +170,19 @@ def get_text_stack(image, labels, input_size):
         return _CropPad.apply(image, boxes.to(image.device), len(labels), input_size[0], input_size[1]), names
     crops = [padder(image[:, l["y_min"]:l["y_max"], l["x_min"]:l["x_max"]], *input_size) for l in labels]
     return torch.stack(crops), names
+
+
+def get_text_stacks(images, box_lists, input_size):
+    """[new] images [N,1,H,W], box_lists: one list of box dicts per document -> (crops [S,1,h,w] of all documents, document after
+    document, [labels per document]).  Box lists that come from a device-resident document store (datasets.resident.DocBoxes) and CUDA
+    images: ONE launch for all strips, and one order-fixed launch for their gradient.  Anything else: get_text_stack per document."""
+    store = getattr(box_lists, "store", None)
+    if images.dim() == 3:
+        images = images[:, None]
+    if store is not None and store.device.type == "cuda" and images.is_cuda:
+        return store.crops(images, box_lists.rows, input_size[0], input_size[1]), store.labels(box_lists.rows)
+    stacks = [get_text_stack(images[i], box_lists[i], input_size) for i in range(len(box_lists))]
+    return torch.cat([c for c, _ in stacks]), [names for _, names in stacks]
 
 
 # ----------------------------------------------------------------------------- OCR / dirs / json / seeds
