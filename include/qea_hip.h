@@ -418,6 +418,10 @@ int qea_lstm_seq_fwd(float* gates, float* c, float* y, const void* planes_fwd, c
                      void* workspace, float* y_absmax, void* stream);
 int qea_lstm_seq_bwd(float* gates, const float* c, const float* dy, const void* planes_bwd, const float* w_absmax, int32_t T,
                      int32_t B, void* workspace, float* dgates_absmax, void* stream);
+/* ABI v9 (additive).  The index of the uint32 word of `workspace` that a pass at B rows sets to 1 when one of its bounded spins ran
+ * out (backward != 0: qea_lstm_seq_bwd, else qea_lstm_seq_fwd; -1 for B <= 0).  The word lies in front of the exchange area, is
+ * zeroed by the pass itself and is valid once the pass has finished on its stream; the query dereferences nothing. */
+int qea_lstm_seq_timeout_index(int32_t B, int32_t backward);
 
 /* ABI v9 (additive).  Several derived weight forms in ONE launch (a model has ~110 of them per optimiser step, a few microseconds each):
  * kind 0 = qea_filter_flip_transpose (a, b, c, d = Co, Ci, KH, KW; amax unused), kind 1 = qea_pack_frag_planes_f16 (a, b = N, Cin),

@@ -614,7 +614,7 @@ int seq_launch(const char* what, SeqArgs& a, int B, void* ws, hipStream_t s, int
   a.sync = (unsigned*)ws;
   a.xch = (char*)ws + seq_sync_words(B, BWD) * 4;
   a.nrb = seq_nrb(B, BWD);
-  a.tmo_index = ng;
+  a.tmo_index = ng;                                  // == qea_lstm_seq_timeout_index(B, BWD)
   static int attr_rc = (int)hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   int rc = attr_rc;
   if (rc != (int)hipSuccess) {
@@ -639,6 +639,12 @@ extern "C" size_t qea_lstm_seq_workspace_bytes(int32_t B) {   // enough for eith
   if (B <= 0) return 0;
   const size_t f = seq_sync_words(B, false) * 4 + seq_xch_bytes(B, false), b = seq_sync_words(B, true) * 4 + seq_xch_bytes(B, true);
   return f > b ? f : b;
+}
+
+// word index (uint32) of the timeout flag inside the workspace of a pass at B rows: what seq_launch hands the kernel as tmo_index
+extern "C" int qea_lstm_seq_timeout_index(int32_t B, int32_t backward) {
+  if (B <= 0) return -1;
+  return seq_groups(B, backward != 0);
 }
 
 extern "C" int qea_lstm_seq_pack(const float* w_hh, void* planes_fwd, void* planes_bwd, const float* w_absmax, void* stream) {

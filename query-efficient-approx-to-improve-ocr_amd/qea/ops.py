@@ -761,8 +761,27 @@ def lstm_packs(whf, whr):
     return pf, pb, mode
 
 
-def _lstm_seq_ws(B, dev):
-    return torch.empty(_lib.lib().qea_lstm_seq_workspace_bytes(B), dtype=torch.uint8, device=dev)
+_LSTM_SEQ_LAST = {"fwd": None, "bwd": None}     # (workspace, B) of the most recent "seq" pass of each kind: see lstm_seq_timed_out
+
+
+def _lstm_seq_ws(B, dev, which):
+    ws = torch.empty(_lib.lib().qea_lstm_seq_workspace_bytes(B), dtype=torch.uint8, device=dev)
+    _LSTM_SEQ_LAST[which] = (ws, B)
+    return ws
+
+
+def lstm_seq_timed_out(which):
+    """True when a bounded spin of the most recent "seq" forward (which = "fwd") or backward ("bwd") ran out: the pass has then set
+    the timeout word of its workspace (qea_lstm_seq_timeout_index) and poisoned its outputs with NaN.  A SYNCHRONISING device-to-host
+    read of one word on the CURRENT stream (call it from the stream the pass ran on, or after that stream has been synchronised):
+    for tests and diagnosis, never called from the engines, and not capturable (do not call it while a stream is capturing; after a replay it reads the word of the captured pass only if that pass was the most recent one made).  The workspace
+    of the last pass of each kind stays allocated until the next one replaces it."""
+    last = _LSTM_SEQ_LAST[which]
+    if last is None:
+        raise _lib.QeaError(f"no \"seq\" {which} pass has run in this process")
+    ws, B = last
+    idx = _lib.lib().qea_lstm_seq_timeout_index(B, int(which == "bwd"))
+    return bool(ws.view(torch.int32)[idx].item() != 0)
 
 
 def lstm_layer_fwd_any(gates, c, y, pack, mode, T, B, y_amax=None):
@@ -772,7 +791,7 @@ def lstm_layer_fwd_any(gates, c, y, pack, mode, T, B, y_amax=None):
         print("lstm fwd", mode, T, B, flush=True)
     if mode == "seq":
         planes, am = pack
-        ws = _lstm_seq_ws(B, gates.device)
+        ws = _lstm_seq_ws(B, gates.device, "fwd")
         _lib.check(_lib.lib().qea_lstm_seq_fwd(_ptr(gates), _ptr(c), _ptr(y), _ptr(planes), _ptr(am), T, B, _ptr(ws), _ptr(y_amax), _stream()), "qea_lstm_seq_fwd")
         return y_amax is not None
     elif mode is True or mode == "bf3":
@@ -784,7 +803,7 @@ def lstm_layer_fwd_any(gates, c, y, pack, mode, T, B, y_amax=None):
 def lstm_layer_bwd_any(gates, c, dy, pack, mode, dc_scratch, T, B, g_amax=None):
     if mode == "seq":
         planes, am = pack
-        ws = _lstm_seq_ws(B, gates.device)
+        ws = _lstm_seq_ws(B, gates.device, "bwd")
         _lib.check(_lib.lib().qea_lstm_seq_bwd(_ptr(gates), _ptr(c), _ptr(dy), _ptr(planes), _ptr(am), T, B, _ptr(ws), _ptr(g_amax), _stream()), "qea_lstm_seq_bwd")
         return g_amax is not None
     elif mode is True or mode == "bf3":

@@ -268,3 +268,27 @@ def test_batchnorm_partition():
     for bad in (5, [3, 3], [4, 0, 3], [8, -1], 0, -2):           # not a multiple, another sum, a zero / negative size, groups < 1
         with pytest.raises(ValueError):
             partition(bad, 7)
+
+
+def test_lstm_seq_timeout_index_lies_in_front_of_the_exchange_area():
+    """qea_lstm_seq_timeout_index(B, backward) names the word a one-launch BiLSTM pass sets when a bounded spin runs out (read by
+    qea.ops.lstm_seq_timed_out).  The workspace is [arrival counter per group][the timeout word][padding to a multiple of 64 words]
+    [exchange area: parity 2 x direction 2 x row blocks of 32 (padded to the workgroup's rows) x bytes per row block]; a group is
+    (workgroup's row block, direction), the workgroup has 128 rows above 512 (forward) / 1024 (backward) rows and 32 up to there.
+    The index must be the group count of its own pass and lie below the 64-word-aligned start of the exchange area, and
+    qea_lstm_seq_workspace_bytes must hold the larger of the two passes' layouts: restated here from csrc/lstm_seq.hip."""
+    from qea import _lib
+    L = _lib.lib()
+    XRB = {0: 16 * 2048, 1: 64 * 2048 + 8 * 128}              # bytes of one row block: forward (h fragments) / backward (+ inverse scales)
+    for B in (1, 32, 33, 512, 513, 1024, 1025, 2048):
+        need = []
+        for bwd in (0, 1):
+            rows = 128 if B > (1024 if bwd else 512) else 32
+            groups = -(-B // rows) * 2
+            idx = L.qea_lstm_seq_timeout_index(B, bwd)
+            assert idx == groups, (B, bwd)
+            xch_start_words = (groups + 1 + 63) // 64 * 64     # the counters, then the timeout word, then the exchange area on a 256-byte line
+            assert 0 <= idx < xch_start_words and idx >= groups, (B, bwd)
+            need.append(xch_start_words * 4 + 2 * 2 * (-(-B // rows) * (rows // 32)) * XRB[bwd])
+        assert L.qea_lstm_seq_workspace_bytes(B) == max(need), B
+    assert L.qea_lstm_seq_timeout_index(0, 0) == -1 and L.qea_lstm_seq_timeout_index(-3, 1) == -1

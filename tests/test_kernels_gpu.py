@@ -491,8 +491,13 @@ def test_lstm_seq_is_bit_identical_under_concurrent_load(B):
         ops.lstm_layer_bwd_any(gates, c, dy, pb, mode, None, T, B)
         return y, acts, c, gates
 
+    def no_timeout():                                     # the passes' timeout words, read before any number is looked at
+        for which in ("fwd", "bwd"):
+            assert not ops.lstm_seq_timed_out(which), f"in-launch hand-off timed out ({which})"
+
     ref = layer()
     torch.cuda.synchronize()
+    no_timeout()
     assert all(torch.isfinite(t).all() for t in ref)
     a = torch.randn(4096, 4096, device=dev)
     side = torch.cuda.Stream()
@@ -502,6 +507,7 @@ def test_lstm_seq_is_bit_identical_under_concurrent_load(B):
                 a @ a
         out = layer()
         torch.cuda.synchronize()
+        no_timeout()
         for r, o in zip(ref, out):
             assert torch.equal(r, o), rep
 

@@ -18,6 +18,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import lstm_spec
 from helpers import SPLIT_ABS, SPLIT_REL     # the per-element contract of qea_split2_f16 (csrc/common.h)
 
 pytestmark = pytest.mark.gpu
@@ -160,30 +161,12 @@ LSTM_SHAPES = [(4, 70), (4, 600), (3, 1300)]         # 32-row groups, ragged / 1
 LSTM_MODES = ["packs", "bf3", "f32"]                 # what ops.lstm_packs returns for the session's mode / the two step kernels
 
 
-@functools.lru_cache(maxsize=None)
 def _lstm_case(T, B):
     """-> gx [T][B][2048] (gate pre-activations), W_hh of both directions, dy [T][B][512] (unit scale), and the fp64 references for that
-    dy: d loss / d gx (the gate gradients) and d loss / d c_init [B][512] (dc).  A plain loop; rows (samples) never mix, so the
-    reference for a per-sample scaled dy is the per-sample scaled reference."""
-    g = torch.Generator().manual_seed(T * 1000 + B)
-    gx = torch.randn(T, B, 2048, generator=g) * 0.5
-    wh = [torch.randn(1024, 256, generator=g) / 16 for _ in range(2)]
-    dy = torch.randn(T, B, 512, generator=g)
-    gxr = gx.double().requires_grad_()
-    c0 = torch.zeros(B, 512, dtype=torch.double, requires_grad=True)
-    outs = []
-    for d in range(2):
-        w = wh[d].double()
-        h, c = torch.zeros(B, 256, dtype=torch.double), c0[:, d * 256:(d + 1) * 256]
-        ys = [None] * T
-        for t in (range(T - 1, -1, -1) if d else range(T)):
-            i, f, gg, o = (gxr[t, :, d * 1024:(d + 1) * 1024] + h @ w.t()).chunk(4, dim=1)
-            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-            h = torch.sigmoid(o) * torch.tanh(c)
-            ys[t] = h
-        outs.append(torch.stack(ys))
-    torch.cat(outs, dim=2).backward(dy.double())
-    return gx, wh, dy, gxr.grad, c0.grad
+    dy: d loss / d gx (the gate gradients) and d loss / d c_init [B][512] (dc), from the one specification of the layer
+    (tests/lstm_spec.py, cached there).  Rows (samples) never mix, so the reference for a per-sample scaled dy is the per-sample
+    scaled reference."""
+    return lstm_spec.unit_case_with_reference(T, B)
 
 
 def _lstm_packs(mode, wh):
@@ -226,10 +209,7 @@ class _LstmLayer:
         return gates, dc, (ga if carried else None)
 
 
-def _per_sample(got, ref):
-    """max error and max |ref| of every sample (dim 1 of [T][B][..], dim 0 of [B][..])"""
-    dims = (0, 2) if ref.dim() == 3 else (1,)
-    return (got.cpu().double() - ref).abs().amax(dim=dims), ref.abs().amax(dim=dims)
+_per_sample = lstm_spec.per_sample     # max error and max |ref| of every sample
 
 
 # ============================================================================= 1. power-of-two homogeneity, bit for bit
