@@ -649,6 +649,35 @@ int qea_spread_pick(const float* est, int32_t n, const float* pts, int32_t k, in
 int qea_seq_entropy(const float* lp, int64_t ld_t, int64_t ld_n, int32_t T, int32_t B, int32_t C, int32_t num_classes, float* out,
                     void* stream);
 
+/* Whole pages of any size through the eval-mode UNet, tile by tile (csrc/page_tiles.hip; qea/pages.py: clean_pages, whose
+ * tiles_gather_spec / tiles_scatter_spec are the specification of these two).  A page store holds n_pages pages back to back, row-major
+ * without padding: page p is h[p] rows of w[p] elements at ELEMENT offset[p] of a store of store_elems elements (8-bit grey, so pages start
+ * at any byte, or fp32); the outputs of the scatter are packed the same way with the same offsets.  All tiles of one call are TH x TW; they
+ * may belong to several pages.
+ * qea_page_tiles_gather — out[N][TH][TW] (fp32, 16-byte aligned) in ONE launch.  tile int32 [N][3] = (page, oy, ox): out[t][y][x] is page
+ *   pixel (oy + y, ox + x), and white (1.0) where that lies outside the page's h x w (the padding of a page to a multiple of 16 is never
+ *   stored).  store_is_f32 = 0: 8-bit pixels, each replaced by table[p] (256 fp32 values on the device, built by the HOST as float32(p) /
+ *   255 as for qea_strip_batch); store_is_f32 = 1: fp32 pixels copied as they are, `table` may be NULL.  Every element of `out` is written
+ *   exactly once, one 16-byte store per lane: TW % 4 == 0.
+ * qea_page_tiles_scatter — tiles[N][TH][TW] (fp32, 16-byte aligned) pasted into the packed outputs in ONE launch.  tile int32 [N][7] =
+ *   (page, oy, ox, cy0, cy1, cx0, cx1): the tile owns the page pixels of its core [cy0, cy1) x [cx0, cx1) (page coordinates) that lie inside
+ *   the tile and inside the page's h x w; each is stored to out_f32 (as it is) and / or to out_u8 as
+ *   (uint8)(min(max(x, 0), 1) * 255.0f) — ONE fp32 multiply and no fused add, then truncation: (x.clamp(0, 1) * 255).to(torch.uint8) bit for
+ *   bit, what ToPILImage makes of a float tensor.  NaN gives 0.  Either output may be NULL, not both.  With cores that partition every
+ *   page (qea/pages.py: plan_tiles) each output element is written exactly once: no atomics, no prior fill; what no core covers is left
+ *   as it was.
+ * A row of either table whose page does not exist or does not lie inside the store (offset[p] < 0 or offset[p] + h[p] * w[p] > store_elems)
+ * gives a white tile / writes nothing.  Nothing synchronises, no workspace, no LDS.  Refused before the launch: a NULL pointer, n_pages or N
+ * outside 1..2^24, store_elems < 1, TH outside 1..8192, TW outside 4..8192 or not a multiple of 4, a flag that is neither 0 nor 1, an 8-bit
+ * store without a table, a misaligned out / tiles / fp32 pointer.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects these two by symbol.) */
+int qea_page_tiles_gather(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h,
+                          const int32_t* w, int32_t n_pages, const int32_t* tile, int32_t N, int32_t TH, int32_t TW, const float* table,
+                          float* out, void* stream);
+int qea_page_tiles_scatter(const float* tiles, int32_t N, int32_t TH, int32_t TW, const int32_t* tile, const int64_t* offset,
+                           const int32_t* h, const int32_t* w, int32_t n_pages, int64_t store_elems, float* out_f32, uint8_t* out_u8,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

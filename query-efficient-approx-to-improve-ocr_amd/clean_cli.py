@@ -1,0 +1,63 @@
+"""[new] Clean a folder of scans with a trained preprocessor (flags: qea/cli_flags.py tag "n").
+
+    python clean_cli.py --prep_path PREP --in_dir scans --out_dir cleaned [--tile H W] [--batch_pages N]
+
+Every png / jpg / jpeg of --in_dir, in name order, is decoded to 8-bit grey, sent through the tiled eval-mode pass of qea/pages.py
+(clean_pages: pages of any size, --batch_pages of them per call so that tiles of different pages share UNet passes) and written to
+--out_dir as an 8-bit grey PNG of the same size and stem.  PIL does the file I/O only: the p / 255 normalisation, the tiling and the
+(uint8)(clamp(x, 0, 1) * 255) quantisation run on the device.  `backend` is the injection seam of the other drivers (the default is
+the HIP path; the oracle backend runs the same plan on the host).
+"""
+import os
+
+import numpy as np
+import torch
+
+from qea.pages import clean_pages
+from qea.trainer_core import hip_backend
+
+EXTENSIONS = (".png", ".jpg", ".jpeg")
+
+
+class CleanPages:
+    def __init__(self, args, backend=None):
+        self.in_dir, self.out_dir = args.in_dir, args.out_dir
+        self.tile = tuple(args.tile)
+        self.batch_pages = max(1, int(args.batch_pages))
+        self.device = (backend or hip_backend()).device
+        self.prep_model = torch.load(args.prep_path, map_location=self.device, weights_only=False).to(self.device).eval()
+        self.names = sorted(n for n in os.listdir(self.in_dir) if n.lower().endswith(EXTENSIONS))
+        stems = [os.path.splitext(n)[0] for n in self.names]
+        twice = sorted({s for s in stems if stems.count(s) > 1})
+        if twice:
+            raise ValueError(f"{self.in_dir}: several files share the stems {twice}; their outputs would overwrite each other")
+
+    def run(self):
+        """-> the paths written, in input order"""
+        from PIL import Image
+        os.makedirs(self.out_dir, exist_ok=True)
+        written = []
+        for i in range(0, len(self.names), self.batch_pages):
+            names = self.names[i:i + self.batch_pages]
+            pages = []
+            for n in names:
+                with Image.open(os.path.join(self.in_dir, n)) as img:
+                    pages.append(torch.from_numpy(np.array(img.convert("L"), dtype=np.uint8)))
+            cleaned = clean_pages(self.prep_model, pages, tile=self.tile, out="u8")
+            for n, page in zip(names, cleaned):
+                path = os.path.join(self.out_dir, os.path.splitext(n)[0] + ".png")
+                Image.fromarray(page.cpu().numpy()).save(path)
+                written.append(path)
+        print(f"{len(written)} pages cleaned into {self.out_dir}")
+        return written
+
+
+def build_parser():
+    from qea.cli_flags import build_parser as _build
+    return _build("n", "Cleans every scan of a folder with a trained preprocessor")
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
+    print(args)
+    CleanPages(args).run()

@@ -1,0 +1,158 @@
+// Whole pages through the eval-mode UNet tile by tile: all tiles of a pass cut out of the packed pages in one launch, and the cores of the
+// cleaned tiles pasted into the packed outputs in one launch (include/qea_hip.h: qea_page_tiles_gather / qea_page_tiles_scatter;
+// qea/pages.py: clean_pages, whose tiles_gather_spec / tiles_scatter_spec are the specification of the two kernels).
+//
+// The page store keeps pages of any sizes back to back, row-major without padding: page p is h[p] rows of w[p] elements at element
+// offset[p] of the store (8-bit grey, so pages start at any byte, or fp32).  The outputs are packed the same way with the same offsets.
+//
+// page_tiles_gather_kernel: out[N][TH][TW] fp32.  Tile t = (page, oy, ox) reads page pixel (oy + y, ox + x); what lies outside the page's
+// h x w is white (1.0): the padding to the next multiple of 16 costs nothing.  8-bit pixels go through the caller's 256-entry table (p / 255
+// as the HOST rounds it, as in csrc/strip_batch.hip).  One lane per four neighbouring pixels of a tile row (TW % 4 == 0), one 16-byte store per
+// lane; grid.x walks the TH * TW / 4 quads of a tile, grid.y the tiles, so the three tile words and the page's words are uniform over the
+// workgroup (scalar loads) and the index arithmetic inside a tile is 32-bit.  Pages start at any element and have any width, so the four
+// source elements of a quad are read one by one; those of a wave's quads are neighbours in a few cache lines.  Every output element is written.
+//
+// page_tiles_scatter_kernel: the same lanes over the same quads, read with one 16-byte load.  Tile t = (page, oy, ox, cy0, cy1, cx0, cx1) owns
+// the page pixels of its core [cy0, cy1) x [cx0, cx1) (page coordinates) that lie inside the tile and inside the page; a lane stores those of
+// its four pixels, as fp32 and / or as 8-bit (uint8)(min(max(x, 0), 1) * 255.0f): one fp32 multiply, truncation, NaN -> 0.  The cores of a
+// page's tiles partition it (qea/pages.py: plan_tiles), so every output element is written exactly once: no atomics, no prior fill.  Output
+// rows have any width and start at any element, so the stores are per pixel; a wave's stores are neighbours in a few cache lines.
+//
+// Both kernels skip a page that does not lie inside the store (offset < 0 or offset + h * w > store_elems): a bad table gives white
+// tiles / unwritten outputs, never an access outside the caller's buffers.
+#include "common.h"
+
+namespace {
+
+constexpr int PT_THREADS = 256;
+
+struct Page {
+  long long off;
+  int h, w;     // 0 x 0: no such page
+};
+
+__device__ __forceinline__ Page page_of(int p, const int64_t* __restrict__ offset, const int32_t* __restrict__ h, const int32_t* __restrict__ w,
+                                        int n_pages, long long store_elems) {
+  Page g = {0, 0, 0};
+  if (p >= 0 && p < n_pages) {
+    const long long off = offset[p];
+    const int ph = h[p], pw = w[p];
+    if (off >= 0 && ph > 0 && pw > 0 && off <= store_elems && (long long)ph * pw <= store_elems - off) {
+      g.off = off;
+      g.h = ph;
+      g.w = pw;
+    }
+  }
+  return g;
+}
+
+template <typename T>
+__global__ __launch_bounds__(PT_THREADS) void page_tiles_gather_kernel(const T* __restrict__ store, long long store_elems,
+                                                                       const int64_t* __restrict__ offset, const int32_t* __restrict__ h,
+                                                                       const int32_t* __restrict__ w, int n_pages,
+                                                                       const int32_t* __restrict__ tile, int N, int TH, int TW,
+                                                                       const float* __restrict__ table, float* __restrict__ out) {
+  const int qw = TW >> 2;                              // quads per row
+  const int q = blockIdx.x * PT_THREADS + threadIdx.x; // quad of the tile, row-major
+  if (q >= TH * qw) return;
+  const int ty = q / qw, tx0 = (q - ty * qw) << 2;
+  for (int t = blockIdx.y; t < N; t += gridDim.y) {    // uniform over the workgroup
+    f32x4 v = {1.f, 1.f, 1.f, 1.f};
+    const Page g = page_of(tile[3 * t], offset, h, w, n_pages, store_elems);
+    const long long py = (long long)tile[3 * t + 1] + ty, px0 = (long long)tile[3 * t + 2] + tx0;
+    if (py >= 0 && py < g.h) {
+      const T* src = store + g.off + py * g.w;         // row py of the page; only columns 0..w-1 are read
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const long long px = px0 + k;
+        if (px >= 0 && px < g.w) {
+          if constexpr (sizeof(T) == 1) v[k] = table[src[px]];
+          else v[k] = src[px];
+        }
+      }
+    }
+    *reinterpret_cast<f32x4*>(out + (((size_t)t * TH * qw + q) << 2)) = v;
+  }
+}
+
+__device__ __forceinline__ uint8_t to_u8(float x) {
+  const float c = fminf(fmaxf(x, 0.f), 1.f);           // fmaxf(NaN, 0) = 0
+  return (uint8_t)(int)__fmul_rn(c, 255.0f);           // one fp32 multiply, then truncation
+}
+
+__global__ __launch_bounds__(PT_THREADS) void page_tiles_scatter_kernel(const float* __restrict__ tiles, int N, int TH, int TW,
+                                                                        const int32_t* __restrict__ tile, const int64_t* __restrict__ offset,
+                                                                        const int32_t* __restrict__ h, const int32_t* __restrict__ w,
+                                                                        int n_pages, long long store_elems, float* __restrict__ out_f32,
+                                                                        uint8_t* __restrict__ out_u8) {
+  const int qw = TW >> 2;
+  const int q = blockIdx.x * PT_THREADS + threadIdx.x;
+  if (q >= TH * qw) return;
+  const int ty = q / qw, tx0 = (q - ty * qw) << 2;
+  for (int t = blockIdx.y; t < N; t += gridDim.y) {    // uniform over the workgroup
+    const int32_t* r = tile + 7 * t;
+    const Page g = page_of(r[0], offset, h, w, n_pages, store_elems);
+    const long long py = (long long)r[1] + ty, px0 = (long long)r[2] + tx0;
+    // rows and columns this tile owns: its core, inside the page (the tile itself bounds ty and tx0 + k)
+    const long long y0 = max(r[3], 0), y1 = min(r[4], g.h), x0 = max(r[5], 0), x1 = min(r[6], g.w);
+    if (py < y0 || py >= y1 || px0 + 3 < x0 || px0 >= x1) continue;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(tiles + (((size_t)t * TH * qw + q) << 2));
+    const long long row = g.off + py * g.w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long long px = px0 + k;
+      if (px >= x0 && px < x1) {
+        if (out_f32) out_f32[row + px] = v[k];
+        if (out_u8) out_u8[row + px] = to_u8(v[k]);
+      }
+    }
+  }
+}
+
+int check_common(const char* who, const void* offset, const void* h, const void* w, const void* tile, int n_pages, long long store_elems, int N,
+                 int TH, int TW) {
+  QEA_REQUIRE(offset && h && w && tile, "%s: null pointer", who);
+  QEA_REQUIRE(n_pages >= 1 && n_pages <= (1 << 24), "%s: n_pages=%d outside 1..2^24", who, n_pages);
+  QEA_REQUIRE(store_elems >= 1, "%s: store_elems=%lld", who, store_elems);
+  QEA_REQUIRE(N >= 1 && N <= (1 << 24), "%s: N=%d outside 1..2^24", who, N);
+  QEA_REQUIRE(TH >= 1 && TH <= 8192, "%s: TH=%d outside 1..8192", who, TH);
+  QEA_REQUIRE(TW >= 4 && TW <= 8192 && TW % 4 == 0, "%s: TW=%d must be a multiple of 4 in 4..8192", who, TW);
+  return QEA_OK;
+}
+
+}  // namespace
+
+extern "C" int qea_page_tiles_gather(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h,
+                                     const int32_t* w, int32_t n_pages, const int32_t* tile, int32_t N, int32_t TH, int32_t TW,
+                                     const float* table, float* out, void* stream) {
+  QEA_REQUIRE(store && out, "qea_page_tiles_gather: null pointer");
+  QEA_REQUIRE(store_is_f32 == 0 || store_is_f32 == 1, "qea_page_tiles_gather: store_is_f32=%d is neither 0 nor 1", store_is_f32);
+  if (int rc = check_common("qea_page_tiles_gather", offset, h, w, tile, n_pages, store_elems, N, TH, TW)) return rc;
+  QEA_REQUIRE(store_is_f32 || table, "qea_page_tiles_gather: an 8-bit store needs the 256-entry table");
+  QEA_REQUIRE(!store_is_f32 || ((uintptr_t)store & 3) == 0, "qea_page_tiles_gather: an fp32 store must be 4-byte aligned");
+  QEA_REQUIRE(((uintptr_t)out & 15) == 0, "qea_page_tiles_gather: out must be 16-byte aligned");
+  const dim3 grid(qea_cdiv((long long)TH * (TW / 4), PT_THREADS), N < 65535 ? N : 65535);   // TH * TW / 4 <= 2^24 quads per tile
+  if (store_is_f32)
+    hipLaunchKernelGGL(page_tiles_gather_kernel<float>, grid, dim3(PT_THREADS), 0, (hipStream_t)stream, (const float*)store,
+                       (long long)store_elems, offset, h, w, n_pages, tile, N, TH, TW, table, out);
+  else
+    hipLaunchKernelGGL(page_tiles_gather_kernel<uint8_t>, grid, dim3(PT_THREADS), 0, (hipStream_t)stream, (const uint8_t*)store,
+                       (long long)store_elems, offset, h, w, n_pages, tile, N, TH, TW, table, out);
+  QEA_CHECK_LAUNCH();
+  return QEA_OK;
+}
+
+extern "C" int qea_page_tiles_scatter(const float* tiles, int32_t N, int32_t TH, int32_t TW, const int32_t* tile, const int64_t* offset,
+                                      const int32_t* h, const int32_t* w, int32_t n_pages, int64_t store_elems, float* out_f32, uint8_t* out_u8,
+                                      void* stream) {
+  QEA_REQUIRE(tiles, "qea_page_tiles_scatter: null pointer");
+  QEA_REQUIRE(out_f32 || out_u8, "qea_page_tiles_scatter: neither an fp32 nor an 8-bit output");
+  if (int rc = check_common("qea_page_tiles_scatter", offset, h, w, tile, n_pages, store_elems, N, TH, TW)) return rc;
+  QEA_REQUIRE(((uintptr_t)tiles & 15) == 0, "qea_page_tiles_scatter: tiles must be 16-byte aligned");
+  QEA_REQUIRE(((uintptr_t)out_f32 & 3) == 0, "qea_page_tiles_scatter: out_f32 must be 4-byte aligned");
+  const dim3 grid(qea_cdiv((long long)TH * (TW / 4), PT_THREADS), N < 65535 ? N : 65535);
+  hipLaunchKernelGGL(page_tiles_scatter_kernel, grid, dim3(PT_THREADS), 0, (hipStream_t)stream, tiles, N, TH, TW, tile, offset, h, w, n_pages,
+                     (long long)store_elems, out_f32, out_u8);
+  QEA_CHECK_LAUNCH();
+  return QEA_OK;
+}

@@ -13,6 +13,9 @@ Returns (accuracy, cer) of the cleaned strips, as the reference's patch flow doe
     twice (by the batch, then by the set); here it is summed over the strips and divided once by the set size.
   * A document whose size is not a multiple of 16 raises the UNet's ValueError with the file's name added (the reference fails
     on it too); it is not padded silently.
+  * [new] --tile H W sends the images of both flows through the tiled whole-page pass (qea/pages.py: clean_pages) instead: a document
+    of ANY size evaluates, as the eval-mode pass over the page padded with white to the next multiple of 16 and cropped back.  Without
+    the flag nothing changes, the ValueError included.
   * [new] --synthetic_size N evaluates on N synthetic strips / documents (datasets/synthetic.py).
   * The loaders run in the main process (the reference asks for properties.num_workers workers).
 `backend` / `dataset` / `ocr` are injection seams for tests, as in the trainers; the default backend is the HIP path.
@@ -22,6 +25,8 @@ import os
 import torch
 
 import properties
+from qea._lib import QeaError
+from qea.pages import clean_pages
 from qea.trainer_core import hip_backend
 from utils import compare_labels, get_ocr_helper, get_text_stack, show_img
 
@@ -35,6 +40,7 @@ class EvalPrep:
         self.ocr_name = args.ocr
         self.dataset_name = args.dataset
         self.show_orig = args.show_orig
+        self.tile = tuple(args.tile) if getattr(args, "tile", None) else None
         self.input_size = properties.input_size
         if self.dataset_name == "vgg":
             self.test_set = os.path.join(args.data_base_path, properties.vgg_text_dataset_test)
@@ -84,7 +90,10 @@ class EvalPrep:
         with torch.no_grad():
             for batch in self.loader_eval:
                 images, labels = batch[0], list(batch[1])
-                img_preds = self.prep_model(images.to(self.device))
+                if self.tile:
+                    img_preds = torch.stack(clean_pages(self.prep_model, list(images), tile=self.tile))
+                else:
+                    img_preds = self.prep_model(images.to(self.device))
                 ocr_lbl_pred = self.ocr.get_labels(img_preds.cpu())
                 ocr_lbl_ori = []
                 if self.show_orig:
@@ -127,10 +136,13 @@ class EvalPrep:
                     ori_lbl_crt_count += c
                     ori_lbl_cer += e
                 try:
-                    pred = self.prep_model(image.unsqueeze(0))[0]
+                    pred = clean_pages(self.prep_model, [image], tile=self.tile)[0] if self.tile else self.prep_model(image.unsqueeze(0))[0]
                 except ValueError as err:
                     raise ValueError(f"{name}: {err}") from err
-                pred_crops, labels = get_text_stack(pred, labels_dict, self.input_size)
+                try:
+                    pred_crops, labels = get_text_stack(pred, labels_dict, self.input_size)
+                except QeaError as err:
+                    raise ValueError(f"{name} ({pred.shape[-2]}x{pred.shape[-1]}): the device crops refuse this page: {err}") from err
                 lbl_count += len(labels)
                 pred_labels = self._ocr(pred_crops)
                 c, e = compare_labels(pred_labels, labels)

@@ -1,7 +1,7 @@
 """The reference's command-line surface, as data.  Names, defaults, types, choices and the
 `store_false` quirk of --random_std are those of patch_cli.py:11-155 and area_cli.py:11-124
 (SURVEY.md §5.6), and of train_crnn.py:217-275, eval_crnn.py and eval_prep.py (tags "c", "e", "v") and pruning/prune_dataset.py:88-106 (tag "r"); the MI355X
-build only ADDS flags (marked new)."""
+build only ADDS flags (marked new), and one front end the reference does not have: clean_cli.py (tag "n")."""
 import properties as _properties
 
 SUBSETS = ["random", "uniformCER", "uniformCERglobal", "randomglobal", "rangeCER", "uniformEntropy", "topKCER"]
@@ -139,6 +139,20 @@ FLAGS += [
                         help="[new] FL feature of a document: mean = its mean CER (the reference); history = the means of its strips' CERs over "
                              "the last --history_len epochs of a trainer's all_cers.json (name -> list of per-epoch CERs)"), "r"),
     ("--history_len", dict(type=int, default=8, help="[new] --features history: epochs per feature row (1..32)"), "r"),
+]
+
+
+# [new] whole pages through the cleaner, tile by tile (qea/pages.py): "n" = clean_cli.py; --tile also on "v" = eval_prep.py
+FLAGS += [
+    ("--prep_path", dict(default=_properties.prep_model_path, help="[new] the trained preprocessor (a whole-module checkpoint)"), "n"),
+    ("--in_dir", dict(required=True, help="[new] folder of scans: every png / jpg / jpeg in it is cleaned"), "n"),
+    ("--out_dir", dict(required=True, help="[new] folder for the cleaned pages: 8-bit grey PNGs of the same sizes and stems"), "n"),
+    ("--tile", dict(type=int, nargs=2, metavar=("H", "W"), default=[1024, 1024],
+                    help="[new] largest tile of the tiled eval-mode pass: multiples of 16, at least 208 each"), "n"),
+    ("--tile", dict(type=int, nargs=2, metavar=("H", "W"),
+                    help="[new] send the images through the tiled whole-page pass (qea/pages.py: clean_pages) with tiles of at most H x W "
+                         "(multiples of 16, at least 208): documents of any size evaluate instead of raising"), "v"),
+    ("--batch_pages", dict(type=int, default=8, help="[new] pages decoded, cleaned and written per call of clean_pages"), "n"),
 ]
 
 

@@ -1037,6 +1037,55 @@ def doc_crops_scatter(dout, box, box_first, doc, strip_first, dimg, accumulate=F
     DOC_LAUNCHES["scatter"] += 1
 
 
+PAGE_LAUNCHES = {"gather": 0, "scatter": 0}   # launches of csrc/page_tiles.hip issued through this module (tests, tools)
+
+
+def _page_tables(who, offset, h, w, rows, cols, tiles):
+    """The argument checks the two entry points of csrc/page_tiles.hip share; -> (n_pages, N, TH, TW)."""
+    if offset.dtype != torch.int64 or h.dtype != torch.int32 or w.dtype != torch.int32 or rows.dtype != torch.int32 or tiles.dtype != torch.float32:
+        raise _lib.QeaError(f"{who} needs int64 offsets, int32 heights, widths and tile rows, fp32 tiles")
+    if not all(t.is_cuda and t.device == tiles.device for t in (offset, h, w, rows)):
+        raise _lib.QeaError(f"{who} needs all its tensors on one CUDA device")
+    if not all(t.is_contiguous() for t in (offset, h, w, rows, tiles)):
+        raise _lib.QeaError(f"{who} needs contiguous tensors")
+    n = offset.numel()
+    if h.numel() != n or w.numel() != n or rows.dim() != 2 or rows.shape[1] != cols or tiles.dim() != 4 or tiles.shape[1] != 1 or tiles.shape[0] != rows.shape[0]:
+        raise _lib.QeaError(f"{who}: {n} offsets, {h.numel()} / {w.numel()} sizes, tile rows {tuple(rows.shape)} (want [N][{cols}]), "
+                            f"tiles {tuple(tiles.shape)} (want [N,1,TH,TW])")
+    return n, tiles.shape[0], tiles.shape[2], tiles.shape[3]
+
+
+def page_tiles_gather(store, offset, h, w, rows, out, table=None):
+    """include/qea_hip.h: qea_page_tiles_gather — the packed pages `store` (uint8 with the 256-entry fp32 `table`, or fp32), their element
+    offset (int64 [n]) and h / w (int32 [n]), the tile rows (int32 [N][3] = page, oy, ox) -> out [N,1,TH,TW] fp32, white outside a page,
+    written whole by ONE launch on the current stream."""
+    n, N, TH, TW = _page_tables("page_tiles_gather", offset, h, w, rows, 3, out)
+    if store.dtype not in (torch.uint8, torch.float32) or store.dim() != 1 or not store.is_contiguous() or store.device != out.device:
+        raise _lib.QeaError("page_tiles_gather needs a one-dimensional contiguous uint8 or float32 store on the tiles' device")
+    if store.dtype == torch.uint8 and (table is None or table.dtype != torch.float32 or table.numel() != 256 or not table.is_contiguous()
+                                       or table.device != out.device):
+        raise _lib.QeaError("page_tiles_gather: a uint8 store needs a contiguous 256-entry fp32 table on the same device")
+    _lib.check(_lib.lib().qea_page_tiles_gather(_ptr(store), int(store.dtype == torch.float32), store.numel(), _ptr(offset), _ptr(h), _ptr(w), n,
+                                                _ptr(rows), N, TH, TW, _ptr(table), _ptr(out), _stream()), "qea_page_tiles_gather")
+    PAGE_LAUNCHES["gather"] += 1
+
+
+def page_tiles_scatter(tiles, rows, offset, h, w, out_f32=None, out_u8=None):
+    """include/qea_hip.h: qea_page_tiles_scatter — tiles [N,1,TH,TW] fp32 and the tile rows (int32 [N][7] = page, oy, ox, cy0, cy1, cx0, cx1)
+    -> the core of every tile pasted into the packed outputs (out_f32 fp32 and / or out_u8 uint8, one-dimensional, as large as each other)
+    by ONE launch without atomics; the 8-bit value is (uint8)(min(max(x, 0), 1) * 255)."""
+    n, N, TH, TW = _page_tables("page_tiles_scatter", offset, h, w, rows, 7, tiles)
+    outs = [(o, dt) for o, dt in ((out_f32, torch.float32), (out_u8, torch.uint8)) if o is not None]
+    if not outs:
+        raise _lib.QeaError("page_tiles_scatter needs out_f32, out_u8 or both")
+    for o, dt in outs:
+        if o.dtype != dt or o.dim() != 1 or not o.is_contiguous() or o.device != tiles.device or o.numel() != outs[0][0].numel():
+            raise _lib.QeaError("page_tiles_scatter needs one-dimensional contiguous outputs (float32 / uint8) of one size on the tiles' device")
+    _lib.check(_lib.lib().qea_page_tiles_scatter(_ptr(tiles), N, TH, TW, _ptr(rows), _ptr(offset), _ptr(h), _ptr(w), n, outs[0][0].numel(),
+                                                 _ptr(out_f32), _ptr(out_u8), _stream()), "qea_page_tiles_scatter")
+    PAGE_LAUNCHES["scatter"] += 1
+
+
 SPREAD_WAVE_MAX_N, SPREAD_LDS4_MAX_N, SPREAD_LDS_MAX_N, SPREAD_MAX_N = 1536, 24576, 32768, 1 << 24    # QEA_SPREAD_* of include/qea_hip.h
 SAMPLER_LAUNCHES = {"spread": 0, "entropy": 0}    # launches of csrc/sampling.hip issued through this module (tests, tools)
 ENTROPY_NUM_CLASSES = 95                          # calc_entropy's constant (selection_utils.py:10), whatever the width of the scores
