@@ -7,9 +7,8 @@
 // strip_first[n] <= s < strip_first[n+1] and is box s - strip_first[n] of that document.
 //
 // doc_crops_gather_kernel: the values of crop_pad_gather_kernel (csrc/misc.hip) for that image and box, the white ground and the
-// floor division of an oversize crop included.  One lane per four neighbouring output pixels of a row (OW % 4 == 0), one 16-byte
-// store per lane; grid.x walks the OH * OW / 4 quads of a strip and grid.y the strips, so the strip is uniform over the workgroup and
-// the image number (a binary search in strip_first) and the four box words are scalar loads.  Every output element is written.
+// floor division of an oversize crop included, as a window gather (csrc/window_gather.h: lanes, reads, store and the bad-table rule).
+// The strip is uniform over the workgroup: its image number (a binary search in strip_first) and its four box words are scalar loads.
 //
 // doc_crops_scatter_kernel: the backward in GATHER form.  Each lane owns four neighbouring pixels of dimg[N][H][W] (W % 4 == 0), a
 // workgroup a 16 x 64 tile of one image.  The workgroup first culls the document's boxes against its tile: 256 boxes at a time, a
@@ -19,36 +18,13 @@
 // first, starting from 0.  Each pixel is written once: the sum, or with `accumulate` dimg + sum; a pixel no box covers gets 0.  No
 // atomics: the result is fixed by the inputs, and for boxes that do not overlap it is 0 + dout = what memset + crop_pad_scatter_kernel
 // leave.  Index arithmetic inside an image or a strip is 32-bit.
-#include "common.h"
-
-static __device__ __forceinline__ int qea_floordiv2(int d) { return d >= 0 ? d / 2 : -((-d + 1) / 2); }
+#include "window_gather.h"
 
 namespace {
 
 constexpr int DC_THREADS = 256;
 constexpr int DC_TILE_W = 64, DC_TILE_H = 16;          // pixels of dimg per workgroup: 16 quads x 16 rows = 256 lanes
 constexpr int DC_LIST = DC_THREADS;                    // boxes culled per chunk, a lane each
-
-// What a strip reads of its image: the box clipped to the image, cut to what an OH x OW target keeps of it.  Output element
-// (ox, oy) of the strip is image pixel (ox - dx, oy - dy) where that lies in [fx0, fx1) x [fy0, fy1), white elsewhere.
-struct Footprint {
-  int fx0, fy0, fx1, fy1, dx, dy;
-};
-
-__device__ __forceinline__ Footprint footprint(const int32_t* __restrict__ b, int H, int W, int OH, int OW) {
-  const int x0 = max(b[0], 0), y0 = max(b[1], 0), x1 = min(b[2], W), y1 = min(b[3], H);   // the store clips already: in bounds whatever it holds
-  const int cw = x1 - x0, ch = y1 - y0;
-  // Python floor division as in padder (utils.py): a crop larger than the target by an odd amount loses the EXTRA pixel on the left/top
-  const int left = qea_floordiv2(OW - cw), top = qea_floordiv2(OH - ch);
-  Footprint f;
-  f.fx0 = x0 + max(0, -left);
-  f.fx1 = x0 + min(cw, OW - left);
-  f.fy0 = y0 + max(0, -top);
-  f.fy1 = y0 + min(ch, OH - top);
-  f.dx = left - x0;
-  f.dy = top - y0;
-  return f;
-}
 
 // image n of strip s: the last n in 0..N-1 with strip_first[n] <= s (uniform: scalar loads)
 __device__ __forceinline__ int image_of(const int32_t* __restrict__ strip_first, int N, int s) {
@@ -60,17 +36,13 @@ __device__ __forceinline__ int image_of(const int32_t* __restrict__ strip_first,
   return lo;
 }
 
-__global__ __launch_bounds__(DC_THREADS) void doc_crops_gather_kernel(const float* __restrict__ imgs, int N, int H, int W,
+__global__ __launch_bounds__(WG_THREADS) void doc_crops_gather_kernel(const float* __restrict__ imgs, int N, int H, int W,
                                                                       const int32_t* __restrict__ box, const int32_t* __restrict__ box_first,
                                                                       int n_docs, int n_boxes, const int64_t* __restrict__ doc,
                                                                       const int32_t* __restrict__ strip_first, int S, int OH, int OW,
                                                                       float* __restrict__ out) {
-  const int qw = OW >> 2;                              // quads per row
-  const int q = blockIdx.x * DC_THREADS + threadIdx.x; // quad of the strip, row-major
-  if (q >= OH * qw) return;
-  const int oy = q / qw, ox0 = (q - oy * qw) << 2;
-  for (int s = blockIdx.y; s < S; s += gridDim.y) {    // uniform over the workgroup
-    f32x4 v = {1.f, 1.f, 1.f, 1.f};
+  window_gather(imgs, (const float*)nullptr, out, S, OH, OW, [=](int s) {
+    Window win = {};
     const int n = image_of(strip_first, N, s);
     const int j = s - strip_first[n];
     const int64_t d = doc[n];
@@ -78,19 +50,11 @@ __global__ __launch_bounds__(DC_THREADS) void doc_crops_gather_kernel(const floa
       const int first = box_first[d], bi = first + j;
       if (first >= 0 && bi < box_first[d + 1] && bi < n_boxes) {
         const Footprint f = footprint(box + 4 * bi, H, W, OH, OW);
-        const int py = oy - f.dy;
-        if (py >= f.fy0 && py < f.fy1) {
-          const float* src = imgs + (size_t)n * H * W + py * W;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int px = ox0 + k - f.dx;
-            if (px >= f.fx0 && px < f.fx1) v[k] = src[px];
-          }
-        }
+        win = {(long long)n * H * W - (f.dy * W + f.dx), W, f.fx0 + f.dx, f.fy0 + f.dy, f.fx1 + f.dx, f.fy1 + f.dy};
       }
     }
-    *reinterpret_cast<f32x4*>(out + (((size_t)s * OH * qw + q) << 2)) = v;
-  }
+    return win;
+  });
 }
 
 struct Culled {
@@ -196,9 +160,7 @@ extern "C" int qea_doc_crops_gather(const float* imgs, int32_t N, int32_t H, int
   QEA_REQUIRE(imgs && out, "qea_doc_crops_gather: null pointer");
   if (int rc = check_tables("qea_doc_crops_gather", box, box_first, doc, strip_first, n_docs, n_boxes, N, H, W, S, OH, OW)) return rc;
   QEA_REQUIRE(((uintptr_t)out & 15) == 0, "qea_doc_crops_gather: out must be 16-byte aligned");
-  const dim3 grid(qea_cdiv((long long)OH * (OW / 4), DC_THREADS), S < 65535 ? S : 65535);   // OH * OW / 4 <= 2^23 quads per strip
-  hipLaunchKernelGGL(doc_crops_gather_kernel, grid, dim3(DC_THREADS), 0, (hipStream_t)stream, imgs, N, H, W, box, box_first, n_docs, n_boxes,
-                     doc, strip_first, S, OH, OW, out);
+  launch_over_quads(doc_crops_gather_kernel, S, OH, OW, stream, imgs, N, H, W, box, box_first, n_docs, n_boxes, doc, strip_first, S, OH, OW, out);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

@@ -4,8 +4,7 @@
 // All HBM- or latency-bound; bytes noted per entry point in include/qea_hip.h.
 #include "common.h"
 #include "edit_distance.h"
-
-static __device__ __forceinline__ int qea_floordiv2(int d) { return d >= 0 ? d / 2 : -((-d + 1) / 2); }
+#include "window_gather.h"
 
 namespace {
 
@@ -146,24 +145,23 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ ke
 }
 
 // ------------------------------------------------------------------ crop + pad
-struct Box { int x0, y0, x1, y1; };
+// Element i of the [N][OH][OW] strips -> the image pixel it shows (csrc/window_gather.h: footprint; the boxes lie inside the image, the
+// caller clips them), or -1 where the strip is white.  A box per element: grid-stride over all elements, the box words per lane.
+__device__ __forceinline__ long long crop_pad_pixel(long long i, const int* __restrict__ boxes, int OH, int OW, int W) {
+  const int ox = (int)(i % OW);
+  const int oy = (int)((i / OW) % OH);
+  const int* b = boxes + 4 * (i / ((long long)OW * OH));
+  const Footprint f = footprint(b[0], b[1], b[2], b[3], OH, OW);
+  const int px = ox - f.dx, py = oy - f.dy;
+  return px >= f.fx0 && px < f.fx1 && py >= f.fy0 && py < f.fy1 ? (long long)py * W + px : -1;
+}
 
 __global__ void crop_pad_gather_kernel(const float* __restrict__ img, int H, int W, const int* __restrict__ boxes, int N, int OH, int OW,
                                        float* __restrict__ out) {
   const long long n_el = (long long)N * OH * OW;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long long)gridDim.x * blockDim.x) {
-    const int ox = (int)(i % OW);
-    const int oy = (int)((i / OW) % OH);
-    const int n = (int)(i / ((long long)OW * OH));
-    const int x0 = boxes[n * 4 + 0], y0 = boxes[n * 4 + 1], x1 = boxes[n * 4 + 2], y1 = boxes[n * 4 + 3];
-    const int cw = x1 - x0, ch = y1 - y0;
-    // Python floor division as in padder (utils.py:118-126): a crop larger than the target by an odd amount loses the
-    // EXTRA pixel on the left/top (negative padding), where C's truncation would take it from the right/bottom
-    const int left = qea_floordiv2(OW - cw), top = qea_floordiv2(OH - ch);
-    const int sx = ox - left, sy = oy - top;
-    float v = 1.f;
-    if (sx >= 0 && sx < cw && sy >= 0 && sy < ch) v = img[(size_t)(y0 + sy) * W + x0 + sx];
-    out[i] = v;
+    const long long p = crop_pad_pixel(i, boxes, OH, OW, W);
+    out[i] = p >= 0 ? img[p] : 1.f;
   }
 }
 
@@ -171,16 +169,8 @@ __global__ void crop_pad_scatter_kernel(const float* __restrict__ dout, const in
                                         int H, int W) {
   const long long n_el = (long long)N * OH * OW;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long long)gridDim.x * blockDim.x) {
-    const int ox = (int)(i % OW);
-    const int oy = (int)((i / OW) % OH);
-    const int n = (int)(i / ((long long)OW * OH));
-    const int x0 = boxes[n * 4 + 0], y0 = boxes[n * 4 + 1], x1 = boxes[n * 4 + 2], y1 = boxes[n * 4 + 3];
-    const int cw = x1 - x0, ch = y1 - y0;
-    // Python floor division as in padder (utils.py:118-126): a crop larger than the target by an odd amount loses the
-    // EXTRA pixel on the left/top (negative padding), where C's truncation would take it from the right/bottom
-    const int left = qea_floordiv2(OW - cw), top = qea_floordiv2(OH - ch);
-    const int sx = ox - left, sy = oy - top;
-    if (sx >= 0 && sx < cw && sy >= 0 && sy < ch) atomicAdd(dimg + (size_t)(y0 + sy) * W + x0 + sx, dout[i]);
+    const long long p = crop_pad_pixel(i, boxes, OH, OW, W);
+    if (p >= 0) atomicAdd(dimg + p, dout[i]);
   }
 }
 

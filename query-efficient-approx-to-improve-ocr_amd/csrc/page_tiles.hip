@@ -6,11 +6,9 @@
 // offset[p] of the store (8-bit grey, so pages start at any byte, or fp32).  The outputs are packed the same way with the same offsets.
 //
 // page_tiles_gather_kernel: out[N][TH][TW] fp32.  Tile t = (page, oy, ox) reads page pixel (oy + y, ox + x); what lies outside the page's
-// h x w is white (1.0): the padding to the next multiple of 16 costs nothing.  8-bit pixels go through the caller's 256-entry table (p / 255
-// as the HOST rounds it, as in csrc/strip_batch.hip).  One lane per four neighbouring pixels of a tile row (TW % 4 == 0), one 16-byte store per
-// lane; grid.x walks the TH * TW / 4 quads of a tile, grid.y the tiles, so the three tile words and the page's words are uniform over the
-// workgroup (scalar loads) and the index arithmetic inside a tile is 32-bit.  Pages start at any element and have any width, so the four
-// source elements of a quad are read one by one; those of a wave's quads are neighbours in a few cache lines.  Every output element is written.
+// h x w is white (1.0): the padding to the next multiple of 16 costs nothing.  A window gather (csrc/window_gather.h: lanes, reads, the
+// 256-entry table of an 8-bit store, the 16-byte store); the three tile words and the page's words are uniform over the workgroup (scalar
+// loads).  Tile origins are any int32: the window is cut to the tile without forming oy + y or h - oy where they overflow, its origin in 64 bits.
 //
 // page_tiles_scatter_kernel: the same lanes over the same quads, read with one 16-byte load.  Tile t = (page, oy, ox, cy0, cy1, cx0, cx1) owns
 // the page pixels of its core [cy0, cy1) x [cx0, cx1) (page coordinates) that lie inside the tile and inside the page; a lane stores those of
@@ -20,11 +18,9 @@
 //
 // Both kernels skip a page that does not lie inside the store (offset < 0 or offset + h * w > store_elems): a bad table gives white
 // tiles / unwritten outputs, never an access outside the caller's buffers.
-#include "common.h"
+#include "window_gather.h"
 
 namespace {
-
-constexpr int PT_THREADS = 256;
 
 struct Page {
   long long off;
@@ -47,32 +43,19 @@ __device__ __forceinline__ Page page_of(int p, const int64_t* __restrict__ offse
 }
 
 template <typename T>
-__global__ __launch_bounds__(PT_THREADS) void page_tiles_gather_kernel(const T* __restrict__ store, long long store_elems,
+__global__ __launch_bounds__(WG_THREADS) void page_tiles_gather_kernel(const T* __restrict__ store, long long store_elems,
                                                                        const int64_t* __restrict__ offset, const int32_t* __restrict__ h,
                                                                        const int32_t* __restrict__ w, int n_pages,
                                                                        const int32_t* __restrict__ tile, int N, int TH, int TW,
                                                                        const float* __restrict__ table, float* __restrict__ out) {
-  const int qw = TW >> 2;                              // quads per row
-  const int q = blockIdx.x * PT_THREADS + threadIdx.x; // quad of the tile, row-major
-  if (q >= TH * qw) return;
-  const int ty = q / qw, tx0 = (q - ty * qw) << 2;
-  for (int t = blockIdx.y; t < N; t += gridDim.y) {    // uniform over the workgroup
-    f32x4 v = {1.f, 1.f, 1.f, 1.f};
+  window_gather(store, table, out, N, TH, TW, [=](int t) {
     const Page g = page_of(tile[3 * t], offset, h, w, n_pages, store_elems);
-    const long long py = (long long)tile[3 * t + 1] + ty, px0 = (long long)tile[3 * t + 2] + tx0;
-    if (py >= 0 && py < g.h) {
-      const T* src = store + g.off + py * g.w;         // row py of the page; only columns 0..w-1 are read
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const long long px = px0 + k;
-        if (px >= 0 && px < g.w) {
-          if constexpr (sizeof(T) == 1) v[k] = table[src[px]];
-          else v[k] = src[px];
-        }
-      }
-    }
-    *reinterpret_cast<f32x4*>(out + (((size_t)t * TH * qw + q) << 2)) = v;
-  }
+    const int oy = tile[3 * t + 1], ox = tile[3 * t + 2];
+    // Tile pixel (x, y) is page pixel (ox + x, oy + y): rows -oy .. h-oy-1 and columns -ox .. w-ox-1 of the tile, cut to it.  Origins are
+    // ANY int32, so a - o may not be formed as an int: cut = min(max(a - o, 0), hi) for a >= 0 < hi, where o < a gives 0 < a - o < 2^32
+    const auto cut = [](int a, int o, int hi) { return o >= a ? 0 : (int)min((unsigned)a - (unsigned)o, (unsigned)hi); };
+    return Window{g.off + (long long)oy * g.w + ox, g.w, cut(0, ox, TW), cut(0, oy, TH), cut(g.w, ox, TW), cut(g.h, oy, TH)};
+  });
 }
 
 __device__ __forceinline__ uint8_t to_u8(float x) {
@@ -80,15 +63,13 @@ __device__ __forceinline__ uint8_t to_u8(float x) {
   return (uint8_t)(int)__fmul_rn(c, 255.0f);           // one fp32 multiply, then truncation
 }
 
-__global__ __launch_bounds__(PT_THREADS) void page_tiles_scatter_kernel(const float* __restrict__ tiles, int N, int TH, int TW,
+__global__ __launch_bounds__(WG_THREADS) void page_tiles_scatter_kernel(const float* __restrict__ tiles, int N, int TH, int TW,
                                                                         const int32_t* __restrict__ tile, const int64_t* __restrict__ offset,
                                                                         const int32_t* __restrict__ h, const int32_t* __restrict__ w,
                                                                         int n_pages, long long store_elems, float* __restrict__ out_f32,
                                                                         uint8_t* __restrict__ out_u8) {
-  const int qw = TW >> 2;
-  const int q = blockIdx.x * PT_THREADS + threadIdx.x;
-  if (q >= TH * qw) return;
-  const int ty = q / qw, tx0 = (q - ty * qw) << 2;
+  int q, ty, tx0;
+  if (!quad_of(TH, TW, q, ty, tx0)) return;
   for (int t = blockIdx.y; t < N; t += gridDim.y) {    // uniform over the workgroup
     const int32_t* r = tile + 7 * t;
     const Page g = page_of(r[0], offset, h, w, n_pages, store_elems);
@@ -96,7 +77,7 @@ __global__ __launch_bounds__(PT_THREADS) void page_tiles_scatter_kernel(const fl
     // rows and columns this tile owns: its core, inside the page (the tile itself bounds ty and tx0 + k)
     const long long y0 = max(r[3], 0), y1 = min(r[4], g.h), x0 = max(r[5], 0), x1 = min(r[6], g.w);
     if (py < y0 || py >= y1 || px0 + 3 < x0 || px0 >= x1) continue;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(tiles + (((size_t)t * TH * qw + q) << 2));
+    const f32x4 v = *reinterpret_cast<const f32x4*>(tiles + quad_element(t, TH, TW, q));
     const long long row = g.off + py * g.w;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -131,13 +112,12 @@ extern "C" int qea_page_tiles_gather(const void* store, int32_t store_is_f32, in
   QEA_REQUIRE(store_is_f32 || table, "qea_page_tiles_gather: an 8-bit store needs the 256-entry table");
   QEA_REQUIRE(!store_is_f32 || ((uintptr_t)store & 3) == 0, "qea_page_tiles_gather: an fp32 store must be 4-byte aligned");
   QEA_REQUIRE(((uintptr_t)out & 15) == 0, "qea_page_tiles_gather: out must be 16-byte aligned");
-  const dim3 grid(qea_cdiv((long long)TH * (TW / 4), PT_THREADS), N < 65535 ? N : 65535);   // TH * TW / 4 <= 2^24 quads per tile
   if (store_is_f32)
-    hipLaunchKernelGGL(page_tiles_gather_kernel<float>, grid, dim3(PT_THREADS), 0, (hipStream_t)stream, (const float*)store,
-                       (long long)store_elems, offset, h, w, n_pages, tile, N, TH, TW, table, out);
+    launch_over_quads(page_tiles_gather_kernel<float>, N, TH, TW, stream, (const float*)store, (long long)store_elems, offset, h, w, n_pages,
+                      tile, N, TH, TW, table, out);
   else
-    hipLaunchKernelGGL(page_tiles_gather_kernel<uint8_t>, grid, dim3(PT_THREADS), 0, (hipStream_t)stream, (const uint8_t*)store,
-                       (long long)store_elems, offset, h, w, n_pages, tile, N, TH, TW, table, out);
+    launch_over_quads(page_tiles_gather_kernel<uint8_t>, N, TH, TW, stream, (const uint8_t*)store, (long long)store_elems, offset, h, w, n_pages,
+                      tile, N, TH, TW, table, out);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -150,9 +130,8 @@ extern "C" int qea_page_tiles_scatter(const float* tiles, int32_t N, int32_t TH,
   if (int rc = check_common("qea_page_tiles_scatter", offset, h, w, tile, n_pages, store_elems, N, TH, TW)) return rc;
   QEA_REQUIRE(((uintptr_t)tiles & 15) == 0, "qea_page_tiles_scatter: tiles must be 16-byte aligned");
   QEA_REQUIRE(((uintptr_t)out_f32 & 3) == 0, "qea_page_tiles_scatter: out_f32 must be 4-byte aligned");
-  const dim3 grid(qea_cdiv((long long)TH * (TW / 4), PT_THREADS), N < 65535 ? N : 65535);
-  hipLaunchKernelGGL(page_tiles_scatter_kernel, grid, dim3(PT_THREADS), 0, (hipStream_t)stream, tiles, N, TH, TW, tile, offset, h, w, n_pages,
-                     (long long)store_elems, out_f32, out_u8);
+  launch_over_quads(page_tiles_scatter_kernel, N, TH, TW, stream, tiles, N, TH, TW, tile, offset, h, w, n_pages, (long long)store_elems, out_f32,
+                    out_u8);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

@@ -26,6 +26,9 @@ The same for the document flow (--resident of patch_cli.py), whose sample path a
                                           and one order-fixed launch without atomics backward (csrc/doc_crops.hip); numpy on the host
   ResidentDocuments.load_or_build         the pack file; its signature also covers every .json
   ResidentDocLoader                       the index DataLoader again; yields [images, DocBoxes (box lists that name store and rows), paths]
+
+Both stores are a _PackedStore (the packed pixels, their upload, the pack file, the index checks and the batch) and both loaders an
+_IndexLoader; a store adds its decode, its signature, what it knows per item and its self-check.
 """
 import hashlib
 import json
@@ -69,47 +72,34 @@ def _decode(path, H, W):
     return np.asarray(img, dtype=np.uint8)
 
 
-def _signature(files, H, W):
-    """sha256 over the format version, the target size and (relative name, byte size, st_mtime_ns) of every file, in listing order."""
+def _stat_rows(files, with_json=False):
+    """[relative name, byte size, st_mtime_ns] of every file (and of its .json), in listing order."""
     root = os.path.commonpath([os.path.dirname(os.path.abspath(f)) for f in files]) if files else ""
     rows = []
     for f in files:
-        st = os.stat(f)
-        rows.append([os.path.relpath(os.path.abspath(f), root), st.st_size, st.st_mtime_ns])
-    return hashlib.sha256(json.dumps({"format": PACK_FORMAT, "size": [H, W], "files": rows}).encode()).hexdigest()
+        for g in (f, f.rsplit(".", 1)[0] + ".json") if with_json else (f,):
+            st = os.stat(g)
+            rows.append([os.path.relpath(os.path.abspath(g), root), st.st_size, st.st_mtime_ns])
+    return rows
 
 
-class ResidentStrips:
-    def __init__(self, dataset, size, device="cpu", max_gb=8.0, _packed=None):
-        if not isinstance(dataset, ImgDataset):
-            raise QeaError(f"ResidentStrips packs an ImgDataset, not a {type(dataset).__name__}")
-        self.H, self.W = _size(size)
+def _signature(files, H, W):
+    """sha256 over the format version, the target size and (relative name, byte size, st_mtime_ns) of every file, in listing order."""
+    return hashlib.sha256(json.dumps({"format": PACK_FORMAT, "size": [H, W], "files": _stat_rows(files)}).encode()).hexdigest()
+
+
+class _PackedStore:
+    """What the resident stores share.  Items (strips, documents) as 8-bit grey, row-major, back to back: pixels (flat uint8), offset
+    int64 [n], h / w int32 [n] and the 256-entry table, numpy arrays on a host store and tensors on a device store; `_host` keeps the host
+    arrays a pack file holds (PACKED names them), nbytes their pixels.  A subclass sets H, W and n, and names what else its pack file
+    holds in _pack_extras()."""
+    PACKED = ("pixels", "offset", "h", "w")
+
+    def _open(self, device, max_gb):
         self.device = torch.device(device)
         if self.device.type not in ("cpu", "cuda"):
-            raise QeaError(f"ResidentStrips: device {device!r} is neither cpu nor cuda")
+            raise QeaError(f"{type(self).__name__}: device {device!r} is neither cpu nor cuda")
         self.max_gb = float(max_gb)
-        files = list(dataset.files)
-        self.n = len(files)
-        self.names = [os.path.basename(f) for f in files]
-        self.labels = [_label(f) for f in files]
-        self.lens = np.array([len(l) for l in self.labels], dtype=np.int32)
-        t0 = time.perf_counter()
-        if _packed is None:
-            pixels, offset, h, w = self._pack(files)
-        else:
-            pixels, offset, h, w = _packed
-            self._guard(pixels.size)
-        self.build_seconds = time.perf_counter() - t0
-        self.nbytes = int(pixels.size)
-        self._host = (pixels, offset, h, w)                                   # what a pack file holds
-        table = norm_table()
-        if self.device.type == "cuda":
-            from qea import _lib
-            _lib.lib()                                                        # a missing kernel is an error here, not at the first batch
-            up = lambda a: torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(self.device)
-            self.pixels, self.offset, self.h, self.w, self.table = up(pixels), up(offset), up(h), up(w), up(table)
-        else:
-            self.pixels, self.offset, self.h, self.w, self.table = pixels, offset, h, w, table
 
     def __len__(self):
         return self.n
@@ -119,63 +109,134 @@ class ResidentStrips:
             raise QeaError(f"the resident pack needs more than {nbytes / 2 ** 30:.3f} GB, above the limit of {self.max_gb:g} GB "
                            "(--resident_max_gb)")
 
-    def _pack(self, files):
-        chunks, total = [], 0
-        offset = np.zeros(len(files), dtype=np.int64)
-        h = np.zeros(len(files), dtype=np.int32)
-        w = np.zeros(len(files), dtype=np.int32)
-        for i, f in enumerate(files):
-            a = _decode(f, self.H, self.W)
-            offset[i], h[i], w[i] = total, a.shape[0], a.shape[1]
+    def _pack(self, decoded):
+        """(pixels, offset, h, w) of an iterator of decoded uint8 [h, w] arrays."""
+        chunks, offset, h, w, total = [], [], [], [], 0
+        for a in decoded:
+            offset.append(total)
+            h.append(a.shape[0])
+            w.append(a.shape[1])
             chunks.append(a.reshape(-1))
             total += a.size
             self._guard(total)                                                # refuse as soon as the limit is passed, not after the decode
         pixels = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.uint8)
-        return pixels, offset, h, w
+        return pixels, np.array(offset, dtype=np.int64), np.array(h, dtype=np.int32), np.array(w, dtype=np.int32)
+
+    def _place(self, host, **tables):
+        """Keeps the host arrays `host` (in PACKED order) for the pack file; pixels, offset, h, w, the table and `tables` become the
+        store's attributes, on a device store as tensors (an empty array as one zero: every pointer is valid)."""
+        self._guard(host[0].size)
+        self._host, self.nbytes = tuple(host), int(host[0].size)
+        arrays = dict(zip(_PackedStore.PACKED, host), table=norm_table(), **tables)
+        if self.device.type == "cuda":
+            from qea import _lib
+            _lib.lib()                                                        # a missing kernel is an error here, not at the first batch
+            arrays = {k: torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(self.device) for k, a in arrays.items()}
+        vars(self).update(arrays)
 
     # ---- the pack file ----
     @classmethod
-    def load_or_build(cls, dataset, size, pack_path, device="cpu", max_gb=8.0):
-        """The store of `dataset` through the pack file at `pack_path` (.npz: pixels, offset, h, w, names, labels, signature).  A pack
-        whose signature is not this dataset's (a file added, removed, resized or rewritten, another target size or format) is never
-        used: the store is rebuilt from the files and the pack overwritten."""
-        H, W = _size(size)
-        sig = _signature(dataset.files, H, W)
+    def _load_or_build(cls, n, pack_path, sig, make):
+        """make(packed) through the pack file: `packed` holds the PACKED arrays of a pack whose signature is `sig` and that lists n items,
+        None otherwise (no such file, an unreadable or foreign one, another signature); the store built from None overwrites the pack."""
         packed = None
         if pack_path and os.path.exists(pack_path):
             try:
                 with np.load(pack_path, allow_pickle=False) as z:
-                    if str(z["signature"]) == sig and len(z["offset"]) == len(dataset.files):
-                        packed = (z["pixels"], z["offset"], z["h"], z["w"])
+                    if str(z["signature"]) == sig and len(z["offset"]) == n:
+                        packed = tuple(z[k] for k in cls.PACKED)
             except (OSError, ValueError, KeyError):
                 packed = None                                                 # unreadable or foreign file: rebuild
-        store = cls(dataset, size, device=device, max_gb=max_gb, _packed=packed)
+        store = make(packed)
         store.from_pack = packed is not None
         if packed is None and pack_path:
             store.save(pack_path, sig)
         return store
 
     def save(self, pack_path, signature=None):
-        pixels, offset, h, w = self._host
         tmp = f"{pack_path}.tmp{os.getpid()}"
         os.makedirs(os.path.dirname(os.path.abspath(pack_path)), exist_ok=True)
         with open(tmp, "wb") as f:
-            np.savez(f, pixels=pixels, offset=offset, h=h, w=w, names=np.array(self.names, dtype=str), labels=np.array(self.labels, dtype=str),
-                     signature=np.array(signature or ""), size=np.array([self.H, self.W], dtype=np.int32))
+            np.savez(f, **dict(zip(self.PACKED, self._host)), **self._pack_extras(), signature=np.array(signature or ""),
+                     size=np.array([self.H, self.W], dtype=np.int32))
         os.replace(tmp, pack_path)
 
     # ---- batches ----
-    def _indices(self, idx):
-        if isinstance(idx, torch.Tensor):
-            if idx.is_cuda:
-                raise ValueError("ResidentStrips.batch: idx is a host sequence or a CPU tensor")
-            idx = idx.numpy()
-        idx = np.ascontiguousarray(np.asarray(list(idx) if not isinstance(idx, np.ndarray) else idx).reshape(-1)).astype(np.int64, copy=False)
-        if idx.size == 0:
-            raise ValueError("ResidentStrips.batch: no indices")
-        if int(idx.min()) < 0 or int(idx.max()) >= self.n:
-            raise ValueError(f"ResidentStrips.batch: indices {int(idx.min())}..{int(idx.max())} outside 0..{self.n - 1}")
-        return idx
+    def _rows(self, rows, what, noun="rows", device_tensor=True):
+        """`rows` (a host sequence, an array or a tensor) as int64 [B], checked against 0..n-1: ValueError before any launch."""
+        who = f"{type(self).__name__}.{what}"
+        if isinstance(rows, torch.Tensor):
+            if rows.is_cuda and not device_tensor:
+                raise ValueError(f"{who}: idx is a host sequence or a CPU tensor")
+            rows = rows.cpu().numpy()
+        rows = np.ascontiguousarray(np.asarray(list(rows) if not isinstance(rows, np.ndarray) else rows).reshape(-1)).astype(np.int64, copy=False)
+        if rows.size == 0:
+            raise ValueError(f"{who}: no {noun}")
+        if int(rows.min()) < 0 or int(rows.max()) >= self.n:
+            raise ValueError(f"{who}: {noun} {int(rows.min())}..{int(rows.max())} outside 0..{self.n - 1}")
+        return rows
+
+    def _batch(self, rows, OH, OW, anchor="centre", out=None):
+        """fp32 [B,1,OH,OW] on the store's device: item rows[b] on white, centred vertically and, by `anchor`, centred or at column 0,
+        clipped to OH x OW.  Device store: one launch of qea_strip_batch.  Host store: numpy, the specification."""
+        shape = (rows.size, 1, OH, OW)
+        if self.device.type == "cuda":
+            from qea import ops
+            # a fresh pinned block per call: the caching host allocator hands it out again only after the copy below has run, so
+            # neither a wait nor a second buffer is needed
+            pinned = torch.empty(rows.size, dtype=torch.int64, pin_memory=True)
+            pinned.numpy()[:] = rows
+            d_rows = pinned.to(self.device, non_blocking=True)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            ops.strip_batch(self.pixels, self.offset, self.h, self.w, d_rows, self.table, out, anchor)
+            return out
+        res = torch.from_numpy(strip_batch_spec(self.pixels, self.offset, self.h, self.w, self.table, rows, OH, OW, anchor))
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+
+
+def strip_batch_spec(pixels, offset, h, w, table, rows, OH, OW, anchor="centre"):
+    """numpy specification of qea_strip_batch: the packed items `rows` -> fp32 [B,1,OH,OW]."""
+    res = np.ones((len(rows), 1, OH, OW), dtype=np.float32)
+    for b, s in enumerate(rows):
+        sh, sw = int(h[s]), int(w[s])
+        hh, ww = min(sh, OH), min(sw, OW)
+        top = (OH - hh) // 2
+        left = 0 if anchor == "left" else (OW - ww) // 2
+        item = pixels[offset[s]: offset[s] + sh * sw].reshape(sh, sw)
+        res[b, 0, top:top + hh, left:left + ww] = table[item[:hh, :ww]]
+    return res
+
+
+class ResidentStrips(_PackedStore):
+    def __init__(self, dataset, size, device="cpu", max_gb=8.0, _packed=None):
+        if not isinstance(dataset, ImgDataset):
+            raise QeaError(f"ResidentStrips packs an ImgDataset, not a {type(dataset).__name__}")
+        self.H, self.W = _size(size)
+        self._open(device, max_gb)
+        files = list(dataset.files)
+        self.n = len(files)
+        self.names = [os.path.basename(f) for f in files]
+        self.labels = [_label(f) for f in files]
+        self.lens = np.array([len(l) for l in self.labels], dtype=np.int32)
+        t0 = time.perf_counter()
+        host = self._pack(_decode(f, self.H, self.W) for f in files) if _packed is None else _packed
+        self.build_seconds = time.perf_counter() - t0
+        self._place(host)
+
+    @classmethod
+    def load_or_build(cls, dataset, size, pack_path, device="cpu", max_gb=8.0):
+        """The store of `dataset` through the pack file at `pack_path` (.npz: pixels, offset, h, w, names, labels, signature).  A pack
+        whose signature is not this dataset's (a file added, removed, resized or rewritten, another target size or format) is never
+        used: the store is rebuilt from the files and the pack overwritten."""
+        return cls._load_or_build(len(dataset.files), pack_path, _signature(dataset.files, *_size(size)),
+                                  lambda packed: cls(dataset, size, device=device, max_gb=max_gb, _packed=packed))
+
+    def _pack_extras(self):
+        return dict(names=np.array(self.names, dtype=str), labels=np.array(self.labels, dtype=str))
 
     def batch(self, idx, out_w=None, anchor="centre", out=None):
         """fp32 [B,1,H,out_w] (out_w defaults to W) on the store's device; `out` (optional) receives it.  anchor="centre": PadWhite's
@@ -183,7 +244,7 @@ class ResidentStrips:
         first out_w columns (datasets.bucketing.pad_to_bucket).  Indices are checked on the host: ValueError before any launch."""
         if anchor not in ANCHORS:
             raise ValueError(f"unknown anchor {anchor!r}")
-        idx = self._indices(idx)
+        idx = self._rows(idx, "batch", noun="indices", device_tensor=False)
         OW = self.W if out_w is None else int(out_w)
         if OW < 4 or OW % 4:
             raise ValueError(f"ResidentStrips.batch: out_w={OW} must be a positive multiple of 4")
@@ -191,30 +252,7 @@ class ResidentStrips:
         if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device.type != self.device.type
                                 or not out.is_contiguous()):
             raise ValueError(f"ResidentStrips.batch: out must be a contiguous fp32 {shape} tensor on {self.device}")
-        if self.device.type == "cuda":
-            from qea import ops
-            # a fresh pinned block per call: the caching host allocator hands it out again only after the copy below has run, so
-            # neither a wait nor a second buffer is needed
-            pinned = torch.empty(idx.size, dtype=torch.int64, pin_memory=True)
-            pinned.numpy()[:] = idx
-            d_idx = pinned.to(self.device, non_blocking=True)
-            if out is None:
-                out = torch.empty(shape, dtype=torch.float32, device=self.device)
-            ops.strip_batch(self.pixels, self.offset, self.h, self.w, d_idx, self.table, out, anchor)
-            return out
-        res = np.ones(shape, dtype=np.float32)
-        for b, s in enumerate(idx):
-            h, w = int(self.h[s]), int(self.w[s])
-            hh, ww = min(h, self.H), min(w, OW)
-            top = (self.H - hh) // 2
-            left = 0 if anchor == "left" else (OW - ww) // 2
-            strip = self.pixels[self.offset[s]: self.offset[s] + h * w].reshape(h, w)
-            res[b, 0, top:top + hh, left:left + ww] = self.table[strip[:hh, :ww]]
-        res = torch.from_numpy(res)
-        if out is not None:
-            out.copy_(res)
-            return out
-        return res
+        return self._batch(idx, self.H, OW, anchor, out)
 
 
 class _Indices(torch.utils.data.Dataset):
@@ -228,11 +266,25 @@ class _Indices(torch.utils.data.Dataset):
         return i
 
 
-class ResidentLoader:
-    """The DataLoader of `dataset` (an ImgDataset, or a Subset of one, whose strips sit in `store`) with the sampling left to torch:
-    a DataLoader over the indices 0..len(dataset)-1 with the caller's batch_size / drop_last / sampler / shuffle draws the same index
-    batches, in the same order and with the same use of the global generator, as one over the samples; each index batch then becomes
-    the list the sample loader collates: [images (on the store's device), labels, names (if include_name), indices (if include_index)]."""
+class _IndexLoader:
+    """The DataLoader of `dataset`, whose items sit in `store`, with the sampling left to torch: a DataLoader over the indices
+    0..len(dataset)-1 with the caller's batch_size / drop_last / sampler / shuffle draws the same index batches, in the same order and
+    with the same use of the global generator, as one over the samples.  A subclass turns each index batch into the sample loader's."""
+
+    def __init__(self, dataset, store, loader_kw):
+        if loader_kw.get("num_workers") or "collate_fn" in loader_kw or "batch_sampler" in loader_kw:
+            raise QeaError(f"{type(self).__name__} takes batch_size, drop_last and sampler or shuffle only")
+        self.dataset, self.store = dataset, store
+        self._indices = torch.utils.data.DataLoader(_Indices(len(dataset)), **loader_kw)
+        self.batch_size, self.sampler = self._indices.batch_size, self._indices.sampler
+
+    def __len__(self):
+        return len(self._indices)
+
+
+class ResidentLoader(_IndexLoader):
+    """The index loader of an ImgDataset, or of a Subset of one, whose strips sit in `store`: each index batch becomes the list the
+    sample loader collates: [images (on the store's device), labels, names (if include_name), indices (if include_index)]."""
 
     def __init__(self, dataset, store, **loader_kw):
         base, self._remap = dataset, None
@@ -240,15 +292,8 @@ class ResidentLoader:
             base, self._remap = dataset.dataset, np.asarray(list(dataset.indices), dtype=np.int64)
         if not isinstance(base, ImgDataset) or [os.path.basename(f) for f in base.files] != store.names:
             raise QeaError("ResidentLoader: the store was not built from this dataset")
-        if loader_kw.get("num_workers") or "collate_fn" in loader_kw or "batch_sampler" in loader_kw:
-            raise QeaError("ResidentLoader takes batch_size, drop_last and sampler or shuffle only")
-        self.dataset, self.store = dataset, store
+        super().__init__(dataset, store, loader_kw)
         self.include_name, self.include_index = base.include_name, base.include_index
-        self._indices = torch.utils.data.DataLoader(_Indices(len(dataset)), **loader_kw)
-        self.batch_size, self.sampler = self._indices.batch_size, self._indices.sampler
-
-    def __len__(self):
-        return len(self._indices)
 
     def __iter__(self):
         for indices in self._indices:                                         # int64 [B], as default_collate makes of the samples' idx
@@ -324,15 +369,8 @@ def _decode_doc(dataset, path):
 
 def _doc_signature(dataset):
     """_signature's rows of every image AND of its .json, with the canvas and the dataset's resize flag."""
-    files = list(dataset.files)
-    root = os.path.commonpath([os.path.dirname(os.path.abspath(f)) for f in files]) if files else ""
-    rows = []
-    for f in files:
-        for g in (f, f.rsplit(".", 1)[0] + ".json"):
-            st = os.stat(g)
-            rows.append([os.path.relpath(os.path.abspath(g), root), st.st_size, st.st_mtime_ns])
     return hashlib.sha256(json.dumps({"format": DOC_PACK_FORMAT, "size": list(dataset.size), "resize": bool(dataset.resize_images),
-                                      "files": rows}).encode()).hexdigest()
+                                      "files": _stat_rows(list(dataset.files), with_json=True)}).encode()).hexdigest()
 
 
 class DocBoxes(list):
@@ -345,10 +383,11 @@ class DocBoxes(list):
         self.store, self.rows = store, [int(r) for r in rows]
 
 
-class ResidentDocuments:
+class ResidentDocuments(_PackedStore):
     """Every document of a PatchDataset (pad=True) decoded ONCE: pixels as the dataset has them before the white pad, boxes as its
     coord_loader returns them.  batch(rows) is torch.stack([dataset[i][0] for i in rows]) bit for bit; crops(images, rows, oh, ow)
     cuts all boxes of those documents out of `images`.  device="cpu": numpy tables and the numpy specification of both."""
+    PACKED = _PackedStore.PACKED + ("src",)           # src int32 [n][2]: the (h, w) of every source image
 
     def __init__(self, dataset, device="cpu", max_gb=8.0, _packed=None):
         from datasets.patch_dataset import PatchDataset
@@ -358,24 +397,23 @@ class ResidentDocuments:
             raise QeaError("ResidentDocuments needs a PatchDataset with pad=True: unpadded documents have no common canvas")
         self.dataset = dataset
         self.H, self.W = dataset.size
-        self.device = torch.device(device)
-        if self.device.type not in ("cpu", "cuda"):
-            raise QeaError(f"ResidentDocuments: device {device!r} is neither cpu nor cuda")
-        self.max_gb = float(max_gb)
+        self._open(device, max_gb)
         self.paths = list(dataset.files)
         self.n = len(self.paths)
         if not self.n:
             raise QeaError("ResidentDocuments: the dataset lists no document")
         t0 = time.perf_counter()
         if _packed is None:
-            pixels, offset, h, w, src = self._pack()
-        else:
-            pixels, offset, h, w, src = _packed
-            self._guard(pixels.size)
-        self.nbytes = int(pixels.size)
-        self._host = (pixels, offset, h, w, src)                              # what a pack file holds
+            src = []                                                          # the source sizes, noted as _pack walks the documents
+
+            def decoded():
+                for f in self.paths:
+                    a, hw = _decode_doc(dataset, f)
+                    src.append(hw)
+                    yield a
+            _packed = self._pack(decoded()) + (np.array(src, dtype=np.int32).reshape(-1, 2),)
         self.boxes, self.branch = [], []
-        for f, (sh, sw) in zip(self.paths, src.tolist()):
+        for f, (sh, sw) in zip(self.paths, _packed[4].tolist()):
             top, left, sx, sy, how = _doc_geometry(dataset, f, sw, sh)
             self.boxes.append(dataset.coord_loader(f, top, left, sx, sy))     # filtering, shifting and the placeholder stay the dataset's
             self.branch.append(how)
@@ -386,36 +424,9 @@ class ResidentDocuments:
         box = np.array([[max(0, b["x_min"]), max(0, b["y_min"]), min(self.W, b["x_max"]), min(self.H, b["y_max"])]
                         for boxes in self.boxes for b in boxes], dtype=np.int32).reshape(-1, 4)
         self.build_seconds = time.perf_counter() - t0
-        table = norm_table()
-        if self.device.type == "cuda":
-            from qea import _lib
-            _lib.lib()                                                        # a missing kernel is an error here, not at the first batch
-            up = lambda a: torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(self.device)
-            self.pixels, self.offset, self.h, self.w, self.table = up(pixels), up(offset), up(h), up(w), up(table)
-            self.box, self.box_first = up(box), up(box_first)
-        else:
-            self.pixels, self.offset, self.h, self.w, self.table, self.box, self.box_first = pixels, offset, h, w, table, box, box_first
+        self._place(_packed, box=box, box_first=box_first)
         self._host_box, self._host_box_first = box, box_first
         self._self_check()
-
-    def __len__(self):
-        return self.n
-
-    _guard = ResidentStrips._guard
-
-    def _pack(self):
-        chunks, total = [], 0
-        offset = np.zeros(self.n, dtype=np.int64)
-        h = np.zeros(self.n, dtype=np.int32)
-        w = np.zeros(self.n, dtype=np.int32)
-        src = np.zeros((self.n, 2), dtype=np.int32)
-        for i, f in enumerate(self.paths):
-            a, src[i] = _decode_doc(self.dataset, f)
-            offset[i], h[i], w[i] = total, a.shape[0], a.shape[1]
-            chunks.append(a.reshape(-1))
-            total += a.size
-            self._guard(total)                                                # refuse as soon as the limit is passed, not after the decode
-        return np.concatenate(chunks), offset, h, w, src
 
     def _self_check(self):
         """The store against the dataset's own samples: the first and the last document and every one stored through an oversize
@@ -429,66 +440,22 @@ class ResidentDocuments:
             if sample[1] != self.boxes[i]:
                 raise QeaError(f"--resident: document {self.paths[i]} comes out of the store with other boxes than out of the dataset")
 
-    # ---- the pack file ----
     @classmethod
     def load_or_build(cls, dataset, pack_path, device="cpu", max_gb=8.0):
         """The store of `dataset` through the pack file at `pack_path` (.npz: pixels, offset, h, w, src, paths, signature).  A pack
         whose signature is not this dataset's (an image or a .json added, removed, resized or rewritten, another canvas or format) is
         never used: the store is rebuilt from the files and the pack overwritten.  Boxes are not packed: they are read from the
         .json files by the dataset's coord_loader either way."""
-        sig = _doc_signature(dataset)
-        packed = None
-        if pack_path and os.path.exists(pack_path):
-            try:
-                with np.load(pack_path, allow_pickle=False) as z:
-                    if str(z["signature"]) == sig and len(z["offset"]) == len(dataset.files):
-                        packed = (z["pixels"], z["offset"], z["h"], z["w"], z["src"])
-            except (OSError, ValueError, KeyError):
-                packed = None                                                 # unreadable or foreign file: rebuild
-        store = cls(dataset, device=device, max_gb=max_gb, _packed=packed)
-        store.from_pack = packed is not None
-        if packed is None and pack_path:
-            store.save(pack_path, sig)
-        return store
+        return cls._load_or_build(len(dataset.files), pack_path, _doc_signature(dataset),
+                                  lambda packed: cls(dataset, device=device, max_gb=max_gb, _packed=packed))
 
-    def save(self, pack_path, signature=None):
-        pixels, offset, h, w, src = self._host
-        tmp = f"{pack_path}.tmp{os.getpid()}"
-        os.makedirs(os.path.dirname(os.path.abspath(pack_path)), exist_ok=True)
-        with open(tmp, "wb") as f:
-            np.savez(f, pixels=pixels, offset=offset, h=h, w=w, src=src, paths=np.array(self.paths, dtype=str),
-                     signature=np.array(signature or ""), size=np.array([self.H, self.W], dtype=np.int32))
-        os.replace(tmp, pack_path)
-
-    # ---- batches ----
-    def _rows(self, rows, what):
-        if isinstance(rows, torch.Tensor):
-            rows = rows.cpu().numpy()
-        rows = np.ascontiguousarray(np.asarray(list(rows) if not isinstance(rows, np.ndarray) else rows).reshape(-1)).astype(np.int64, copy=False)
-        if rows.size == 0:
-            raise ValueError(f"ResidentDocuments.{what}: no rows")
-        if int(rows.min()) < 0 or int(rows.max()) >= self.n:
-            raise ValueError(f"ResidentDocuments.{what}: rows {int(rows.min())}..{int(rows.max())} outside 0..{self.n - 1}")
-        return rows
+    def _pack_extras(self):
+        return dict(paths=np.array(self.paths, dtype=str))
 
     def batch(self, rows):
         """fp32 [N,1,H,W] on the store's device: documents `rows` centred on the white canvas, the dataset's own samples bit for bit.
         On the device one launch of qea_strip_batch (OH = H, OW = W, centre anchor)."""
-        rows = self._rows(rows, "batch")
-        shape = (rows.size, 1, self.H, self.W)
-        if self.device.type == "cuda":
-            from qea import ops
-            pinned = torch.empty(rows.size, dtype=torch.int64, pin_memory=True)   # a fresh block per call, see ResidentStrips.batch
-            pinned.numpy()[:] = rows
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-            ops.strip_batch(self.pixels, self.offset, self.h, self.w, pinned.to(self.device, non_blocking=True), self.table, out, "centre")
-            return out
-        res = np.ones(shape, dtype=np.float32)
-        for b, s in enumerate(rows):
-            h, w = int(self.h[s]), int(self.w[s])
-            top, left = (self.H - h) // 2, (self.W - w) // 2
-            res[b, 0, top:top + h, left:left + w] = self.table[self.pixels[self.offset[s]: self.offset[s] + h * w].reshape(h, w)]
-        return torch.from_numpy(res)
+        return self._batch(self._rows(rows, "batch"), self.H, self.W)
 
     def strip_tables(self, rows):
         """(doc int64 [N], strip_first int32 [N+1]) of a step on documents `rows`, as host arrays."""
@@ -513,7 +480,7 @@ class ResidentDocuments:
         if self.device.type == "cuda":
             if not images.is_cuda:
                 raise ValueError("ResidentDocuments.crops: a device store cuts device images")
-            # doc and strip_first in ONE pinned block and one non-blocking copy (fresh per call, see ResidentStrips.batch)
+            # doc and strip_first in ONE pinned block and one non-blocking copy (fresh per call, see _PackedStore._batch)
             N = doc.size
             pinned = torch.empty(8 * N + 4 * (N + 1), dtype=torch.uint8, pin_memory=True)
             pinned[:8 * N].view(torch.int64).numpy()[:] = doc
@@ -575,24 +542,16 @@ class _DocCropsHost(torch.autograd.Function):
         return torch.from_numpy(d)[:, None], None, None, None, None, None, None
 
 
-class ResidentDocLoader:
-    """The DataLoader of a PatchDataset whose documents sit in `store`, with the sampling left to torch (see ResidentLoader): a
-    DataLoader over the indices with the caller's batch_size / drop_last / sampler / shuffle draws the same index batches, in the same
-    order and with the same use of the global generator, as DataLoader(dataset, collate_fn=PatchDataset.collate, ...).  Each batch is
-    [images on the store's device, DocBoxes (the box lists, with the store and the rows), paths (if include_name)]."""
+class ResidentDocLoader(_IndexLoader):
+    """The index loader of a PatchDataset whose documents sit in `store`: the same index batches as
+    DataLoader(dataset, collate_fn=PatchDataset.collate, ...).  Each batch is [images on the store's device, DocBoxes (the box lists,
+    with the store and the rows), paths (if include_name)]."""
 
     def __init__(self, dataset, store, **loader_kw):
         if store.dataset is not dataset and list(dataset.files) != store.paths:
             raise QeaError("ResidentDocLoader: the store was not built from this dataset")
-        if loader_kw.get("num_workers") or "collate_fn" in loader_kw or "batch_sampler" in loader_kw:
-            raise QeaError("ResidentDocLoader takes batch_size, drop_last and sampler or shuffle only")
-        self.dataset, self.store = dataset, store
+        super().__init__(dataset, store, loader_kw)
         self.include_name = dataset.include_name
-        self._indices = torch.utils.data.DataLoader(_Indices(len(dataset)), **loader_kw)
-        self.batch_size, self.sampler = self._indices.batch_size, self._indices.sampler
-
-    def __len__(self):
-        return len(self._indices)
 
     def __iter__(self):
         for indices in self._indices:

@@ -966,6 +966,23 @@ def ctc_history_loss(lp, input_lengths, lens, offs, chars, depth_n, weights, w_s
     return loss, grad, nll
 
 
+def _tensors(who, device, *specs):
+    """The tensor checks of the gather / scatter wrappers below -> the tensors' device pointers, in order.  A spec is (name, tensor,
+    dtype[, element count]): every tensor is of its dtype, contiguous and on the CUDA device `device`, and has that many elements where
+    a count is given, or a QeaError names the caller, the tensor and what is wrong with it.  (These wrappers sit between the device
+    events of 15 us launches: one pass, no second look at a tensor that is right.)"""
+    if device.type != "cuda":
+        raise _lib.QeaError(f"{who} needs CUDA tensors (there is no CPU path), not {device}")
+    ptrs = []
+    for spec in specs:
+        t = spec[1]
+        if t.dtype is not spec[2] or t.device != device or not t.is_contiguous() or (len(spec) > 3 and t.numel() != spec[3]):
+            raise _lib.QeaError(f"{who}: {spec[0]} must be a contiguous {spec[2]} tensor on {device}" + (f" of {spec[3]} elements" if len(spec) > 3 else "")
+                                + f", not {'a' if t.is_contiguous() else 'a strided'} {t.dtype} tensor on {t.device} of {t.numel()} elements")
+        ptrs.append(t.data_ptr())
+    return ptrs
+
+
 STRIP_ANCHORS = {"centre": 0, "left": 1}     # QEA_STRIP_ANCHOR_* of include/qea_hip.h
 STRIP_LAUNCHES = {"batch": 0}                # launches of csrc/strip_batch.hip issued through this module (tests, tools)
 
@@ -975,17 +992,13 @@ def strip_batch(pixels, offset, h, w, idx, table, out, anchor="centre"):
     idx (int64 [B]) and the 256-entry fp32 table -> out [B][1][OH][OW] fp32, written whole by ONE launch on the current stream."""
     if anchor not in STRIP_ANCHORS:
         raise ValueError(f"unknown anchor {anchor!r}")
-    if (pixels.dtype != torch.uint8 or offset.dtype != torch.int64 or h.dtype != torch.int32 or w.dtype != torch.int32
-            or idx.dtype != torch.int64 or table.dtype != torch.float32 or out.dtype != torch.float32):
-        raise _lib.QeaError("strip_batch needs uint8 pixels, int64 offsets and indices, int32 heights and widths, an fp32 table and output")
-    if not all(t.is_contiguous() for t in (pixels, offset, h, w, idx, table, out)):
-        raise _lib.QeaError("strip_batch needs contiguous tensors")
     n, B = offset.numel(), idx.numel()
-    if h.numel() != n or w.numel() != n or table.numel() != 256 or out.dim() != 4 or out.shape[0] != B or out.shape[1] != 1:
-        raise _lib.QeaError(f"strip_batch: {n} offsets, {h.numel()} / {w.numel()} sizes, a table of {table.numel()}, out {tuple(out.shape)} for "
-                            f"{B} indices")
-    _lib.check(_lib.lib().qea_strip_batch(_ptr(pixels), _ptr(offset), _ptr(h), _ptr(w), n, _ptr(idx), B, out.shape[2], out.shape[3],
-                                          STRIP_ANCHORS[anchor], _ptr(table), _ptr(out), _stream()), "qea_strip_batch")
+    p = _tensors("strip_batch", out.device, ("pixels", pixels, torch.uint8), ("offset", offset, torch.int64), ("h", h, torch.int32, n),
+                 ("w", w, torch.int32, n), ("idx", idx, torch.int64), ("table", table, torch.float32, 256), ("out", out, torch.float32))
+    if out.dim() != 4 or out.shape[0] != B or out.shape[1] != 1:
+        raise _lib.QeaError(f"strip_batch: out {tuple(out.shape)} for {B} indices")
+    _lib.check(_lib.lib().qea_strip_batch(p[0], p[1], p[2], p[3], n, p[4], B, out.shape[2], out.shape[3], STRIP_ANCHORS[anchor], p[5], p[6],
+                                          _stream()), "qea_strip_batch")
     STRIP_LAUNCHES["batch"] += 1
 
 
@@ -993,15 +1006,8 @@ DOC_LAUNCHES = {"gather": 0, "scatter": 0}    # launches of csrc/doc_crops.hip i
 
 
 def _doc_tables(who, box, box_first, doc, strip_first, imgs, strips):
-    """The argument checks the two entry points of csrc/doc_crops.hip share; -> (N, H, W, n_docs, n_boxes, S, OH, OW)."""
-    tensors = (box, box_first, doc, strip_first, imgs, strips)
-    if (box.dtype != torch.int32 or box_first.dtype != torch.int32 or doc.dtype != torch.int64 or strip_first.dtype != torch.int32
-            or imgs.dtype != torch.float32 or strips.dtype != torch.float32):
-        raise _lib.QeaError(f"{who} needs int32 boxes, box_first and strip_first, int64 doc, fp32 images and strips")
-    if not all(t.is_cuda and t.device == imgs.device for t in tensors):
-        raise _lib.QeaError(f"{who} needs all its tensors on one CUDA device")
-    if not all(t.is_contiguous() for t in tensors):
-        raise _lib.QeaError(f"{who} needs contiguous tensors")
+    """The argument checks the two entry points of csrc/doc_crops.hip share; -> (pointers of box, box_first, doc, strip_first, imgs and
+    strips, (N, H, W), n_docs, n_boxes, (S, OH, OW))."""
     if imgs.dim() == 4 and imgs.shape[1] == 1:
         N, _, H, W = imgs.shape
     elif imgs.dim() == 3:
@@ -1011,62 +1017,61 @@ def _doc_tables(who, box, box_first, doc, strip_first, imgs, strips):
     if strips.dim() != 4 or strips.shape[1] != 1:
         raise _lib.QeaError(f"{who}: strips {tuple(strips.shape)} are not [S,1,OH,OW]")
     S, _, OH, OW = strips.shape
+    p = _tensors(who, imgs.device, ("box", box, torch.int32), ("box_first", box_first, torch.int32), ("doc", doc, torch.int64, N),
+                 ("strip_first", strip_first, torch.int32, N + 1), ("images", imgs, torch.float32), ("strips", strips, torch.float32))
     n_docs = box_first.numel() - 1
-    if box.dim() != 2 or box.shape[1] != 4 or n_docs < 1 or doc.numel() != N or strip_first.numel() != N + 1:
-        raise _lib.QeaError(f"{who}: boxes {tuple(box.shape)}, {box_first.numel()} box_first, {doc.numel()} doc and {strip_first.numel()} "
-                            f"strip_first entries for {N} images")
-    return N, H, W, n_docs, box.shape[0], S, OH, OW
+    if box.dim() != 2 or box.shape[1] != 4 or n_docs < 1:
+        raise _lib.QeaError(f"{who}: boxes {tuple(box.shape)} are not [total][4], or fewer than two box_first entries ({box_first.numel()})")
+    return p, (N, H, W), n_docs, box.shape[0], (S, OH, OW)
 
 
 def doc_crops_gather(imgs, box, box_first, doc, strip_first, out):
     """include/qea_hip.h: qea_doc_crops_gather — imgs [N,1,H,W] fp32, the store's box / box_first, doc (int64 [N]) and strip_first
     (int32 [N+1]) -> out [S,1,OH,OW], every strip of the step, written whole by ONE launch on the current stream."""
-    N, H, W, n_docs, n_boxes, S, OH, OW = _doc_tables("doc_crops_gather", box, box_first, doc, strip_first, imgs, out)
-    _lib.check(_lib.lib().qea_doc_crops_gather(_ptr(imgs), N, H, W, _ptr(box), _ptr(box_first), n_docs, n_boxes, _ptr(doc), _ptr(strip_first),
-                                               S, OH, OW, _ptr(out), _stream()), "qea_doc_crops_gather")
+    (box, box_first, doc, strip_first, imgs, out), image, n_docs, n_boxes, strip = _doc_tables("doc_crops_gather", box, box_first, doc,
+                                                                                              strip_first, imgs, out)
+    _lib.check(_lib.lib().qea_doc_crops_gather(imgs, *image, box, box_first, n_docs, n_boxes, doc, strip_first, *strip, out, _stream()),
+               "qea_doc_crops_gather")
     DOC_LAUNCHES["gather"] += 1
 
 
 def doc_crops_scatter(dout, box, box_first, doc, strip_first, dimg, accumulate=False):
     """include/qea_hip.h: qea_doc_crops_scatter — dout [S,1,OH,OW] -> dimg [N,1,H,W], written whole (or added to, `accumulate`) by ONE
     launch without atomics: per pixel the sum over the covering boxes in ascending box order."""
-    N, H, W, n_docs, n_boxes, S, OH, OW = _doc_tables("doc_crops_scatter", box, box_first, doc, strip_first, dimg, dout)
-    _lib.check(_lib.lib().qea_doc_crops_scatter(_ptr(dout), S, OH, OW, _ptr(box), _ptr(box_first), n_docs, n_boxes, _ptr(doc),
-                                                _ptr(strip_first), _ptr(dimg), N, H, W, int(bool(accumulate)), _stream()),
-               "qea_doc_crops_scatter")
+    (box, box_first, doc, strip_first, dimg, dout), image, n_docs, n_boxes, strip = _doc_tables("doc_crops_scatter", box, box_first, doc,
+                                                                                               strip_first, dimg, dout)
+    _lib.check(_lib.lib().qea_doc_crops_scatter(dout, *strip, box, box_first, n_docs, n_boxes, doc, strip_first, dimg, *image,
+                                                int(bool(accumulate)), _stream()), "qea_doc_crops_scatter")
     DOC_LAUNCHES["scatter"] += 1
 
 
 PAGE_LAUNCHES = {"gather": 0, "scatter": 0}   # launches of csrc/page_tiles.hip issued through this module (tests, tools)
 
 
-def _page_tables(who, offset, h, w, rows, cols, tiles):
-    """The argument checks the two entry points of csrc/page_tiles.hip share; -> (n_pages, N, TH, TW)."""
-    if offset.dtype != torch.int64 or h.dtype != torch.int32 or w.dtype != torch.int32 or rows.dtype != torch.int32 or tiles.dtype != torch.float32:
-        raise _lib.QeaError(f"{who} needs int64 offsets, int32 heights, widths and tile rows, fp32 tiles")
-    if not all(t.is_cuda and t.device == tiles.device for t in (offset, h, w, rows)):
-        raise _lib.QeaError(f"{who} needs all its tensors on one CUDA device")
-    if not all(t.is_contiguous() for t in (offset, h, w, rows, tiles)):
-        raise _lib.QeaError(f"{who} needs contiguous tensors")
+def _page_tables(who, offset, h, w, rows, cols, tiles, *more):
+    """The argument checks the two entry points of csrc/page_tiles.hip share (`more`: the specs of their own tensors);
+    -> (pointers of offset, h, w, rows, tiles and `more`, n_pages, (N, TH, TW))."""
     n = offset.numel()
-    if h.numel() != n or w.numel() != n or rows.dim() != 2 or rows.shape[1] != cols or tiles.dim() != 4 or tiles.shape[1] != 1 or tiles.shape[0] != rows.shape[0]:
-        raise _lib.QeaError(f"{who}: {n} offsets, {h.numel()} / {w.numel()} sizes, tile rows {tuple(rows.shape)} (want [N][{cols}]), "
-                            f"tiles {tuple(tiles.shape)} (want [N,1,TH,TW])")
-    return n, tiles.shape[0], tiles.shape[2], tiles.shape[3]
+    p = _tensors(who, tiles.device, ("offset", offset, torch.int64), ("h", h, torch.int32, n), ("w", w, torch.int32, n),
+                 ("tile rows", rows, torch.int32), ("tiles", tiles, torch.float32), *more)
+    if rows.dim() != 2 or rows.shape[1] != cols or tiles.dim() != 4 or tiles.shape[1] != 1 or tiles.shape[0] != rows.shape[0]:
+        raise _lib.QeaError(f"{who}: tile rows {tuple(rows.shape)} (want [N][{cols}]), tiles {tuple(tiles.shape)} (want [N,1,TH,TW])")
+    return p, n, (tiles.shape[0], tiles.shape[2], tiles.shape[3])
 
 
 def page_tiles_gather(store, offset, h, w, rows, out, table=None):
     """include/qea_hip.h: qea_page_tiles_gather — the packed pages `store` (uint8 with the 256-entry fp32 `table`, or fp32), their element
     offset (int64 [n]) and h / w (int32 [n]), the tile rows (int32 [N][3] = page, oy, ox) -> out [N,1,TH,TW] fp32, white outside a page,
     written whole by ONE launch on the current stream."""
-    n, N, TH, TW = _page_tables("page_tiles_gather", offset, h, w, rows, 3, out)
-    if store.dtype not in (torch.uint8, torch.float32) or store.dim() != 1 or not store.is_contiguous() or store.device != out.device:
-        raise _lib.QeaError("page_tiles_gather needs a one-dimensional contiguous uint8 or float32 store on the tiles' device")
-    if store.dtype == torch.uint8 and (table is None or table.dtype != torch.float32 or table.numel() != 256 or not table.is_contiguous()
-                                       or table.device != out.device):
-        raise _lib.QeaError("page_tiles_gather: a uint8 store needs a contiguous 256-entry fp32 table on the same device")
-    _lib.check(_lib.lib().qea_page_tiles_gather(_ptr(store), int(store.dtype == torch.float32), store.numel(), _ptr(offset), _ptr(h), _ptr(w), n,
-                                                _ptr(rows), N, TH, TW, _ptr(table), _ptr(out), _stream()), "qea_page_tiles_gather")
+    if store.dtype not in (torch.uint8, torch.float32) or store.dim() != 1:
+        raise _lib.QeaError("page_tiles_gather needs a one-dimensional uint8 or float32 store")
+    if store.dtype == torch.uint8 and table is None:
+        raise _lib.QeaError("page_tiles_gather: a uint8 store needs the 256-entry fp32 table")
+    (offset, h, w, rows, out, store_p, *table_p), n, tile = _page_tables(
+        "page_tiles_gather", offset, h, w, rows, 3, out, ("store", store, store.dtype),
+        *([("table", table, torch.float32, 256)] if table is not None else []))
+    _lib.check(_lib.lib().qea_page_tiles_gather(store_p, int(store.dtype == torch.float32), store.numel(), offset, h, w, n, rows, *tile,
+                                                table_p[0] if table_p else None, out, _stream()), "qea_page_tiles_gather")
     PAGE_LAUNCHES["gather"] += 1
 
 
@@ -1074,15 +1079,15 @@ def page_tiles_scatter(tiles, rows, offset, h, w, out_f32=None, out_u8=None):
     """include/qea_hip.h: qea_page_tiles_scatter — tiles [N,1,TH,TW] fp32 and the tile rows (int32 [N][7] = page, oy, ox, cy0, cy1, cx0, cx1)
     -> the core of every tile pasted into the packed outputs (out_f32 fp32 and / or out_u8 uint8, one-dimensional, as large as each other)
     by ONE launch without atomics; the 8-bit value is (uint8)(min(max(x, 0), 1) * 255)."""
-    n, N, TH, TW = _page_tables("page_tiles_scatter", offset, h, w, rows, 7, tiles)
-    outs = [(o, dt) for o, dt in ((out_f32, torch.float32), (out_u8, torch.uint8)) if o is not None]
+    outs = [(name, o, dt) for name, o, dt in (("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8)) if o is not None]
     if not outs:
         raise _lib.QeaError("page_tiles_scatter needs out_f32, out_u8 or both")
-    for o, dt in outs:
-        if o.dtype != dt or o.dim() != 1 or not o.is_contiguous() or o.device != tiles.device or o.numel() != outs[0][0].numel():
-            raise _lib.QeaError("page_tiles_scatter needs one-dimensional contiguous outputs (float32 / uint8) of one size on the tiles' device")
-    _lib.check(_lib.lib().qea_page_tiles_scatter(_ptr(tiles), N, TH, TW, _ptr(rows), _ptr(offset), _ptr(h), _ptr(w), n, outs[0][0].numel(),
-                                                 _ptr(out_f32), _ptr(out_u8), _stream()), "qea_page_tiles_scatter")
+    if any(o.dim() != 1 for _, o, _ in outs):
+        raise _lib.QeaError("page_tiles_scatter needs one-dimensional outputs")
+    size = outs[0][1].numel()
+    (offset, h, w, rows, tiles, *_), n, tile = _page_tables("page_tiles_scatter", offset, h, w, rows, 7, tiles, *(spec + (size,) for spec in outs))
+    _lib.check(_lib.lib().qea_page_tiles_scatter(tiles, *tile, rows, offset, h, w, n, size, _ptr(out_f32), _ptr(out_u8), _stream()),
+               "qea_page_tiles_scatter")
     PAGE_LAUNCHES["scatter"] += 1
 
 

@@ -240,6 +240,34 @@ def test_abi_has_the_two_entry_points():
     assert b"16-byte" in L.qea_last_error()
 
 
+def test_pack_files_hold_exactly_their_keys(tmp_path, dataset):
+    """The two .npz layouts (format 1 of each): a pack written by an earlier version loads, and an earlier version loads these."""
+    import resident_fixture as RF
+    from datasets.img_dataset import ImgDataset
+    from datasets.resident import DOC_PACK_FORMAT, PACK_FORMAT, ResidentDocuments, ResidentStrips
+    assert PACK_FORMAT == 1 and DOC_PACK_FORMAT == 1
+    RF.write_strips(str(tmp_path / "strips"))
+    ResidentStrips.load_or_build(ImgDataset(str(tmp_path / "strips")), RF.SIZE, str(tmp_path / "strips.npz"))
+    ResidentDocuments.load_or_build(dataset, str(tmp_path / "docs.npz"))
+    with np.load(tmp_path / "strips.npz", allow_pickle=False) as z:
+        assert sorted(z.files) == sorted(["pixels", "offset", "h", "w", "names", "labels", "signature", "size"])
+    with np.load(tmp_path / "docs.npz", allow_pickle=False) as z:
+        assert sorted(z.files) == sorted(["pixels", "offset", "h", "w", "src", "paths", "signature", "size"])
+        assert z["src"].dtype == np.int32 and z["src"].tolist() == [[h, w] for h, w, _ in DF.DOCS] and z["size"].tolist() == [H, W]
+
+
+def test_strip_store_and_document_store_agree(doc_dir, store):
+    """The documents that fit the canvas are strips of a ResidentStrips with the canvas as its size: the two stores share the packing
+    and the batch, so their batches are the same tensor."""
+    from datasets.img_dataset import ImgDataset
+    from datasets.resident import ResidentStrips
+    strips = ResidentStrips(ImgDataset(doc_dir), DF.CANVAS)
+    assert [os.path.basename(p) for p in store.paths] == strips.names
+    fit = [i for i, how in enumerate(store.branch) if how == "fit"]
+    assert len(fit) == 6
+    assert torch.equal(strips.batch(fit), store.batch(fit)) and torch.equal(strips.batch(fit[::-1] + fit), store.batch(fit[::-1] + fit))
+
+
 def _oracle_backend():
     from oracle.modules import OracleCRNN, OracleUNet
     from qea.trainer_core import Backend
