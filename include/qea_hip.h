@@ -493,6 +493,21 @@ int qea_crop_pad_scatter(const float* dout, const int32_t* boxes, int32_t N, int
 int qea_greedy_decode(const float* scores, int32_t ld_t, int32_t ld_n, int32_t T, int32_t N, int32_t C, int32_t blank,
                       int32_t* tokens, int32_t* lengths, void* stream);
 
+/* CTC prefix beam search: stands beside utils.pred_to_string (utils.py:74-92), which decodes greedily; the reference has no beam.
+ * Per sample the K most probable LABELLINGS (the alignments that spell the same text added up), best first, with their
+ * log-probabilities.  Specified in fp64 with a fixed candidate order (DESIGN.md "CTC prefix beam search"): scores element (t,n,c) at
+ * t*ld_t + n*ld_n + c is converted to fp64 exactly, a NaN counts as -inf, lse(a,b) = max(a,b) + log1p(exp(-|a-b|)); the candidates
+ * of a step are walked by (beam rank, slot) with slot 0 = the prefix itself and slot s >= 1 = the prefix plus the s-th non-blank class;
+ * an extension that is itself a beam entry is folded into that entry's slot 0; candidates of score -inf are dropped; the next beam is
+ * the K best, equal scores in candidate order (a stable sort).
+ *   tokens [N][K][T] int32: the prefix of rank k, then -1 up to T;  lengths [N][K]: its length, -1 for the ranks beyond the live
+ *   count;  beam_scores [N][K] fp64: its log-probability, -inf for those ranks.
+ * One workgroup per sample, one launch, no workspace, no atomics; every output element is written once.
+ * Refused before any launch: K outside 1..32, C outside 2..256, T outside 1..512, blank outside 0..C-1, N < 1, NULL pointers.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects it by symbol.) */
+int qea_ctc_beam_decode(const float* scores, int32_t ld_t, int32_t ld_n, int32_t T, int32_t N, int32_t C, int32_t blank, int32_t K,
+                        int32_t* tokens, int32_t* lengths, double* beam_scores, void* stream);
+
 /* Unit-cost edit distance between the greedy decode of each sample (pred_tokens [N][ldp], pred_len)
  * and its ground-truth token string (concatenated gt_tokens, gt_offsets, gt_len): the numerator of
  * utils.compare_labels' CER (utils.py:95-110, python-Levenshtein `distance`); the host divides by

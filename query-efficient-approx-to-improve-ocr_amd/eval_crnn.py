@@ -13,6 +13,10 @@ The printed lines are the reference's.  Differences, all deliberate:
     the printed average is neither a mean nor a sum; here the sum runs over all strips and is divided once, as in the area flow.
   * --show_txt without --show_orig prints the predictions (the reference reads an unassigned variable there).
   * [new] --synthetic_size N evaluates on N synthetic strips / documents (datasets/synthetic.py).
+  * [new] --beam K decodes all three flows with a CTC prefix beam search of K entries (utils.pred_to_string(beam=K): the device kernel
+    of csrc/ctc_beam.hip for CUDA scores) instead of the greedy best path: the strings are the most probable LABELLINGS.  The dict then
+    also has beam, crnn_mean_log_score (the mean log-probability of those labellings) and greedy_disagreements (the strips whose
+    greedy string differs), and one more line is printed.  Without the flag nothing changes.
   * The loaders run in the main process (the reference asks for properties.num_workers workers).
 `backend` / `dataset` / `ocr` are injection seams for tests, as in the trainers; the default backend is the HIP path.
 """
@@ -35,6 +39,8 @@ class EvalCRNN:
         self.ocr_name = args.ocr
         self.dataset_name = args.dataset
         self.show_orig = args.show_orig
+        self.beam = int(getattr(args, "beam", 0) or 0)               # [new] --beam K: prefix beam search instead of greedy
+        self.beam_log_score, self.greedy_disagreements = 0.0, 0
         self.input_size = properties.input_size
         if self.dataset_name == "vgg":
             self.test_set = os.path.join(args.data_base_path, properties.vgg_text_dataset_test)
@@ -76,6 +82,17 @@ class EvalCRNN:
     def _scores(self, images):
         return self.crnn_model(images.to(self.device))
 
+    def _decode(self, scores, labels):
+        """The strings the CRNN reads: greedy, or with --beam K the best entry of the prefix beam search; that flow also adds up the
+        entries' log-probabilities and counts the strips that greedy reads differently."""
+        if not self.beam:
+            return pred_to_string(scores, labels, self.index_to_char)
+        preds, logp = pred_to_string(scores, labels, self.index_to_char, beam=self.beam, return_scores=True)
+        greedy = pred_to_string(scores, labels, self.index_to_char)
+        self.beam_log_score += sum(logp)
+        self.greedy_disagreements += sum(int(p != q) for p, q in zip(preds, greedy))
+        return preds
+
     def _print_labels(self, labels, pred, ori):
         print()
         print("{:<25}{:<25}{:<25}".format("GT Label", "Label for pred", "Label for original"))
@@ -87,17 +104,22 @@ class EvalCRNN:
                "crnn_cer": crnn_cer / max(1, count)}
         if self.show_orig:
             res.update(ocr_correct=ori_correct, ocr_accuracy=ori_correct / max(1, count), ocr_cer=ori_cer / max(1, count))
+        if self.beam:
+            res.update(beam=self.beam, crnn_mean_log_score=self.beam_log_score / max(1, count), greedy_disagreements=self.greedy_disagreements)
+            print("Beam {:d}: mean log-probability of the best labelling {:.5f}, differs from greedy on {:d}/{:d} strips".format(
+                self.beam, res["crnn_mean_log_score"], self.greedy_disagreements, count))
         return res
 
     def eval_area(self):
         print("Eval with ", self.ocr_name)
         self.crnn_model.eval()
+        self.beam_log_score, self.greedy_disagreements = 0.0, 0
         crnn_correct_count, ori_correct_count, ori_cer, crnn_cer = 0, 0, 0.0, 0.0
         with torch.no_grad():
             for batch in self.loader_eval:
                 images, labels = batch[0], list(batch[1])
                 scores = self._scores(images)
-                ocr_lbl_crnn = pred_to_string(scores, labels, self.index_to_char)
+                ocr_lbl_crnn = self._decode(scores, labels)
                 ocr_lbl_ori = []
                 if self.show_orig:
                     ocr_lbl_ori = self.ocr.get_labels(images.cpu())
@@ -121,6 +143,7 @@ class EvalCRNN:
     def eval_patch(self):
         print("Eval with ", self.ocr_name)
         self.crnn_model.eval()
+        self.beam_log_score, self.greedy_disagreements = 0.0, 0
         ori_lbl_crt_count, ori_lbl_cer, lbl_count, crnn_correct_count, crnn_cer = 0, 0.0, 0, 0, 0.0
         with torch.no_grad():
             for i in range(len(self.dataset)):
@@ -133,7 +156,7 @@ class EvalCRNN:
                     ori_lbl_crt_count += c
                     ori_lbl_cer += e
                 scores = self._scores(text_crops)
-                ocr_lbl_crnn = pred_to_string(scores, labels, self.index_to_char)
+                ocr_lbl_crnn = self._decode(scores, labels)
                 c, e = compare_labels(ocr_lbl_crnn, labels)
                 crnn_correct_count += c
                 crnn_cer += e

@@ -1,0 +1,100 @@
+"""CTC prefix beam search on the host: the specification of include/qea_hip.h's qea_ctc_beam_decode (DESIGN.md "CTC prefix beam
+search") as a numpy fp64 loop.  It decodes CPU tensors for utils.pred_to_string, and QEA_BEAM=host sends CUDA tensors through it too
+(an A/B switch like QEA_SAMPLER=host); the device kernel (csrc/ctc_beam.hip) returns the same beams.
+
+A beam entry is (prefix, pb, pnb): the log-probabilities of the prefix over the alignments that end in blank / in non-blank.  The
+candidates of a step are laid out as a [live, C] table: row = beam rank, column 0 = the prefix itself, column s >= 1 = the prefix
+plus the s-th non-blank class.  Row-major order of that table is the candidate order, and a stable descending sort picks the next
+beam, so equal scores keep that order.
+"""
+import math
+import os
+
+import numpy as np
+import torch
+
+MAX_K, MAX_C, MAX_T = 32, 256, 512           # the limits of qea_ctc_beam_decode
+_NEG = -math.inf
+
+
+def use_host():
+    return os.environ.get("QEA_BEAM", "device") == "host"
+
+
+def lse(a, b):
+    if a == _NEG:
+        return b
+    if b == _NEG:
+        return a
+    return max(a, b) + math.log1p(math.exp(-abs(a - b)))
+
+
+def check_limits(T, C, K, blank):
+    from ._lib import QeaError
+    if not 1 <= K <= MAX_K:
+        raise QeaError(f"ctc_beam_decode: K={K} outside 1..{MAX_K}")
+    if not 2 <= C <= MAX_C:
+        raise QeaError(f"ctc_beam_decode: C={C} outside 2..{MAX_C}")
+    if not 1 <= T <= MAX_T:
+        raise QeaError(f"ctc_beam_decode: T={T} outside 1..{MAX_T}")
+    if not 0 <= blank < C:
+        raise QeaError(f"ctc_beam_decode: blank={blank} outside 0..{C - 1}")
+
+
+def decode_sample(lp, K, blank=0):
+    """lp [T][C] float32 (numpy) -> [(prefix tuple, score)] of at most K entries, best first."""
+    T, C = lp.shape
+    lp = lp.astype(np.float64)
+    lp[np.isnan(lp)] = _NEG
+    classes = np.array([c for c in range(C) if c != blank], dtype=np.int64)          # column s of the table holds classes[s - 1]
+    column = {int(c): s + 1 for s, c in enumerate(classes)}
+    beam = [((), 0.0, _NEG)]
+    for t in range(T):
+        row = lp[t]
+        live = len(beam)
+        rank = {p: j for j, (p, _, _) in enumerate(beam)}
+        tot = [lse(pb, pnb) for _, pb, pnb in beam]
+        stay_pb = [tot[i] + row[blank] for i in range(live)]
+        stay_pnb = [beam[i][2] + row[beam[i][0][-1]] if beam[i][0] else _NEG for i in range(live)]
+        table = np.empty((live, C))
+        for i, (p, pb, _) in enumerate(beam):
+            table[i, 1:] = tot[i] + row[classes]
+            if p:
+                table[i, column[p[-1]]] = pb + row[p[-1]]                          # a repeat of the last token needs a blank between
+        for j, (p, _, _) in enumerate(beam):                                        # an extension that is entry j: fold it into j
+            i = rank.get(p[:-1]) if p else None
+            if i is not None:
+                stay_pnb[j] = lse(stay_pnb[j], float(table[i, column[p[-1]]]))
+                table[i, column[p[-1]]] = _NEG
+        table[:, 0] = [lse(stay_pb[i], stay_pnb[i]) for i in range(live)]
+        flat = table.ravel()
+        flat[np.isnan(flat)] = _NEG
+        order = np.argsort(-flat, kind="stable")[:K]
+        nxt = []
+        for idx in order.tolist():
+            if flat[idx] == _NEG:
+                break
+            i, s = divmod(idx, C)
+            if s == 0:
+                nxt.append((beam[i][0], stay_pb[i], stay_pnb[i]))
+            else:
+                nxt.append((beam[i][0] + (int(classes[s - 1]),), _NEG, float(flat[idx])))
+        beam = nxt
+    return [(p, lse(pb, pnb)) for p, pb, pnb in beam]
+
+
+def ctc_beam_decode(scores, K, blank=0):
+    """scores [T,N,C] float32 (any device) -> (tokens int32 [N,K,T], lengths int32 [N,K], scores float64 [N,K]) on the CPU, in the
+    layout of qea.ops.ctc_beam_decode: -1 behind every prefix, length -1 and score -inf in the rows beyond the live count."""
+    T, N, C = scores.shape
+    check_limits(T, C, int(K), int(blank))
+    lp = scores.detach().to("cpu", torch.float32).numpy()
+    tokens = np.full((N, K, T), -1, dtype=np.int32)
+    lengths = np.full((N, K), -1, dtype=np.int32)
+    out = np.full((N, K), _NEG, dtype=np.float64)
+    for n in range(N):
+        for k, (p, s) in enumerate(decode_sample(lp[:, n, :], int(K), int(blank))):
+            tokens[n, k, :len(p)] = p
+            lengths[n, k] = len(p)
+            out[n, k] = s
+    return torch.from_numpy(tokens), torch.from_numpy(lengths), torch.from_numpy(out)

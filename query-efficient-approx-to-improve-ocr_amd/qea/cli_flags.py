@@ -114,6 +114,9 @@ FLAGS += [
     ("--show_orig", dict(action="store_true", help="Show original flow evaluation"), "ev"),
     # ---- new (additive) ----
     ("--synthetic_size", dict(type=int, help="[new] use N synthetic samples (datasets/synthetic.py) instead of reading --data_base_path"), "cev"),
+    ("--beam", dict(type=int, default=0, help="[new] decode with a CTC prefix beam search of K entries (1..32) instead of the greedy best path: the most "
+                                              "probable labelling, its log-probability, and how many strips it reads differently from greedy; "
+                                              "0 = greedy"), "e"),
     ("--graph", dict(action="store_true", help="[new] replay the warm-up step (CRNN -> CTC -> backward -> Adam) as ONE hipGraph per (batch size, "
                                                "width, target-length cap, lr); the first two steps of a shape run eagerly, single-process runs only"),
      "c"),

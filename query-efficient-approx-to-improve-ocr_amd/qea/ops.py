@@ -869,6 +869,28 @@ def greedy_decode(scores, ld_t, ld_n, T, N, C_, blank, tokens, lengths):
                "qea_greedy_decode")
 
 
+def ctc_beam_decode(scores, K, blank=0):
+    """CTC prefix beam search (include/qea_hip.h: qea_ctc_beam_decode) of scores [T,N,C] (CUDA, float32, any T / N strides, unit class
+    stride) -> (tokens int32 [N,K,T] with -1 behind every prefix, lengths int32 [N,K], scores float64 [N,K]), best first, on the
+    device and without a synchronisation.  Raises QeaError for K outside 1..32, C outside 2..256, T outside 1..512, blank outside
+    0..C-1."""
+    if scores.dim() != 3 or not scores.is_cuda or scores.dtype != torch.float32:
+        raise _lib.QeaError("ctc_beam_decode needs a CUDA float32 tensor [T,N,C] (there is no CPU path here: qea.beam has one)")
+    if scores.stride(2) != 1:
+        raise _lib.QeaError("ctc_beam_decode needs a unit class stride: make the last dimension contiguous")
+    if not (0 <= scores.stride(0) < 2 ** 31 and 0 <= scores.stride(1) < 2 ** 31):
+        raise _lib.QeaError("ctc_beam_decode: the T and N strides must fit 32 bits")
+    T, N, C_ = scores.shape
+    K = int(K)
+    rows = max(K, 1)
+    tokens = torch.empty(N, rows, T, dtype=torch.int32, device=scores.device)
+    lengths = torch.empty(N, rows, dtype=torch.int32, device=scores.device)
+    out = torch.empty(N, rows, dtype=torch.float64, device=scores.device)
+    _lib.check(_lib.lib().qea_ctc_beam_decode(_ptr(scores), scores.stride(0), scores.stride(1), T, N, C_, int(blank), K, _ptr(tokens),
+                                              _ptr(lengths), _ptr(out), _stream()), "qea_ctc_beam_decode")
+    return tokens, lengths, out
+
+
 def prof_read_launches(klass, capacity=4096):
     import numpy as np
     ms = np.zeros(capacity)

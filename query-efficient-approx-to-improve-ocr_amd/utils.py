@@ -4,7 +4,9 @@ padder / get_text_stack :118-141, get_ocr_helper :180-188, create_dirs :191-206,
 save_all_jsons :209-231, handle_optuna_trial :233-237, set_random_seeds :240-243).
 
 GPU-side work goes through the HIP library: greedy CTC decode (one wave per sample instead of a
-Python loop with an .item() per (b,t)), crop + pad gather with a scatter-add backward.  The optional
+Python loop with an .item() per (b,t)), crop + pad gather with a scatter-add backward.  [new] beam_decode and the
+beam= / nbest= / return_scores= arguments of pred_to_string and batch_cers add a CTC prefix beam search (csrc/ctc_beam.hip for CUDA
+scores, qea/beam.py on the host); the reference has no beam and the defaults are its greedy decode.  The optional
 third-party pieces of the reference file (wandb, optuna, unidecode, Levenshtein, torchvision) are
 imported lazily and only where the corresponding feature is used."""
 import json
@@ -27,8 +29,52 @@ def get_char_maps(vocabulary=None):
 
 
 # ----------------------------------------------------------------------------- decode / CER
-def pred_to_string(scores, labels, index_to_char, show_text=False):
-    """Greedy CTC decode of scores [T,B,C]: per-step argmax, collapse repeats, drop index 0."""
+def beam_decode(scores, beam, blank=0):
+    """[new] CTC prefix beam search of scores [T,B,C] with `beam` entries per sample -> (tokens int32 [B,K,T], lengths int32 [B,K],
+    log-probabilities float64 [B,K]), best first.  CUDA tensors: one launch (qea.ops.ctc_beam_decode), results stay on the device;
+    CPU tensors, or QEA_BEAM=host: the same specification as a host loop (qea/beam.py)."""
+    from qea import beam as host_beam
+    s = scores.detach()
+    if s.is_cuda and not host_beam.use_host():
+        from qea import ops
+        if s.dtype != torch.float32:
+            s = s.float()
+        if s.stride(2) != 1:
+            s = s.contiguous()
+        return ops.ctc_beam_decode(s, beam, blank)
+    tokens, lengths, logp = host_beam.ctc_beam_decode(s, beam, blank)
+    return tokens.to(s.device), lengths.to(s.device), logp.to(s.device)
+
+
+def _beam_to_string(scores, labels, index_to_char, show_text, beam, nbest, return_scores):
+    from qea._lib import QeaError
+    if not 1 <= nbest <= beam:
+        raise QeaError(f"pred_to_string: nbest={nbest} outside 1..beam={beam}")
+    tokens, lengths, logp = beam_decode(scores, beam, 0)
+    tk, ln, lp = tokens.cpu().tolist(), lengths.cpu().tolist(), logp.cpu().tolist()
+    B = len(tk)
+    # a rank beyond the live count (length -1, score -inf: fewer than `beam` labellings have a non-zero probability) reads ""
+    lists = [["".join(index_to_char[i] for i in tk[b][k][:max(ln[b][k], 0)]) for k in range(nbest)] for b in range(B)]
+    preds = [l[0] for l in lists]
+    if show_text:
+        for l, p in zip(labels, preds):
+            print(l, " -> ", p)
+    out = preds if nbest == 1 else lists
+    if return_scores:
+        return out, ([lp[b][0] for b in range(B)] if nbest == 1 else [lp[b][:nbest] for b in range(B)])
+    return out
+
+
+def pred_to_string(scores, labels, index_to_char, show_text=False, beam=0, nbest=1, return_scores=False):
+    """Greedy CTC decode of scores [T,B,C]: per-step argmax, collapse repeats, drop index 0.
+    [new] beam=K > 0: CTC prefix beam search with K entries instead (beam_decode) -> the most probable labelling per sample;
+    nbest=n <= K: a list of the n best strings per sample instead of one string; return_scores=True: (strings, log-probabilities
+    as Python floats of the same nesting).  beam=0 is the greedy path; it has no scores and no second-best reading."""
+    if beam:
+        return _beam_to_string(scores, labels, index_to_char, show_text, int(beam), int(nbest), return_scores)
+    if nbest != 1 or return_scores:
+        from qea._lib import QeaError
+        raise QeaError("pred_to_string: nbest and return_scores need beam=K > 0 (the greedy decode has neither)")
     T, B, C = scores.shape
     if scores.is_cuda:
         from qea import ops
@@ -79,19 +125,26 @@ def compare_labels(preds, labels):
     return correct, total_cer
 
 
-def batch_cers(scores, labels, char_to_index, blank=0):
+def batch_cers(scores, labels, char_to_index, blank=0, beam=0):
     """Per-sample CER of the greedy decode of `scores` [T,B,C] against `labels`, entirely on the GPU up to
     the final division: decode kernel -> edit-distance kernel -> one [B] int32 copy to the host.  Equals
-    [compare_labels([pred_i], [label_i])[1] for i] of the reference loop (train_nn_patch.py:336-342)."""
+    [compare_labels([pred_i], [label_i])[1] for i] of the reference loop (train_nn_patch.py:336-342).
+    [new] beam=K > 0: the CER of the best entry of the prefix beam search instead (rank 0 of beam_decode)."""
     from qea import ops
     T, B, C = scores.shape
     s = scores.detach()
     if s.stride(2) != 1:
         s = s.contiguous()
     dev = s.device
-    tokens = torch.empty(B, T, dtype=torch.int32, device=dev)
-    plen = torch.empty(B, dtype=torch.int32, device=dev)
-    ops.greedy_decode(s, s.stride(0), s.stride(1), T, B, C, blank, tokens, plen)
+    if beam:
+        btok, blen, _ = beam_decode(s, int(beam), blank)
+        # the edit-distance kernel takes rows of at most 128 tokens: rank 0 as a [B][T] slice of its own, not a K * T stride
+        # (length -1 = no labelling with a non-zero probability at all: scored as the empty string)
+        tokens, plen = btok[:, 0, :].contiguous(), blen[:, 0].clamp(min=0).contiguous()
+    else:
+        tokens = torch.empty(B, T, dtype=torch.int32, device=dev)
+        plen = torch.empty(B, dtype=torch.int32, device=dev)
+        ops.greedy_decode(s, s.stride(0), s.stride(1), T, B, C, blank, tokens, plen)
     glen = torch.tensor([len(l) for l in labels], dtype=torch.int32)
     goff = torch.zeros(B, dtype=torch.int64)
     if B > 1:
