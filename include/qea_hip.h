@@ -508,6 +508,23 @@ int qea_greedy_decode(const float* scores, int32_t ld_t, int32_t ld_n, int32_t T
 int qea_ctc_beam_decode(const float* scores, int32_t ld_t, int32_t ld_n, int32_t T, int32_t N, int32_t C, int32_t blank, int32_t K,
                         int32_t* tokens, int32_t* lengths, double* beam_scores, void* stream);
 
+/* The same search with a character n-gram prior fused in (DESIGN.md "Character n-gram fusion"); everything above stands, plus:
+ *   lm_context m = 0, 1, 2 (unigram, bigram, trigram).  The context of a prefix is its last m tokens, padded on the left with BOS, which
+ *   is represented by the blank index; ctx(p) = sum_q tok_q * C^(m-1-q), ctx(p + c) = (ctx(p) * C + c) mod C^m, ctx = 0 for m = 0.
+ *   lm_table [C^m][C] fp64, already alpha * log P(c | ctx) + beta; a NaN entry counts as -inf; column `blank` is never read.  The device
+ *   only ever ADDS table entries.  A beam entry also carries lm (0 at the start) and ctx.  Slot 0 of entry i keeps lm_i and ctx_i and
+ *   ranks by lse(pb', pnb') + lm_i; slot c has lm' = lm_i + lm_table[ctx_i][c] and ranks by pnb' + lm' (first lm', then the sum), pnb'
+ *   the plain search's term.  A ranking score that is not greater than -inf is dropped; the next beam is the K best by RANKING score,
+ *   equal scores in candidate order.  pb / pnb stay pure CTC quantities; folding is unchanged (the same prefix has the same lm, ctx).
+ *   ctc_scores [N][K]: lse(pb, pnb) of rank k;  total_scores [N][K]: ctc + lm, what the order was decided by;  both -inf (and length
+ *   -1) beyond the live count.  With an all-zero table tokens, lengths and ctc_scores are qea_ctc_beam_decode's, and total == ctc.
+ * Refused before any launch: what qea_ctc_beam_decode refuses, lm_context outside 0..2, C^(lm_context + 1) > 2^21 table entries
+ * (16 MB: a trigram up to C = 128, a bigram up to C = 256), NULL lm_table / total_scores.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects it by symbol.) */
+int qea_ctc_beam_decode_lm(const float* scores, int32_t ld_t, int32_t ld_n, int32_t T, int32_t N, int32_t C, int32_t blank, int32_t K,
+                           const double* lm_table, int32_t lm_context, int32_t* tokens, int32_t* lengths, double* ctc_scores,
+                           double* total_scores, void* stream);
+
 /* Unit-cost edit distance between the greedy decode of each sample (pred_tokens [N][ldp], pred_len)
  * and its ground-truth token string (concatenated gt_tokens, gt_offsets, gt_len): the numerator of
  * utils.compare_labels' CER (utils.py:95-110, python-Levenshtein `distance`); the host divides by

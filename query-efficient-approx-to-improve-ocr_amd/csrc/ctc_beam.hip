@@ -1,4 +1,5 @@
-// CTC prefix beam search (include/qea_hip.h: qea_ctc_beam_decode; the specification is DESIGN.md "CTC prefix beam search").
+// CTC prefix beam search (include/qea_hip.h: qea_ctc_beam_decode, qea_ctc_beam_decode_lm; the specification is DESIGN.md "CTC prefix
+// beam search" and "Character n-gram fusion").
 // The reference decodes greedily only (utils.py:74-92); this is the decoder that adds up the alignments of a labelling.
 //
 // ONE 256-thread workgroup per sample, no communication between workgroups, no atomics, no workspace; every output element is
@@ -10,6 +11,11 @@
 // extension slots that were folded into another entry's stay slot (8 KB).
 // Candidate (owner rank i, slot s) has index i * C + s, thread (index & 255) keeps it in register (index >> 8): ascending index is
 // the specification's candidate order, so "largest score, lowest index" K times is the stable descending sort.
+//
+// LM = true (qea_ctc_beam_decode_lm) is the same body with a character n-gram prior fused in: an entry also carries lm (the sum of the
+// fused-table entries along its prefix) and ctx (the index of its last m tokens), the candidate registers hold the RANKING score
+// (CTC term + lm, table entries are only ever added), and the next generation's pb / pnb / tot are recomputed from the CTC terms,
+// never derived from the ranking score.  LM = false compiles to the plain search: every fused statement is under if constexpr.
 #include <limits.h>
 #include <math.h>
 
@@ -19,6 +25,8 @@ namespace {
 
 constexpr int BEAM_THREADS = 256;
 constexpr int BEAM_MAX_K = 32, BEAM_MAX_C = 256, BEAM_MAX_T = 512;
+constexpr int BEAM_LM_MAX_CONTEXT = 2;
+constexpr long long BEAM_LM_MAX_ENTRIES = 1ll << 21;                    // C^(m+1) fp64 entries: 16 MB
 constexpr unsigned long long BEAM_HASH_SEED = 0x9E3779B97F4A7C15ull, BEAM_HASH_MUL = 0x100000001B3ull;
 
 __device__ __forceinline__ double beam_lse(double a, double b) {
@@ -33,16 +41,30 @@ __device__ __forceinline__ bool beam_before(double s, int i, double s2, int i2) 
 // slot s >= 1 of a beam entry is the s-th class that is not the blank, ascending
 __device__ __forceinline__ int beam_slot_class(int s, int blank) { return s <= blank ? s - 1 : s; }
 
-// R: candidate registers per thread, K * C <= R * 256
-template <int R>
-__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __restrict__ scores, int ld_t, int ld_n, int T, int C, int blank,
-                                                                 int K, int* __restrict__ tokens, int* __restrict__ lengths,
-                                                                 double* __restrict__ beam_scores) {
+// a fused-table entry: NaN counts as -inf
+__device__ __forceinline__ double beam_lm_entry(const double* __restrict__ lm_table, int ctx, int C, int c) {
+  const double w = lm_table[(long long)ctx * C + c];
+  return w != w ? -INFINITY : w;
+}
+
+// R: candidate registers per thread, K * C <= R * 256.  LM: lm_table [ctx_mod][C] fp64 with ctx_mod = C^m, total_scores [N][K];
+// without LM the three are unused (NULL, 1, NULL).
+// A workgroup is one wave per SIMD, so waves per SIMD = workgroups per CU, and with 8 strips per CU (N = 2048) a variant that loses
+// one takes another round.  The plain variants fit 5, 4, 2, 1 (94, 124, 205, 256 + AGPRs); left alone the fused ones take 104, 141,
+// 245 + 32 AGPRs (the table entries' addresses) and fit 4, 3, 1, 1: they are asked to keep the plain variants' occupancy.
+constexpr int beam_min_waves(int R, bool LM) { return !LM ? 1 : R == 1 ? 5 : R == 4 ? 4 : R == 12 ? 2 : 1; }
+
+template <int R, bool LM>
+__global__ __launch_bounds__(BEAM_THREADS, beam_min_waves(R, LM)) void ctc_beam_kernel(
+    const float* __restrict__ scores, int ld_t, int ld_n, int T, int C, int blank, int K, const double* __restrict__ lm_table, int ctx_mod,
+    int* __restrict__ tokens, int* __restrict__ lengths, double* __restrict__ beam_scores, double* __restrict__ total_scores) {
   extern __shared__ __align__(16) unsigned char pre[];                 // [2][K][T] prefixes, one byte per token
   __shared__ double row[BEAM_MAX_C];                                    // lp[t][:] as fp64, NaN -> -inf
   __shared__ double s_pb[2][BEAM_MAX_K], s_pnb[2][BEAM_MAX_K], s_tot[2][BEAM_MAX_K];
   __shared__ unsigned long long s_hash[2][BEAM_MAX_K], s_phash[2][BEAM_MAX_K];
   __shared__ int s_len[2][BEAM_MAX_K], s_last[2][BEAM_MAX_K];
+  __shared__ double s_lm[2][BEAM_MAX_K];                                // LM: the table entries along the prefix, added up
+  __shared__ int s_ctx[2][BEAM_MAX_K];                                  // LM: index of the last m tokens, BOS (= blank) padded
   __shared__ double stay_pb[BEAM_MAX_K], stay_pnb[BEAM_MAX_K];        // slot 0 of every entry, merges folded in
   __shared__ int parent[BEAM_MAX_K];                                    // rank of the entry whose prefix + last token is entry j, or -1
   __shared__ unsigned char folded[BEAM_MAX_K * BEAM_MAX_C];             // [i][c] != 0: slot of class c of entry i does not exist
@@ -61,6 +83,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     s_phash[0][0] = 0;
     s_len[0][0] = 0;
     s_last[0][0] = -1;
+    if constexpr (LM) {
+      int ctx = 0;
+      for (int q = 1; q < ctx_mod; q *= C) ctx = ctx * C + blank;       // the blank, m times
+      s_lm[0][0] = 0.0;
+      s_ctx[0][0] = ctx;
+    }
   }
   int g = 0, nlive = 1;
   float nxt = tid < C ? base[tid] : 0.f;
@@ -69,6 +97,21 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     if (tid < C) row[tid] = nxt != nxt ? -INFINITY : (double)nxt;
     if (tid < K) parent[tid] = -1;
     __syncthreads();
+
+    // LM: the table entry of every extension slot this thread owns; in flight during the stay slots and the folding
+    // (they wait in the candidate registers: consecutive threads read consecutive classes of one table row)
+    double sc[R];
+    if constexpr (LM) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int idx = r * BEAM_THREADS + tid;
+        sc[r] = 0.0;
+        if (idx < nlive * C) {
+          const int i = idx / C, s = idx - i * C;
+          if (s != 0) sc[r] = beam_lm_entry(lm_table, s_ctx[g][i], C, beam_slot_class(s, blank));
+        }
+      }
+    }
 
     // slot 0 of every entry; which entries are another entry's prefix plus one token (hash first, the bytes decide)
     if (tid < nlive) {
@@ -99,7 +142,6 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     __syncthreads();
 
     // candidate scores, in registers
-    double sc[R];
     const int ncand = nlive * C;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -109,9 +151,16 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         const int i = idx / C, s = idx - i * C;
         if (s == 0) {
           v = beam_lse(stay_pb[i], stay_pnb[i]);
+          if constexpr (LM) v = v + s_lm[g][i];
         } else {
           const int c = beam_slot_class(s, blank);
-          if (!folded[i * C + c]) v = (c == s_last[g][i] ? s_pb[g][i] : s_tot[g][i]) + row[c];
+          if (!folded[i * C + c]) {
+            v = (c == s_last[g][i] ? s_pb[g][i] : s_tot[g][i]) + row[c];
+            if constexpr (LM) {
+              const double lm2 = s_lm[g][i] + sc[r];                    // first lm', then the sum: the specification's association
+              v = v + lm2;
+            }
+          }
         }
         if (!(v > -INFINITY)) v = -INFINITY;                            // a NaN (from +inf inputs) is dropped like -inf
       }
@@ -193,16 +242,29 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         s_phash[g2][tid] = s_phash[g][i];
         s_len[g2][tid] = s_len[g][i];
         s_last[g2][tid] = s_last[g][i];
+        if constexpr (LM) {
+          s_tot[g2][tid] = beam_lse(stay_pb[i], stay_pnb[i]);
+          s_lm[g2][tid] = s_lm[g][i];
+          s_ctx[g2][tid] = s_ctx[g][i];
+        }
       } else {
         const int c = beam_slot_class(s, blank);
         s_pb[g2][tid] = -INFINITY;
-        s_pnb[g2][tid] = sel_s[tid];
+        if constexpr (LM) {                                             // sel_s is the ranking score: the CTC term is formed again
+          const double pnb = (c == s_last[g][i] ? s_pb[g][i] : s_tot[g][i]) + row[c];
+          s_pnb[g2][tid] = pnb;
+          s_tot[g2][tid] = pnb;
+          s_lm[g2][tid] = s_lm[g][i] + beam_lm_entry(lm_table, s_ctx[g][i], C, c);
+          s_ctx[g2][tid] = (s_ctx[g][i] * C + c) % ctx_mod;
+        } else {
+          s_pnb[g2][tid] = sel_s[tid];
+        }
         s_hash[g2][tid] = (s_hash[g][i] ^ (unsigned long long)(c + 1)) * BEAM_HASH_MUL;
         s_phash[g2][tid] = s_hash[g][i];
         s_len[g2][tid] = s_len[g][i] + 1;
         s_last[g2][tid] = c;
       }
-      s_tot[g2][tid] = sel_s[tid];                                      // lse(pb', pnb'): the candidate's score
+      if constexpr (!LM) s_tot[g2][tid] = sel_s[tid];                   // lse(pb', pnb'): the candidate's score
     }
     const int L = t + 1;                                                // no prefix is longer than t + 1 after step t
     for (int e = tid; e < nnew * L; e += BEAM_THREADS) {
@@ -228,35 +290,58 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   if (tid < K) {
     lengths[(long long)n * K + tid] = tid < nlive ? s_len[g][tid] : -1;
     beam_scores[(long long)n * K + tid] = tid < nlive ? s_tot[g][tid] : -INFINITY;
+    if constexpr (LM) total_scores[(long long)n * K + tid] = tid < nlive ? s_tot[g][tid] + s_lm[g][tid] : -INFINITY;
   }
 }
 
-template <int R>
-void beam_launch(const float* scores, int ld_t, int ld_n, int T, int N, int C, int blank, int K, int* tokens, int* lengths, double* beam_scores,
-                 hipStream_t stream) {
-  hipLaunchKernelGGL(ctc_beam_kernel<R>, dim3(N), dim3(BEAM_THREADS), (size_t)2 * K * T, stream, scores, ld_t, ld_n, T, C, blank, K, tokens,
-                     lengths, beam_scores);
+template <int R, bool LM>
+void beam_launch(const float* scores, int ld_t, int ld_n, int T, int N, int C, int blank, int K, const double* lm_table, int ctx_mod,
+                 int* tokens, int* lengths, double* beam_scores, double* total_scores, hipStream_t stream) {
+  hipLaunchKernelGGL((ctc_beam_kernel<R, LM>), dim3(N), dim3(BEAM_THREADS), (size_t)2 * K * T, stream, scores, ld_t, ld_n, T, C, blank, K,
+                     lm_table, ctx_mod, tokens, lengths, beam_scores, total_scores);
+}
+
+// the limits both entry points share, then the register variant that holds K * C candidates
+template <bool LM>
+int beam_decode(const char* who, const float* scores, int ld_t, int ld_n, int T, int N, int C, int blank, int K, const double* lm_table,
+                int ctx_mod, int* tokens, int* lengths, double* beam_scores, double* total_scores, hipStream_t st) {
+  QEA_REQUIRE(scores && tokens && lengths && beam_scores && N > 0 && ld_t >= 0 && ld_n >= 0, "%s: bad arguments", who);
+  QEA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, "%s: K=%d outside 1..%d", who, K, BEAM_MAX_K);
+  QEA_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "%s: C=%d outside 2..%d", who, C, BEAM_MAX_C);
+  QEA_REQUIRE(T >= 1 && T <= BEAM_MAX_T, "%s: T=%d outside 1..%d", who, T, BEAM_MAX_T);
+  QEA_REQUIRE(blank >= 0 && blank < C, "%s: blank=%d outside 0..%d", who, blank, C - 1);
+  const int per_thread = qea_cdiv((long long)K * C, BEAM_THREADS);
+  if (per_thread <= 1)
+    beam_launch<1, LM>(scores, ld_t, ld_n, T, N, C, blank, K, lm_table, ctx_mod, tokens, lengths, beam_scores, total_scores, st);
+  else if (per_thread <= 4)
+    beam_launch<4, LM>(scores, ld_t, ld_n, T, N, C, blank, K, lm_table, ctx_mod, tokens, lengths, beam_scores, total_scores, st);
+  else if (per_thread <= 12)
+    beam_launch<12, LM>(scores, ld_t, ld_n, T, N, C, blank, K, lm_table, ctx_mod, tokens, lengths, beam_scores, total_scores, st);
+  else
+    beam_launch<32, LM>(scores, ld_t, ld_n, T, N, C, blank, K, lm_table, ctx_mod, tokens, lengths, beam_scores, total_scores, st);
+  QEA_CHECK_LAUNCH();
+  return QEA_OK;
 }
 
 }  // namespace
 
 extern "C" int qea_ctc_beam_decode(const float* scores, int32_t ld_t, int32_t ld_n, int32_t T, int32_t N, int32_t C, int32_t blank, int32_t K,
                                    int32_t* tokens, int32_t* lengths, double* beam_scores, void* stream) {
-  QEA_REQUIRE(scores && tokens && lengths && beam_scores && N > 0 && ld_t >= 0 && ld_n >= 0, "qea_ctc_beam_decode: bad arguments");
-  QEA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, "qea_ctc_beam_decode: K=%d outside 1..%d", K, BEAM_MAX_K);
-  QEA_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "qea_ctc_beam_decode: C=%d outside 2..%d", C, BEAM_MAX_C);
-  QEA_REQUIRE(T >= 1 && T <= BEAM_MAX_T, "qea_ctc_beam_decode: T=%d outside 1..%d", T, BEAM_MAX_T);
-  QEA_REQUIRE(blank >= 0 && blank < C, "qea_ctc_beam_decode: blank=%d outside 0..%d", blank, C - 1);
-  const int per_thread = qea_cdiv((long long)K * C, BEAM_THREADS);
-  hipStream_t st = (hipStream_t)stream;
-  if (per_thread <= 1)
-    beam_launch<1>(scores, ld_t, ld_n, T, N, C, blank, K, tokens, lengths, beam_scores, st);
-  else if (per_thread <= 4)
-    beam_launch<4>(scores, ld_t, ld_n, T, N, C, blank, K, tokens, lengths, beam_scores, st);
-  else if (per_thread <= 12)
-    beam_launch<12>(scores, ld_t, ld_n, T, N, C, blank, K, tokens, lengths, beam_scores, st);
-  else
-    beam_launch<32>(scores, ld_t, ld_n, T, N, C, blank, K, tokens, lengths, beam_scores, st);
-  QEA_CHECK_LAUNCH();
-  return QEA_OK;
+  return beam_decode<false>("qea_ctc_beam_decode", scores, ld_t, ld_n, T, N, C, blank, K, nullptr, 1, tokens, lengths, beam_scores, nullptr,
+                            (hipStream_t)stream);
+}
+
+extern "C" int qea_ctc_beam_decode_lm(const float* scores, int32_t ld_t, int32_t ld_n, int32_t T, int32_t N, int32_t C, int32_t blank, int32_t K,
+                                      const double* lm_table, int32_t lm_context, int32_t* tokens, int32_t* lengths, double* ctc_scores,
+                                      double* total_scores, void* stream) {
+  QEA_REQUIRE(lm_table && total_scores, "qea_ctc_beam_decode_lm: bad arguments");
+  QEA_REQUIRE(lm_context >= 0 && lm_context <= BEAM_LM_MAX_CONTEXT, "qea_ctc_beam_decode_lm: lm_context=%d outside 0..%d", lm_context,
+              BEAM_LM_MAX_CONTEXT);
+  QEA_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "qea_ctc_beam_decode_lm: C=%d outside 2..%d", C, BEAM_MAX_C);
+  long long ctx_mod = 1;
+  for (int q = 0; q < lm_context; ++q) ctx_mod *= C;
+  QEA_REQUIRE(ctx_mod * C <= BEAM_LM_MAX_ENTRIES, "qea_ctc_beam_decode_lm: a table of C^(m+1) = %lld entries, more than %lld", ctx_mod * C,
+              BEAM_LM_MAX_ENTRIES);
+  return beam_decode<true>("qea_ctc_beam_decode_lm", scores, ld_t, ld_n, T, N, C, blank, K, lm_table, (int)ctx_mod, tokens, lengths, ctc_scores,
+                           total_scores, (hipStream_t)stream);
 }

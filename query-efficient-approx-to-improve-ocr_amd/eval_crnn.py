@@ -17,6 +17,10 @@ The printed lines are the reference's.  Differences, all deliberate:
     of csrc/ctc_beam.hip for CUDA scores) instead of the greedy best path: the strings are the most probable LABELLINGS.  The dict then
     also has beam, crnn_mean_log_score (the mean log-probability of those labellings) and greedy_disagreements (the strips whose
     greedy string differs), and one more line is printed.  Without the flag nothing changes.
+  * [new] --lm PATH (with --beam K) fuses the character n-gram model of that file (qea/lm.py, written by lm_cli.py) into the search,
+    weight --lm_weight, per-character bonus --lm_bonus: the strings are the fused search's.  The dict then also has lm_order,
+    lm_weight, lm_bonus, crnn_mean_total_score (the mean of the scores the search ranked by) and lm_disagreements (the strips the plain
+    beam of the same K reads differently); crnn_mean_log_score stays the mean CTC log-probability of the chosen readings.
   * The loaders run in the main process (the reference asks for properties.num_workers workers).
 `backend` / `dataset` / `ocr` are injection seams for tests, as in the trainers; the default backend is the HIP path.
 """
@@ -26,7 +30,7 @@ import torch
 
 import properties
 from qea.trainer_core import hip_backend
-from utils import compare_labels, get_char_maps, get_ocr_helper, get_text_stack, pred_to_string, show_img
+from utils import beam_decode_lm, compare_labels, get_char_maps, get_ocr_helper, get_text_stack, pred_to_string, show_img
 
 
 class EvalCRNN:
@@ -41,6 +45,11 @@ class EvalCRNN:
         self.show_orig = args.show_orig
         self.beam = int(getattr(args, "beam", 0) or 0)               # [new] --beam K: prefix beam search instead of greedy
         self.beam_log_score, self.greedy_disagreements = 0.0, 0
+        self.lm_path = getattr(args, "lm", None)                     # [new] --lm PATH: a character n-gram model fused into the search
+        self.lm_weight, self.lm_bonus = float(getattr(args, "lm_weight", 1.0)), float(getattr(args, "lm_bonus", 0.0))
+        self.lm, self.beam_total_score, self.lm_disagreements = None, 0.0, 0
+        if self.lm_path and not self.beam:
+            raise ValueError("--lm needs --beam K: the model is fused into the prefix beam search")
         self.input_size = properties.input_size
         if self.dataset_name == "vgg":
             self.test_set = os.path.join(args.data_base_path, properties.vgg_text_dataset_test)
@@ -57,6 +66,9 @@ class EvalCRNN:
         self.ocr = ocr if ocr is not None else get_ocr_helper(self.ocr_name, is_eval=True)
         print(self.ocr)
         self.char_to_index, self.index_to_char, self.vocab_size = get_char_maps(properties.char_set)
+        if self.lm_path:
+            from qea.lm import CharLM
+            self.lm = CharLM.load(self.lm_path, self.char_to_index)
 
         n = getattr(args, "synthetic_size", None)
         if self.dataset_name == "pos":
@@ -87,8 +99,17 @@ class EvalCRNN:
         entries' log-probabilities and counts the strips that greedy reads differently."""
         if not self.beam:
             return pred_to_string(scores, labels, self.index_to_char)
-        preds, logp = pred_to_string(scores, labels, self.index_to_char, beam=self.beam, return_scores=True)
         greedy = pred_to_string(scores, labels, self.index_to_char)
+        if self.lm is not None:                                       # rank 0 of the fused search, its CTC score and its total
+            tokens, lengths, ctc, total = (v[:, 0].cpu().tolist() for v in beam_decode_lm(scores, self.beam, self.lm, self.lm_weight, self.lm_bonus))
+            preds = ["".join(self.index_to_char[i] for i in tk[:max(n, 0)]) for tk, n in zip(tokens, lengths)]
+            plain = pred_to_string(scores, labels, self.index_to_char, beam=self.beam)
+            self.beam_log_score += sum(ctc)
+            self.beam_total_score += sum(total)
+            self.lm_disagreements += sum(int(p != q) for p, q in zip(preds, plain))
+            self.greedy_disagreements += sum(int(p != q) for p, q in zip(preds, greedy))
+            return preds
+        preds, logp = pred_to_string(scores, labels, self.index_to_char, beam=self.beam, return_scores=True)
         self.beam_log_score += sum(logp)
         self.greedy_disagreements += sum(int(p != q) for p, q in zip(preds, greedy))
         return preds
@@ -108,12 +129,17 @@ class EvalCRNN:
             res.update(beam=self.beam, crnn_mean_log_score=self.beam_log_score / max(1, count), greedy_disagreements=self.greedy_disagreements)
             print("Beam {:d}: mean log-probability of the best labelling {:.5f}, differs from greedy on {:d}/{:d} strips".format(
                 self.beam, res["crnn_mean_log_score"], self.greedy_disagreements, count))
+        if self.lm is not None:
+            res.update(lm_order=self.lm.order, lm_weight=self.lm_weight, lm_bonus=self.lm_bonus,
+                       crnn_mean_total_score=self.beam_total_score / max(1, count), lm_disagreements=self.lm_disagreements)
+            print("Character {:d}-gram fused (weight {:g}, bonus {:g}): mean total score {:.5f}, differs from the plain beam on {:d}/{:d} strips".format(
+                self.lm.order, self.lm_weight, self.lm_bonus, res["crnn_mean_total_score"], self.lm_disagreements, count))
         return res
 
     def eval_area(self):
         print("Eval with ", self.ocr_name)
         self.crnn_model.eval()
-        self.beam_log_score, self.greedy_disagreements = 0.0, 0
+        self.beam_log_score, self.greedy_disagreements, self.beam_total_score, self.lm_disagreements = 0.0, 0, 0.0, 0
         crnn_correct_count, ori_correct_count, ori_cer, crnn_cer = 0, 0, 0.0, 0.0
         with torch.no_grad():
             for batch in self.loader_eval:
@@ -143,7 +169,7 @@ class EvalCRNN:
     def eval_patch(self):
         print("Eval with ", self.ocr_name)
         self.crnn_model.eval()
-        self.beam_log_score, self.greedy_disagreements = 0.0, 0
+        self.beam_log_score, self.greedy_disagreements, self.beam_total_score, self.lm_disagreements = 0.0, 0, 0.0, 0
         ori_lbl_crt_count, ori_lbl_cer, lbl_count, crnn_correct_count, crnn_cer = 0, 0.0, 0, 0, 0.0
         with torch.no_grad():
             for i in range(len(self.dataset)):

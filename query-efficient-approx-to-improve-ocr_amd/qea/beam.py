@@ -6,6 +6,10 @@ A beam entry is (prefix, pb, pnb): the log-probabilities of the prefix over the 
 candidates of a step are laid out as a [live, C] table: row = beam rank, column 0 = the prefix itself, column s >= 1 = the prefix
 plus the s-th non-blank class.  Row-major order of that table is the candidate order, and a stable descending sort picks the next
 beam, so equal scores keep that order.
+
+With lm_table (qea_ctc_beam_decode_lm, DESIGN.md "Character n-gram fusion") an entry also carries lm, the sum of the fused-table
+entries along its prefix, and ctx, the index of its last lm_context tokens (BOS = the blank index on the left).  A second [live, C]
+table then holds the RANKING scores, CTC term + lm, and the sort runs on that one; pb / pnb stay pure CTC quantities.
 """
 import math
 import os
@@ -14,6 +18,7 @@ import numpy as np
 import torch
 
 MAX_K, MAX_C, MAX_T = 32, 256, 512           # the limits of qea_ctc_beam_decode
+MAX_LM_CONTEXT, MAX_LM_ENTRIES = 2, 1 << 21  # and of qea_ctc_beam_decode_lm: C ** (context + 1) fp64 table entries, 16 MB
 _NEG = -math.inf
 
 
@@ -41,13 +46,35 @@ def check_limits(T, C, K, blank):
         raise QeaError(f"ctc_beam_decode: blank={blank} outside 0..{C - 1}")
 
 
-def decode_sample(lp, K, blank=0):
-    """lp [T][C] float32 (numpy) -> [(prefix tuple, score)] of at most K entries, best first."""
+def check_lm_limits(C, context, table_shape=None):
+    """The fused search's own limits; table_shape, where given, must be (C ** context, C)."""
+    from ._lib import QeaError
+    if not 0 <= context <= MAX_LM_CONTEXT:
+        raise QeaError(f"ctc_beam_decode_lm: lm_context={context} outside 0..{MAX_LM_CONTEXT}")
+    if C ** (context + 1) > MAX_LM_ENTRIES:
+        raise QeaError(f"ctc_beam_decode_lm: a table of C^(m+1) = {C ** (context + 1)} entries, more than {MAX_LM_ENTRIES}")
+    if table_shape is not None and tuple(table_shape) != (C ** context, C):
+        raise QeaError(f"ctc_beam_decode_lm: the table is {tuple(table_shape)}, not [C**context, C] = {(C ** context, C)}")
+
+
+def start_context(C, context, blank):
+    """ctx(()): the blank, `context` times."""
+    return sum(blank * C ** q for q in range(context))
+
+
+def decode_sample(lp, K, blank=0, lm_table=None, lm_context=0):
+    """lp [T][C] float32 (numpy) -> [(prefix tuple, score)] of at most K entries, best first.  With lm_table (fp64 numpy
+    [C ** lm_context, C]) the search is the fused one and the entries are (prefix tuple, ctc, total)."""
     T, C = lp.shape
     lp = lp.astype(np.float64)
     lp[np.isnan(lp)] = _NEG
     classes = np.array([c for c in range(C) if c != blank], dtype=np.int64)          # column s of the table holds classes[s - 1]
     column = {int(c): s + 1 for s, c in enumerate(classes)}
+    fused = lm_table is not None
+    if fused:
+        W = np.where(np.isnan(lm_table), _NEG, lm_table)
+        mod = C ** lm_context
+        state = [(0.0, start_context(C, lm_context, blank))]                       # (lm, ctx) per beam entry
     beam = [((), 0.0, _NEG)]
     for t in range(T):
         row = lp[t]
@@ -67,10 +94,18 @@ def decode_sample(lp, K, blank=0):
                 stay_pnb[j] = lse(stay_pnb[j], float(table[i, column[p[-1]]]))
                 table[i, column[p[-1]]] = _NEG
         table[:, 0] = [lse(stay_pb[i], stay_pnb[i]) for i in range(live)]
-        flat = table.ravel()
+        if fused:                                                                   # ranking = CTC term + lm', lm' formed first
+            lm2 = np.empty((live, C))
+            with np.errstate(invalid="ignore"):
+                for i, (lm, ctx) in enumerate(state):
+                    lm2[i, 0] = lm
+                    lm2[i, 1:] = lm + W[ctx, classes]
+                flat = (table + lm2).ravel()
+        else:
+            flat = table.ravel()
         flat[np.isnan(flat)] = _NEG
         order = np.argsort(-flat, kind="stable")[:K]
-        nxt = []
+        nxt, nstate = [], []
         for idx in order.tolist():
             if flat[idx] == _NEG:
                 break
@@ -78,23 +113,47 @@ def decode_sample(lp, K, blank=0):
             if s == 0:
                 nxt.append((beam[i][0], stay_pb[i], stay_pnb[i]))
             else:
-                nxt.append((beam[i][0] + (int(classes[s - 1]),), _NEG, float(flat[idx])))
+                nxt.append((beam[i][0] + (int(classes[s - 1]),), _NEG, float(table[i, s])))
+            if fused:
+                nstate.append((float(lm2[i, s]), state[i][1] if s == 0 else (state[i][1] * C + int(classes[s - 1])) % mod))
         beam = nxt
+        if fused:
+            state = nstate
+    if fused:
+        return [(p, lse(pb, pnb), lse(pb, pnb) + lm) for (p, pb, pnb), (lm, _) in zip(beam, state)]
     return [(p, lse(pb, pnb)) for p, pb, pnb in beam]
 
 
-def ctc_beam_decode(scores, K, blank=0):
+def ctc_beam_decode(scores, K, blank=0, lm_table=None, lm_context=0):
     """scores [T,N,C] float32 (any device) -> (tokens int32 [N,K,T], lengths int32 [N,K], scores float64 [N,K]) on the CPU, in the
-    layout of qea.ops.ctc_beam_decode: -1 behind every prefix, length -1 and score -inf in the rows beyond the live count."""
+    layout of qea.ops.ctc_beam_decode: -1 behind every prefix, length -1 and score -inf in the rows beyond the live count.
+    With lm_table (a float64 tensor or array [C ** lm_context, C]): the fused search, in the layout of qea.ops.ctc_beam_decode_lm,
+    (tokens, lengths, ctc float64 [N,K], total float64 [N,K])."""
     T, N, C = scores.shape
     check_limits(T, C, int(K), int(blank))
+    fused = lm_table is not None
+    if fused:
+        lm_context = int(lm_context)
+        check_lm_limits(C, lm_context, tuple(lm_table.shape))
+        if torch.is_tensor(lm_table):
+            lm_table = lm_table.detach().to("cpu", torch.float64).numpy()
+        lm_table = np.asarray(lm_table, dtype=np.float64)
+    elif lm_context:
+        from ._lib import QeaError
+        raise QeaError("ctc_beam_decode: lm_context without an lm_table")
     lp = scores.detach().to("cpu", torch.float32).numpy()
     tokens = np.full((N, K, T), -1, dtype=np.int32)
     lengths = np.full((N, K), -1, dtype=np.int32)
     out = np.full((N, K), _NEG, dtype=np.float64)
+    total = np.full((N, K), _NEG, dtype=np.float64)
     for n in range(N):
-        for k, (p, s) in enumerate(decode_sample(lp[:, n, :], int(K), int(blank))):
+        for k, entry in enumerate(decode_sample(lp[:, n, :], int(K), int(blank), lm_table, lm_context)):
+            p = entry[0]
             tokens[n, k, :len(p)] = p
             lengths[n, k] = len(p)
-            out[n, k] = s
+            out[n, k] = entry[1]
+            if fused:
+                total[n, k] = entry[2]
+    if fused:
+        return torch.from_numpy(tokens), torch.from_numpy(lengths), torch.from_numpy(out), torch.from_numpy(total)
     return torch.from_numpy(tokens), torch.from_numpy(lengths), torch.from_numpy(out)

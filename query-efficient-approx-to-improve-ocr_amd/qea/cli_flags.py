@@ -117,6 +117,11 @@ FLAGS += [
     ("--beam", dict(type=int, default=0, help="[new] decode with a CTC prefix beam search of K entries (1..32) instead of the greedy best path: the most "
                                               "probable labelling, its log-probability, and how many strips it reads differently from greedy; "
                                               "0 = greedy"), "e"),
+    ("--lm", dict(help="[new] --beam K: fuse the character n-gram model of this file (written by lm_cli.py) into the prefix beam search: a "
+                       "candidate is ranked by its CTC log-probability plus lm_weight * log P(c | context) + lm_bonus per character"), "e"),
+    ("--lm_weight", dict(type=float, default=1.0, help="[new] --lm: weight of the model's log-probabilities"), "e"),
+    ("--lm_bonus", dict(type=float, default=0.0, help="[new] --lm: bonus per character (the model has no end-of-word term: this is the "
+                                                      "length control)"), "e"),
     ("--graph", dict(action="store_true", help="[new] replay the warm-up step (CRNN -> CTC -> backward -> Adam) as ONE hipGraph per (batch size, "
                                                "width, target-length cap, lr); the first two steps of a shape run eagerly, single-process runs only"),
      "c"),

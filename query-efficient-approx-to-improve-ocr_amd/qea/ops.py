@@ -891,6 +891,37 @@ def ctc_beam_decode(scores, K, blank=0):
     return tokens, lengths, out
 
 
+def ctc_beam_decode_lm(scores, K, table, context, blank=0):
+    """The prefix beam search with a character n-gram prior fused in (include/qea_hip.h: qea_ctc_beam_decode_lm): scores as for
+    ctc_beam_decode, table = the fused W [C ** context, C] (CUDA, float64, contiguous; qea.lm.CharLM.fused), context 0..2 ->
+    (tokens int32 [N,K,T], lengths int32 [N,K], ctc float64 [N,K], total float64 [N,K]), best first by total, on the device and
+    without a synchronisation.  Raises QeaError for what ctc_beam_decode refuses, context outside 0..2, C ** (context + 1) > 2 ** 21
+    and a table of another device, dtype, layout or shape."""
+    if scores.dim() != 3 or not scores.is_cuda or scores.dtype != torch.float32:
+        raise _lib.QeaError("ctc_beam_decode_lm needs a CUDA float32 tensor [T,N,C] (there is no CPU path here: qea.beam has one)")
+    if scores.stride(2) != 1:
+        raise _lib.QeaError("ctc_beam_decode_lm needs a unit class stride: make the last dimension contiguous")
+    if not (0 <= scores.stride(0) < 2 ** 31 and 0 <= scores.stride(1) < 2 ** 31):
+        raise _lib.QeaError("ctc_beam_decode_lm: the T and N strides must fit 32 bits")
+    T, N, C_ = scores.shape
+    K, context = int(K), int(context)
+    if not 0 <= context <= 2:
+        raise _lib.QeaError(f"ctc_beam_decode_lm: context={context} outside 0..2")
+    if C_ ** (context + 1) > 2 ** 21:
+        raise _lib.QeaError(f"ctc_beam_decode_lm: a table of C^(m+1) = {C_ ** (context + 1)} entries, more than {2 ** 21}")
+    if not (torch.is_tensor(table) and table.is_cuda and table.device == scores.device and table.dtype == torch.float64
+            and table.is_contiguous() and tuple(table.shape) == (C_ ** context, C_)):
+        raise _lib.QeaError(f"ctc_beam_decode_lm needs a contiguous CUDA float64 table [C**context, C] = {(C_ ** context, C_)} on the scores' device")
+    rows = max(K, 1)
+    tokens = torch.empty(N, rows, T, dtype=torch.int32, device=scores.device)
+    lengths = torch.empty(N, rows, dtype=torch.int32, device=scores.device)
+    ctc = torch.empty(N, rows, dtype=torch.float64, device=scores.device)
+    total = torch.empty(N, rows, dtype=torch.float64, device=scores.device)
+    _lib.check(_lib.lib().qea_ctc_beam_decode_lm(_ptr(scores), scores.stride(0), scores.stride(1), T, N, C_, int(blank), K, _ptr(table), context,
+                                                 _ptr(tokens), _ptr(lengths), _ptr(ctc), _ptr(total), _stream()), "qea_ctc_beam_decode_lm")
+    return tokens, lengths, ctc, total
+
+
 def prof_read_launches(klass, capacity=4096):
     import numpy as np
     ms = np.zeros(capacity)

@@ -6,7 +6,8 @@ save_all_jsons :209-231, handle_optuna_trial :233-237, set_random_seeds :240-243
 GPU-side work goes through the HIP library: greedy CTC decode (one wave per sample instead of a
 Python loop with an .item() per (b,t)), crop + pad gather with a scatter-add backward.  [new] beam_decode and the
 beam= / nbest= / return_scores= arguments of pred_to_string and batch_cers add a CTC prefix beam search (csrc/ctc_beam.hip for CUDA
-scores, qea/beam.py on the host); the reference has no beam and the defaults are its greedy decode.  The optional
+scores, qea/beam.py on the host), and beam_decode_lm / lm= / lm_weight= / lm_bonus= fuse a character n-gram prior (qea/lm.py) into
+that search; the reference has no beam and the defaults are its greedy decode.  The optional
 third-party pieces of the reference file (wandb, optuna, unidecode, Levenshtein, torchvision) are
 imported lazily and only where the corresponding feature is used."""
 import json
@@ -46,11 +47,34 @@ def beam_decode(scores, beam, blank=0):
     return tokens.to(s.device), lengths.to(s.device), logp.to(s.device)
 
 
-def _beam_to_string(scores, labels, index_to_char, show_text, beam, nbest, return_scores):
+def beam_decode_lm(scores, beam, lm, alpha=1.0, beta=0.0, blank=0):
+    """[new] beam_decode with the character n-gram model `lm` (qea.lm.CharLM) fused into the search: a candidate is ranked by its CTC
+    log-probability plus alpha * log P(c | context) + beta per character -> (tokens int32 [B,K,T], lengths int32 [B,K],
+    ctc float64 [B,K], total float64 [B,K]), best first by total.  CUDA tensors: one launch (qea.ops.ctc_beam_decode_lm); CPU
+    tensors, or QEA_BEAM=host: the same specification as a host loop (qea/beam.py)."""
+    from qea import beam as host_beam
+    from qea._lib import QeaError
+    s = scores.detach()
+    if lm.num_classes != s.shape[2] or lm.blank != blank:
+        raise QeaError(f"beam_decode_lm: the model has {lm.num_classes} classes and blank {lm.blank}, the scores {s.shape[2]} and {blank}")
+    if s.is_cuda and not host_beam.use_host():
+        from qea import ops
+        if s.dtype != torch.float32:
+            s = s.float()
+        if s.stride(2) != 1:
+            s = s.contiguous()
+        return ops.ctc_beam_decode_lm(s, beam, lm.fused(alpha, beta, s.device), lm.context, blank)
+    return tuple(v.to(s.device) for v in host_beam.ctc_beam_decode(s, beam, blank, lm.fused(alpha, beta, "cpu"), lm.context))
+
+
+def _beam_to_string(scores, labels, index_to_char, show_text, beam, nbest, return_scores, lm=None, lm_weight=1.0, lm_bonus=0.0):
     from qea._lib import QeaError
     if not 1 <= nbest <= beam:
         raise QeaError(f"pred_to_string: nbest={nbest} outside 1..beam={beam}")
-    tokens, lengths, logp = beam_decode(scores, beam, 0)
+    if lm is None:
+        tokens, lengths, logp = beam_decode(scores, beam, 0)
+    else:                                                              # the scores returned are the totals: what decided the order
+        tokens, lengths, _, logp = beam_decode_lm(scores, beam, lm, lm_weight, lm_bonus, 0)
     tk, ln, lp = tokens.cpu().tolist(), lengths.cpu().tolist(), logp.cpu().tolist()
     B = len(tk)
     # a rank beyond the live count (length -1, score -inf: fewer than `beam` labellings have a non-zero probability) reads ""
@@ -65,13 +89,19 @@ def _beam_to_string(scores, labels, index_to_char, show_text, beam, nbest, retur
     return out
 
 
-def pred_to_string(scores, labels, index_to_char, show_text=False, beam=0, nbest=1, return_scores=False):
+def pred_to_string(scores, labels, index_to_char, show_text=False, beam=0, nbest=1, return_scores=False, lm=None, lm_weight=1.0,
+                   lm_bonus=0.0):
     """Greedy CTC decode of scores [T,B,C]: per-step argmax, collapse repeats, drop index 0.
     [new] beam=K > 0: CTC prefix beam search with K entries instead (beam_decode) -> the most probable labelling per sample;
     nbest=n <= K: a list of the n best strings per sample instead of one string; return_scores=True: (strings, log-probabilities
-    as Python floats of the same nesting).  beam=0 is the greedy path; it has no scores and no second-best reading."""
+    as Python floats of the same nesting).  beam=0 is the greedy path; it has no scores and no second-best reading.
+    [new] lm=CharLM (with beam=K): the search with that character n-gram model fused in (beam_decode_lm), weight lm_weight and
+    per-character bonus lm_bonus; the strings are the fused search's and return_scores gives its TOTAL scores."""
+    if lm is not None and not beam:
+        from qea._lib import QeaError
+        raise QeaError("pred_to_string: lm needs beam=K > 0 (the greedy decode has no search to fuse a prior into)")
     if beam:
-        return _beam_to_string(scores, labels, index_to_char, show_text, int(beam), int(nbest), return_scores)
+        return _beam_to_string(scores, labels, index_to_char, show_text, int(beam), int(nbest), return_scores, lm, lm_weight, lm_bonus)
     if nbest != 1 or return_scores:
         from qea._lib import QeaError
         raise QeaError("pred_to_string: nbest and return_scores need beam=K > 0 (the greedy decode has neither)")
@@ -125,19 +155,23 @@ def compare_labels(preds, labels):
     return correct, total_cer
 
 
-def batch_cers(scores, labels, char_to_index, blank=0, beam=0):
+def batch_cers(scores, labels, char_to_index, blank=0, beam=0, lm=None, lm_weight=1.0, lm_bonus=0.0):
     """Per-sample CER of the greedy decode of `scores` [T,B,C] against `labels`, entirely on the GPU up to
     the final division: decode kernel -> edit-distance kernel -> one [B] int32 copy to the host.  Equals
     [compare_labels([pred_i], [label_i])[1] for i] of the reference loop (train_nn_patch.py:336-342).
-    [new] beam=K > 0: the CER of the best entry of the prefix beam search instead (rank 0 of beam_decode)."""
+    [new] beam=K > 0: the CER of the best entry of the prefix beam search instead (rank 0 of beam_decode); with lm=CharLM, of the
+    search with that model fused in (rank 0 of beam_decode_lm)."""
     from qea import ops
+    if lm is not None and not beam:
+        from qea._lib import QeaError
+        raise QeaError("batch_cers: lm needs beam=K > 0")
     T, B, C = scores.shape
     s = scores.detach()
     if s.stride(2) != 1:
         s = s.contiguous()
     dev = s.device
     if beam:
-        btok, blen, _ = beam_decode(s, int(beam), blank)
+        btok, blen = (beam_decode(s, int(beam), blank) if lm is None else beam_decode_lm(s, int(beam), lm, lm_weight, lm_bonus, blank))[:2]
         # the edit-distance kernel takes rows of at most 128 tokens: rank 0 as a [B][T] slice of its own, not a K * T stride
         # (length -1 = no labelling with a non-zero probability at all: scored as the empty string)
         tokens, plen = btok[:, 0, :].contiguous(), blen[:, 0].clamp(min=0).contiguous()
