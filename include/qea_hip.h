@@ -488,8 +488,9 @@ int qea_crop_pad_gather(const float* img, int32_t H, int32_t W, const int32_t* b
 int qea_crop_pad_scatter(const float* dout, const int32_t* boxes, int32_t N, int32_t OH, int32_t OW, float* dimg,
                          int32_t H, int32_t W, void* stream);
 
-/* utils.pred_to_string (utils.py:74-92): per-step argmax (first maximum), collapse repeats, drop
- * blank -> tokens [N][T] int32 + lengths [N]; scores element (t,n,c) at t*ld_t + n*ld_n + c. */
+/* utils.pred_to_string (utils.py:74-92): per-step argmax (torch.argmax's rule: the first NaN if the row
+ * has one, else the first maximum), collapse repeats, drop blank -> tokens [N][T] int32 + lengths [N];
+ * scores element (t,n,c) at t*ld_t + n*ld_n + c. */
 int qea_greedy_decode(const float* scores, int32_t ld_t, int32_t ld_n, int32_t T, int32_t N, int32_t C, int32_t blank,
                       int32_t* tokens, int32_t* lengths, void* stream);
 

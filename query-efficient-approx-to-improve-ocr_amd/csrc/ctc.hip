@@ -30,8 +30,10 @@ __global__ __launch_bounds__(256) void log_softmax_fwd_kernel(const float* __res
   float s = 0.f;
   for (int c = lane; c < C; c += 64) s += expf(xr[c] - mx);
   s = qea_wave_sum(s);
-  const float lz = mx + logf(s);
-  for (int c = lane; c < C; c += 64) y[row * ldy + c] = xr[c] - lz;
+  // (x - mx) - log s, not x - (mx + log s): the latter rounds at the size of mx, which a common offset of the logits makes arbitrarily
+  // larger than the result
+  const float ls = logf(s);
+  for (int c = lane; c < C; c += 64) y[row * ldy + c] = (xr[c] - mx) - ls;
 }
 
 // dx = g - exp(lp) * sum_c g ; optional NaN -> 0 (models/model_crnn.py:30-32); pad columns -> 0
@@ -40,13 +42,15 @@ __global__ __launch_bounds__(256) void log_softmax_bwd_kernel(const float* __res
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += g[row * ldg + c];
-  s = qea_wave_sum(s);
+  // the row sum and the product with it in fp64: an fp32 sum's rounding, times the row's largest probability, would be the largest
+  // term of the error (a row is C <= a few hundred values: the fp64 adds cost nothing next to the loads)
+  double s = 0.0;
+  for (int c = lane; c < C; c += 64) s += (double)g[row * ldg + c];
+  s = qea_wave_sum_d(s);
   for (int c = lane; c < Cpad; c += 64) {
     float v = 0.f;
     if (c < C) {
-      v = g[row * ldg + c] - expf(lp[row * ldlp + c]) * s;
+      v = (float)((double)g[row * ldg + c] - (double)expf(lp[row * ldlp + c]) * s);
       if (scrub && v != v) v = 0.f;
     }
     dx[row * lddx + c] = v;

@@ -175,7 +175,8 @@ __global__ void crop_pad_scatter_kernel(const float* __restrict__ dout, const in
 }
 
 // ------------------------------------------------------------------ greedy CTC decode
-// one wave per sample: argmax over C per step (first maximum), collapse repeats, drop blank
+// one wave per sample: argmax over C per step (torch.argmax's: the first NaN if the row has one, else the first maximum),
+// collapse repeats, drop blank
 __global__ __launch_bounds__(64) void greedy_decode_kernel(const float* __restrict__ scores, int ld_t, int ld_n, int T, int N, int C, int blank,
                                                            int* __restrict__ tokens, int* __restrict__ lengths) {
   const int n = blockIdx.x, lane = threadIdx.x;
@@ -192,7 +193,10 @@ __global__ __launch_bounds__(64) void greedy_decode_kernel(const float* __restri
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(best, o, 64);
       const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+      // the rule of torch.argmax, across lanes as within one: a NaN ranks above every number, and among equals (or among NaNs)
+      // the smaller index wins.  A total order, so the butterfly leaves the same bi in all 64 lanes.
+      const bool on = ov != ov, bn = best != best;
+      if (on ? (!bn || oi < bi) : (!bn && (ov > best || (ov == best && oi < bi)))) { best = ov; bi = oi; }
     }
     // reference quirk (utils.py:85-88): the first emitted char does not look at the previous index
     if (bi != blank && (len == 0 || bi != prev)) {
