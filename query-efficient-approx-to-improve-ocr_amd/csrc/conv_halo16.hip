@@ -43,9 +43,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_m16_wg
   constexpr bool SMALL = IMW != 0;
   constexpr int IMH = SMALL ? IMW / 4 : 1;
   constexpr int IPX = SMALL ? 32 / IMW : 1, IPY = SMALL ? TH / IMH : 1;
-  constexpr int TW = 32, HW_ = SMALL ? IPX * (IMW + 2) : TW + 2, HH = SMALL ? TH + 1 : TH + 2, HP = HH * HW_;
+  constexpr int TW = 32, HW_ = SMALL ? IPX * (IMW + 2) : TW + 2, HH = SMALL ? TH : TH + 2, HP = HH * HW_;
   static_assert(!SMALL || COUT == 128, "small-image tiles: one wave row");
   constexpr int WN = COUT / 32, WM = 4 / WN, MI = TH / WM;
+  // Padding rows.  A (tile row i, kh) group whose input row lies above or below its image multiplies zeros: it is left out of the loop, and
+  // the row is neither loaded nor staged.  Small images: a compile-time property of (i, kh), so their LDS image has no zero row at all.
+  // Whole-width tiles: the top group of a wave whose first row is image row 0 and the bottom group of one whose last row is image row
+  // H - 1 (wave-uniform: a scalar branch around that group's two half rows alone, so that only their accumulators cross a join — the loop
+  // compiled in whole forms behind one branch cost 40 registers and scratch), and halo rows 0 / TH + 1 of a tile at the top / bottom of
+  // its image stay unstaged.  Only where it paid in the trace (profiles/padding_rows_ab.json): the instances of
+  // the 4- and 8-row maps.  COUT = 64 and the 2 x 2 pool (16-row maps, 1/24 of the groups) and the BatchNorm-backward form keep the
+  // full loop, as does COUT = 32 (one row per wave).
+  constexpr bool EDGE = !SMALL && COUT == 128 && PKW != 2 && !BST;
   constexpr int NG = COUT / 16;                           // 16-channel groups per n-block
   constexpr int PLANE = HP * CIN, PLANE_B = PLANE * 2;
   constexpr int STEPS = 18;                               // 9 taps x two 32-channel k-steps per chunk
@@ -59,7 +68,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_m16_wg
 
   const int tiles_x = W / TW, tiles_y = H / TH;
   const int nblk = Ntot / COUT;
-  struct Item { int nb, tile_id, b, x0, y0; };
+  struct Item { int nb, tile_id, b, x0, y0; bool skt, skb; };   // skt / skb: halo row 0 / TH + 1 is padding that no wave reads
   auto decode = [&](int vb) {
     const int lid = qea_xcd_swizzle(vb, total);
     Item it;
@@ -68,6 +77,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_m16_wg
     if (SMALL) {
       it.b = it.tile_id * (IPX * IPY);
       it.x0 = it.y0 = 0;
+      it.skt = it.skb = false;
       return it;
     }
     int bid = it.tile_id;
@@ -77,35 +87,41 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_m16_wg
     it.b = bid / tiles_y;
     it.x0 = tx * TW;
     it.y0 = ty * TH;
+    it.skt = EDGE && ty == 0;
+    it.skb = EDGE && ty == tiles_y - 1;
     return it;
   };
   auto rot = [](int p, int slot) { return (slot + p) & 7; };
 
   constexpr int C4 = CIN / 4, NLD = (HP * C4 + 255) / 256, QS = 256 / C4;
   f32x4 hv[NLD];
+  // iteration i of the gather / staging loops lies wholly inside a padding row that no wave reads (block-uniform)
+  auto unread = [](const Item& it, int i) { return EDGE && ((it.skt && i * QS + QS <= HW_) || (it.skb && i * QS >= (TH + 1) * HW_)); };
   auto gather = [&](const Item& it, int chunk, int tid) {
     const float* xb = x + (size_t)it.b * H * W * ldx + chunk * CIN + (tid % C4) * 4;
     int q = tid / C4;
     int hy = q / HW_, hx = q - hy * HW_;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      int iy, ix;
-      bool ok;
-      if (SMALL) {
-        const int gx = hx / (IMW + 2);
-        const int img = (hy / IMH) * IPX + gx;
-        ix = hx - gx * (IMW + 2) - 1;
-        iy = (img * IMH + hy % IMH);
-        ok = q < HP && hy < TH && (unsigned)ix < (unsigned)IMW && it.b + img < B;
-      } else {
-        iy = it.y0 + hy - 1;
-        ix = it.x0 + hx - 1;
-        ok = q < HP && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
+      if (!unread(it, i)) {
+        int iy, ix;
+        bool ok;
+        if (SMALL) {
+          const int gx = hx / (IMW + 2);
+          const int img = (hy / IMH) * IPX + gx;
+          ix = hx - gx * (IMW + 2) - 1;
+          iy = (img * IMH + hy % IMH);
+          ok = q < HP && (unsigned)ix < (unsigned)IMW && it.b + img < B;
+        } else {
+          iy = it.y0 + hy - 1;
+          ix = it.x0 + hx - 1;
+          ok = q < HP && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
+        }
+        typedef const __attribute__((address_space(1))) f32x4* gptr;   // (a generic pointer would make these flat loads: lgkmcnt too)
+        const gptr pz = (gptr)(const void*)qea_zero16;
+        const gptr pv = (gptr)(const void*)(xb + ((size_t)iy * W + ix) * ldx);
+        hv[i] = *(ok ? pv : pz);
       }
-      typedef const __attribute__((address_space(1))) f32x4* gptr;   // (a generic pointer would make these flat loads: lgkmcnt too)
-      const gptr pz = (gptr)(const void*)qea_zero16;
-      const gptr pv = (gptr)(const void*)(xb + ((size_t)iy * W + ix) * ldx);
-      hv[i] = *(ok ? pv : pz);
       q += QS;
       hx += QS;
       if (hx >= HW_) {
@@ -114,12 +130,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_m16_wg
       }
     }
   };
-  auto stage = [&](int tid) {
+  auto stage = [&](const Item& it, int tid) {
     const int c4 = tid % C4;
     int q = tid / C4;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      if (q < HP) {
+      if (q < HP && !unread(it, i)) {
         const int o = q * CIN + rot(q, c4 >> 1) * 8 + (c4 & 1) * 4;
         f16x4 h, l;
         qea_split2_f16(hv[i], sx, h, l);
@@ -163,6 +179,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_m16_wg
     const int nvb = vb + gridDim.x;
     const bool has_next = nvb < total;
     const Item nxt = decode(has_next ? nvb : vb);
+    // this wave's first row is the image's first / its last row the image's last (wave-uniform: kept in scalar registers)
+    const bool top = EDGE && __builtin_amdgcn_readfirstlane(cur.y0 + wm * MI) == 0;
+    const bool bot = EDGE && __builtin_amdgcn_readfirstlane(cur.y0 + wm * MI + MI) == H;
     f32x4 acc[MI][4];                                     // [tile row][half row * 2 + channel group]
 #pragma unroll
     for (int i = 0; i < MI; ++i)
@@ -176,29 +195,74 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_m16_wg
       asm volatile("" : "+v"(tid));                       // (the gather / staging addresses are recomputed per chunk, not kept in registers)
       if (!first) __syncthreads();
       first = false;
-      stage(tid);
+      stage(cur, tid);
       __syncthreads();
       if (chunk + 1 < chunks) gather(cur, chunk + 1, tid);
       else if (has_next) gather(nxt, 0, tid);
       constexpr int GR = MI * 2;                          // 16-pixel groups per step
-      auto read_a = [&](int st, int g, f16x8* a) {
+      // Groups whose input row is padding come in pairs (both half rows of tile row i), so the live groups of a step stay an even number
+      // and the A double buffer keeps the parity of g.  dead: known at compile time (small images).  edge: the pair of this wave that
+      // reads the row above / below the tile — left out, by a uniform branch around the pair alone, when that row is padding.
+      auto dead = [](int st, int g) {
+        const int rr = (g / 2) % IMH + st / 6 - 1;
+        return SMALL && (rr < 0 || rr >= IMH);
+      };
+      auto edge = [](int st, int g) { return EDGE && ((st / 6 == 0 && g / 2 == 0) || (st / 6 == 2 && g / 2 == MI - 1)); };
+      auto a_off = [&](int st, int g) {                    // live groups only
         const int tap = st / 2, ks = st % 2;
         const int kh = tap / 3, kw = tap % 3;
         const int i = g / 2, xh = g % 2;
         int c;
         if (SMALL) {
-          const int rr = i % IMH + kh - 1;
-          const int srow = (rr >= 0 && rr < IMH) ? (i / IMH) * IMH + rr : TH;
-          c = srow * HW_ + kw + (IMW == 16 ? xh * 18 : xh * 20);
+          c = (i + kh - 1) * HW_ + kw + (IMW == 16 ? xh * 18 : xh * 20);
         } else {
           c = (i + kh) * HW_ + kw + xh * 16;
         }
-        const char* src = reinterpret_cast<const char*>(As) + T[(ks * 4 + c) & 7] + c * (CIN * 2);
+        return T[(ks * 4 + c) & 7] + c * (CIN * 2);
+      };
+      auto read_at = [&](int off, f16x8* a) {
+        const char* src = reinterpret_cast<const char*>(As) + off;
         a[0] = *reinterpret_cast<const f16x8*>(src);
         a[1] = *reinterpret_cast<const f16x8*>(src + PLANE_B);
       };
       f16x8 ar[2][2];
-      read_a(0, 0, ar[0]);
+      read_at(EDGE ? (top ? a_off(0, 2) : a_off(0, 0)) : a_off(0, dead(0, 0) ? 2 : 0), ar[0]);
+      // one group: the A fragments of the next live group, then this group's six MFMAs
+      auto group = [&](int st, int g) {
+        const int cb = st & 1;
+        int ns = st, ng = g + 1;
+        if (ng < GR && dead(ns, ng)) ng += 2;
+        if (ng >= GR) {
+          ++ns;
+          ng = (ns < STEPS && dead(ns, 0)) ? 2 : 0;
+        }
+        const f16x8* a = ar[g & 1];
+        const bool more = ns < STEPS;
+        if (more) {
+          int off = a_off(ns, ng);
+          if (edge(ns, ng) && !edge(st, g)) {               // the first group of an edge pair: past the pair when it is left out
+            int as = ns, ag = ng + 2;
+            if (ag >= GR) {
+              ++as;
+              ag = 0;
+            }
+            if (as < STEPS) off = (as / 6 == 0 ? top : bot) ? a_off(as, ag) : off;   // (the last pair of all: its row is in LDS, read or not)
+          }
+          read_at(off, ar[ng & 1]);
+        }
+        const int i = g / 2, xh = g % 2;
+        // smallest terms first (ll is dropped): lh, hl, hh — the two channel groups interleaved
+#pragma unroll
+        for (int g2 = 0; g2 < 2; ++g2) acc[i][xh * 2 + g2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], bq[cb][g2][0], acc[i][xh * 2 + g2], 0, 0, 0);
+#pragma unroll
+        for (int g2 = 0; g2 < 2; ++g2) acc[i][xh * 2 + g2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], bq[cb][g2][1], acc[i][xh * 2 + g2], 0, 0, 0);
+#pragma unroll
+        for (int g2 = 0; g2 < 2; ++g2) acc[i][xh * 2 + g2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], bq[cb][g2][0], acc[i][xh * 2 + g2], 0, 0, 0);
+        if (more) {
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // the two LDS reads of the next live group ...
+          __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);   // ... ahead of the six MFMAs of this one
+        }
+      };
 #pragma unroll
       for (int st = 0; st < STEPS; ++st) {
         const int cb = st & 1;
@@ -206,22 +270,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_m16_wg
         else if (has_next) load_b(nxt.nb, 0, cb ^ 1, tid);
         __builtin_amdgcn_sched_barrier(0);                // keep the next step's filter loads AHEAD of this step's MFMAs
 #pragma unroll
-        for (int g = 0; g < GR; ++g) {
-          const int f = st * GR + g;
-          const f16x8* a = ar[f & 1];
-          const bool more = f + 1 < STEPS * GR;
-          if (more) read_a((f + 1) / GR, (f + 1) % GR, ar[(f + 1) & 1]);
-          const int i = g / 2, xh = g % 2;
-          // smallest terms first (ll is dropped): lh, hl, hh — the two channel groups interleaved
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2) acc[i][xh * 2 + g2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], bq[cb][g2][0], acc[i][xh * 2 + g2], 0, 0, 0);
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2) acc[i][xh * 2 + g2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], bq[cb][g2][1], acc[i][xh * 2 + g2], 0, 0, 0);
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2) acc[i][xh * 2 + g2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], bq[cb][g2][0], acc[i][xh * 2 + g2], 0, 0, 0);
-          if (more) {
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // the two LDS reads of group f + 1 ...
-            __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);   // ... ahead of the six MFMAs of group f
+        for (int g = 0; g < GR; g += 2) {
+          if (dead(st, g)) continue;
+          if (edge(st, g)) {
+            if (!(st / 6 == 0 ? top : bot)) {
+              group(st, g);
+              group(st, g + 1);
+            }
+          } else {
+            group(st, g);
+            group(st, g + 1);
           }
         }
       }
@@ -436,7 +494,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(halo_m16_wg
 
 template <int COUT, bool STATS, int IMW = 0, int PKW = 0, bool BST = false>
 int launch_halo_m16_(const ConvArgs& a, hipStream_t s) {
-  constexpr size_t lds = IMW ? (size_t)2 * (4 + 1) * (32 / IMW) * (IMW + 2) * 64 * 2 : (size_t)2 * (4 + 2) * 34 * 64 * 2;
+  constexpr size_t lds = IMW ? (size_t)2 * 4 * (32 / IMW) * (IMW + 2) * 64 * 2 : (size_t)2 * (4 + 2) * 34 * 64 * 2;
   constexpr auto kern = conv3x3_halo_m16_kernel<COUT, STATS, IMW, PKW, BST>;
   const int rc = reserve_lds<kern>("qea_conv_igemm(halo m16)", lds);
   if (rc != QEA_OK) return rc;
