@@ -526,6 +526,26 @@ int qea_ctc_beam_decode_lm(const float* scores, int32_t ld_t, int32_t ld_n, int3
                            const double* lm_table, int32_t lm_context, int32_t* tokens, int32_t* lengths, double* ctc_scores,
                            double* total_scores, void* stream);
 
+/* The plain search restricted to the paths of a deterministic automaton over the non-blank classes (DESIGN.md "Automaton-constrained
+ * search"; a word-list trie is the usual one: qea/lexicon.py); everything said for qea_ctc_beam_decode stands, plus:
+ *   S >= 1 states, state 0 the start, E edges in CSR form: first [S+1] int32 (first[0] = 0, non-decreasing, first[S] = E), the edges of
+ *   state s are first[s] .. first[s+1]-1; label [E] int32, the class of each edge, strictly ascending within a state, never the blank;
+ *   child [E] int32, the target state.  Which states accept is the host's business: the device never sees it.
+ *   A beam entry also carries a state, 0 for the empty prefix.  Slot c of entry i exists only when state(i) has an edge labelled c (a
+ *   slot that does not exist scores -inf, exactly like a folded one); the new entry carries that edge's child; slot 0 keeps its state.
+ *   Folding, pb / pnb / tot, the candidate order and the stable selection are unchanged, and the scores stay pure CTC quantities: a
+ *   returned score is the CTC log-likelihood of that labelling.
+ *   states [N][K] int32: the state of rank k, -1 beyond the live count.  The whole last beam is returned, accepted or not.
+ *   Tables that break the statements above cannot make the kernel read outside the four arrays: an edge whose label is the blank or
+ *   outside 0..C-1, or whose child is outside 0..S-1, is absent, and the values of `first` are clamped to 0..E.
+ *   With the one-state automaton that loops on every class, tokens, lengths and beam_scores are qea_ctc_beam_decode's bit for bit.
+ * Refused before any launch: what qea_ctc_beam_decode refuses, S < 1, E outside 0..2^26-1 (the edges of up to 32 live states are
+ * counted in an int32), NULL first / label / child / states.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects it by symbol.) */
+int qea_ctc_beam_decode_dfa(const float* scores, int32_t ld_t, int32_t ld_n, int32_t T, int32_t N, int32_t C, int32_t blank, int32_t K,
+                            const int32_t* first, const int32_t* label, const int32_t* child, int32_t S, int32_t E, int32_t* tokens,
+                            int32_t* lengths, double* beam_scores, int32_t* states, void* stream);
+
 /* Unit-cost edit distance between the greedy decode of each sample (pred_tokens [N][ldp], pred_len)
  * and its ground-truth token string (concatenated gt_tokens, gt_offsets, gt_len): the numerator of
  * utils.compare_labels' CER (utils.py:95-110, python-Levenshtein `distance`); the host divides by

@@ -21,6 +21,11 @@ The printed lines are the reference's.  Differences, all deliberate:
     weight --lm_weight, per-character bonus --lm_bonus: the strings are the fused search's.  The dict then also has lm_order,
     lm_weight, lm_bonus, crnn_mean_total_score (the mean of the scores the search ranked by) and lm_disagreements (the strips the plain
     beam of the same K reads differently); crnn_mean_log_score stays the mean CTC log-probability of the chosen readings.
+  * [new] --lexicon PATH (with --beam K, not with --lm) keeps the search inside the word list of that file (qea/lexicon.py, written by
+    lexicon_cli.py; utils.pred_to_string(beam=K, lexicon=)): a strip reads as its best-ranked entry that is a word of the list, and
+    as the plain beam's best where none of its K is.  The dict then also has lexicon_words, lexicon_misses (the strips with no word
+    among their K), lexicon_disagreements (the strips the plain beam of the same K reads differently) and lexicon_oov_labels (the
+    ground-truth labels that are not in the list: they bound the accuracy).
   * The loaders run in the main process (the reference asks for properties.num_workers workers).
 `backend` / `dataset` / `ocr` are injection seams for tests, as in the trainers; the default backend is the HIP path.
 """
@@ -30,7 +35,7 @@ import torch
 
 import properties
 from qea.trainer_core import hip_backend
-from utils import beam_decode_lm, compare_labels, get_char_maps, get_ocr_helper, get_text_stack, pred_to_string, show_img
+from utils import beam_decode_lm, compare_labels, lexicon_best, get_char_maps, get_ocr_helper, get_text_stack, pred_to_string, show_img
 
 
 class EvalCRNN:
@@ -50,6 +55,10 @@ class EvalCRNN:
         self.lm, self.beam_total_score, self.lm_disagreements = None, 0.0, 0
         if self.lm_path and not self.beam:
             raise ValueError("--lm needs --beam K: the model is fused into the prefix beam search")
+        self.lexicon_path = getattr(args, "lexicon", None)           # [new] --lexicon PATH: the search stays inside a word list
+        self.lexicon, self.lexicon_misses, self.lexicon_disagreements, self.lexicon_oov_labels = None, 0, 0, 0
+        if self.lexicon_path and (not self.beam or self.lm_path):
+            raise ValueError("--lexicon needs --beam K and cannot be combined with --lm")
         self.input_size = properties.input_size
         if self.dataset_name == "vgg":
             self.test_set = os.path.join(args.data_base_path, properties.vgg_text_dataset_test)
@@ -69,6 +78,9 @@ class EvalCRNN:
         if self.lm_path:
             from qea.lm import CharLM
             self.lm = CharLM.load(self.lm_path, self.char_to_index)
+        if self.lexicon_path:
+            from qea.lexicon import Lexicon
+            self.lexicon = Lexicon.load(self.lexicon_path, self.char_to_index)
 
         n = getattr(args, "synthetic_size", None)
         if self.dataset_name == "pos":
@@ -109,6 +121,16 @@ class EvalCRNN:
             self.lm_disagreements += sum(int(p != q) for p, q in zip(preds, plain))
             self.greedy_disagreements += sum(int(p != q) for p, q in zip(preds, greedy))
             return preds
+        if self.lexicon is not None:                                  # the best-ranked word of the list, the plain beam's best on a miss
+            tokens, lengths, logp, miss = (v.cpu().tolist() for v in lexicon_best(scores, self.beam, self.lexicon))
+            preds = ["".join(self.index_to_char[i] for i in tk[0][:max(n[0], 0)]) for tk, n in zip(tokens, lengths)]
+            plain = pred_to_string(scores, labels, self.index_to_char, beam=self.beam)
+            self.beam_log_score += sum(lp[0] for lp in logp)
+            self.lexicon_misses += sum(int(m) for m in miss)
+            self.lexicon_disagreements += sum(int(p != q) for p, q in zip(preds, plain))
+            self.lexicon_oov_labels += sum(int(not self.lexicon.accepts_string(l, self.char_to_index)) for l in labels)
+            self.greedy_disagreements += sum(int(p != q) for p, q in zip(preds, greedy))
+            return preds
         preds, logp = pred_to_string(scores, labels, self.index_to_char, beam=self.beam, return_scores=True)
         self.beam_log_score += sum(logp)
         self.greedy_disagreements += sum(int(p != q) for p, q in zip(preds, greedy))
@@ -134,12 +156,19 @@ class EvalCRNN:
                        crnn_mean_total_score=self.beam_total_score / max(1, count), lm_disagreements=self.lm_disagreements)
             print("Character {:d}-gram fused (weight {:g}, bonus {:g}): mean total score {:.5f}, differs from the plain beam on {:d}/{:d} strips".format(
                 self.lm.order, self.lm_weight, self.lm_bonus, res["crnn_mean_total_score"], self.lm_disagreements, count))
+        if self.lexicon is not None:
+            res.update(lexicon_words=self.lexicon.num_words, lexicon_misses=self.lexicon_misses,
+                       lexicon_disagreements=self.lexicon_disagreements, lexicon_oov_labels=self.lexicon_oov_labels)
+            print("Lexicon of {} words: no word among the {:d} entries of {:d}/{:d} strips, differs from the plain beam on {:d}, {:d} labels "
+                  "are not in the lexicon".format(self.lexicon.num_words, self.beam, self.lexicon_misses, count, self.lexicon_disagreements,
+                                                  self.lexicon_oov_labels))
         return res
 
     def eval_area(self):
         print("Eval with ", self.ocr_name)
         self.crnn_model.eval()
         self.beam_log_score, self.greedy_disagreements, self.beam_total_score, self.lm_disagreements = 0.0, 0, 0.0, 0
+        self.lexicon_misses, self.lexicon_disagreements, self.lexicon_oov_labels = 0, 0, 0
         crnn_correct_count, ori_correct_count, ori_cer, crnn_cer = 0, 0, 0.0, 0.0
         with torch.no_grad():
             for batch in self.loader_eval:
@@ -170,6 +199,7 @@ class EvalCRNN:
         print("Eval with ", self.ocr_name)
         self.crnn_model.eval()
         self.beam_log_score, self.greedy_disagreements, self.beam_total_score, self.lm_disagreements = 0.0, 0, 0.0, 0
+        self.lexicon_misses, self.lexicon_disagreements, self.lexicon_oov_labels = 0, 0, 0
         ori_lbl_crt_count, ori_lbl_cer, lbl_count, crnn_correct_count, crnn_cer = 0, 0.0, 0, 0, 0.0
         with torch.no_grad():
             for i in range(len(self.dataset)):

@@ -10,6 +10,10 @@ beam, so equal scores keep that order.
 With lm_table (qea_ctc_beam_decode_lm, DESIGN.md "Character n-gram fusion") an entry also carries lm, the sum of the fused-table
 entries along its prefix, and ctx, the index of its last lm_context tokens (BOS = the blank index on the left).  A second [live, C]
 table then holds the RANKING scores, CTC term + lm, and the sort runs on that one; pb / pnb stay pure CTC quantities.
+
+With automaton (qea_ctc_beam_decode_dfa, DESIGN.md "Automaton-constrained search") an entry also carries a state of a deterministic
+automaton over the non-blank classes; a column whose class has no edge out of the row's state is -inf, like a folded one, and an
+extension takes the edge's child.  Scores are unchanged CTC quantities.
 """
 import math
 import os
@@ -19,6 +23,7 @@ import torch
 
 MAX_K, MAX_C, MAX_T = 32, 256, 512           # the limits of qea_ctc_beam_decode
 MAX_LM_CONTEXT, MAX_LM_ENTRIES = 2, 1 << 21  # and of qea_ctc_beam_decode_lm: C ** (context + 1) fp64 table entries, 16 MB
+MAX_DFA_EDGES = (1 << 26) - 1                # and of qea_ctc_beam_decode_dfa: K edge lists end to end are counted in an int32
 _NEG = -math.inf
 
 
@@ -62,10 +67,42 @@ def start_context(C, context, blank):
     return sum(blank * C ** q for q in range(context))
 
 
-def decode_sample(lp, K, blank=0, lm_table=None, lm_context=0):
+def automaton_edges(automaton, C, blank):
+    """automaton: a qea.lexicon.Lexicon, or any object or tuple with first / label / child -> a function state -> {class: child} of the
+    edges that exist (DESIGN.md "Automaton-constrained search": a label that is the blank or outside 0..C-1 and a child outside
+    0..S-1 make an edge absent, the values of `first` are clamped to 0..E), filled in state by state as the search asks."""
+    if isinstance(automaton, (tuple, list)):
+        first, label, child = automaton[:3]
+    else:
+        first, label, child = automaton.first, automaton.label, automaton.child
+    first, label, child = (np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64) for a in (first, label, child))
+    S, E = len(first) - 1, min(len(label), len(child))
+    known = {}
+
+    def edges(state):
+        if state not in known:
+            lo, hi = (int(min(max(first[s], 0), E)) for s in (state, state + 1))
+            out = {}
+            for c, ch in zip(label[lo:hi].tolist(), child[lo:hi].tolist()):
+                if c != blank and 0 <= c < C and 0 <= ch < S and c not in out:
+                    out[c] = ch
+            known[state] = out
+        return known[state]
+    return edges
+
+
+def decode_sample(lp, K, blank=0, lm_table=None, lm_context=0, automaton=None):
     """lp [T][C] float32 (numpy) -> [(prefix tuple, score)] of at most K entries, best first.  With lm_table (fp64 numpy
-    [C ** lm_context, C]) the search is the fused one and the entries are (prefix tuple, ctc, total)."""
+    [C ** lm_context, C]) the search is the fused one and the entries are (prefix tuple, ctc, total).  With automaton (see
+    automaton_edges; not together with lm_table) the search is the constrained one and the entries are (prefix tuple, score, state)."""
     T, C = lp.shape
+    edges = None
+    if automaton is not None:
+        if lm_table is not None:
+            from ._lib import QeaError
+            raise QeaError("ctc_beam_decode: an automaton together with an lm_table is not supported")
+        edges = automaton if callable(automaton) else automaton_edges(automaton, C, blank)
+        dfa = [0]                                                                   # the state of every beam entry
     lp = lp.astype(np.float64)
     lp[np.isnan(lp)] = _NEG
     classes = np.array([c for c in range(C) if c != blank], dtype=np.int64)          # column s of the table holds classes[s - 1]
@@ -88,6 +125,11 @@ def decode_sample(lp, K, blank=0, lm_table=None, lm_context=0):
             table[i, 1:] = tot[i] + row[classes]
             if p:
                 table[i, column[p[-1]]] = pb + row[p[-1]]                          # a repeat of the last token needs a blank between
+            if edges is not None:                                                   # a slot without an edge does not exist
+                gone = np.ones(C, dtype=bool)
+                gone[[column[c] for c in edges(dfa[i])]] = False
+                gone[0] = False
+                table[i, gone] = _NEG
         for j, (p, _, _) in enumerate(beam):                                        # an extension that is entry j: fold it into j
             i = rank.get(p[:-1]) if p else None
             if i is not None:
@@ -105,11 +147,13 @@ def decode_sample(lp, K, blank=0, lm_table=None, lm_context=0):
             flat = table.ravel()
         flat[np.isnan(flat)] = _NEG
         order = np.argsort(-flat, kind="stable")[:K]
-        nxt, nstate = [], []
+        nxt, nstate, ndfa = [], [], []
         for idx in order.tolist():
             if flat[idx] == _NEG:
                 break
             i, s = divmod(idx, C)
+            if edges is not None:                                                   # a stay keeps its state, an extension takes the edge
+                ndfa.append(dfa[i] if s == 0 else edges(dfa[i])[int(classes[s - 1])])
             if s == 0:
                 nxt.append((beam[i][0], stay_pb[i], stay_pnb[i]))
             else:
@@ -119,18 +163,40 @@ def decode_sample(lp, K, blank=0, lm_table=None, lm_context=0):
         beam = nxt
         if fused:
             state = nstate
+        if edges is not None:
+            dfa = ndfa
+    if edges is not None:
+        return [(p, lse(pb, pnb), st) for (p, pb, pnb), st in zip(beam, dfa)]
     if fused:
         return [(p, lse(pb, pnb), lse(pb, pnb) + lm) for (p, pb, pnb), (lm, _) in zip(beam, state)]
     return [(p, lse(pb, pnb)) for p, pb, pnb in beam]
 
 
-def ctc_beam_decode(scores, K, blank=0, lm_table=None, lm_context=0):
+def ctc_beam_decode(scores, K, blank=0, lm_table=None, lm_context=0, automaton=None):
     """scores [T,N,C] float32 (any device) -> (tokens int32 [N,K,T], lengths int32 [N,K], scores float64 [N,K]) on the CPU, in the
     layout of qea.ops.ctc_beam_decode: -1 behind every prefix, length -1 and score -inf in the rows beyond the live count.
     With lm_table (a float64 tensor or array [C ** lm_context, C]): the fused search, in the layout of qea.ops.ctc_beam_decode_lm,
-    (tokens, lengths, ctc float64 [N,K], total float64 [N,K])."""
+    (tokens, lengths, ctc float64 [N,K], total float64 [N,K]).
+    With automaton (a qea.lexicon.Lexicon, or first / label / child as attributes or a tuple; not together with lm_table): the
+    constrained search, in the layout of qea.ops.ctc_beam_decode_dfa, (tokens, lengths, scores, states int32 [N,K], -1 beyond the
+    live count)."""
     T, N, C = scores.shape
     check_limits(T, C, int(K), int(blank))
+    if automaton is not None:
+        from ._lib import QeaError
+        if lm_table is not None:
+            raise QeaError("ctc_beam_decode: an automaton together with an lm_table is not supported")
+        edges = automaton_edges(automaton, C, int(blank))
+        lp = scores.detach().to("cpu", torch.float32).numpy()
+        tokens = np.full((N, K, T), -1, dtype=np.int32)
+        lengths = np.full((N, K), -1, dtype=np.int32)
+        out = np.full((N, K), _NEG, dtype=np.float64)
+        states = np.full((N, K), -1, dtype=np.int32)
+        for n in range(N):
+            for k, (p, s, st) in enumerate(decode_sample(lp[:, n, :], int(K), int(blank), automaton=edges)):
+                tokens[n, k, :len(p)] = p
+                lengths[n, k], out[n, k], states[n, k] = len(p), s, st
+        return torch.from_numpy(tokens), torch.from_numpy(lengths), torch.from_numpy(out), torch.from_numpy(states)
     fused = lm_table is not None
     if fused:
         lm_context = int(lm_context)

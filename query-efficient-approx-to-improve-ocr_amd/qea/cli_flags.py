@@ -122,6 +122,9 @@ FLAGS += [
     ("--lm_weight", dict(type=float, default=1.0, help="[new] --lm: weight of the model's log-probabilities"), "e"),
     ("--lm_bonus", dict(type=float, default=0.0, help="[new] --lm: bonus per character (the model has no end-of-word term: this is the "
                                                       "length control)"), "e"),
+    ("--lexicon", dict(help="[new] --beam K: keep the prefix beam search inside the word list of this file (written by lexicon_cli.py) and read "
+                            "each strip as its best-ranked entry that is a word of the list; a strip with none among its K reads as the plain "
+                            "beam's best.  Not together with --lm"), "e"),
     ("--graph", dict(action="store_true", help="[new] replay the warm-up step (CRNN -> CTC -> backward -> Adam) as ONE hipGraph per (batch size, "
                                                "width, target-length cap, lr); the first two steps of a shape run eagerly, single-process runs only"),
      "c"),

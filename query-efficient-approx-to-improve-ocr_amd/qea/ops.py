@@ -922,6 +922,40 @@ def ctc_beam_decode_lm(scores, K, table, context, blank=0):
     return tokens, lengths, ctc, total
 
 
+def ctc_beam_decode_dfa(scores, K, automaton, blank=0):
+    """The prefix beam search restricted to the paths of a deterministic automaton (include/qea_hip.h: qea_ctc_beam_decode_dfa): scores
+    as for ctc_beam_decode, automaton = what qea.lexicon.Lexicon.device(scores.device) returns (the validated tables; nothing else
+    is taken) -> (tokens int32 [N,K,T], lengths int32 [N,K], scores float64 [N,K], states int32 [N,K], -1 beyond the live count), best
+    first, on the device and without a synchronisation.  The whole last beam is returned: automaton.final[state] says which ranks
+    are accepted.  Raises QeaError for what ctc_beam_decode refuses, anything but a DeviceAutomaton, and one of another device, class
+    count or blank."""
+    from .lexicon import DeviceAutomaton
+    if scores.dim() != 3 or not scores.is_cuda or scores.dtype != torch.float32:
+        raise _lib.QeaError("ctc_beam_decode_dfa needs a CUDA float32 tensor [T,N,C] (there is no CPU path here: qea.beam has one)")
+    if scores.stride(2) != 1:
+        raise _lib.QeaError("ctc_beam_decode_dfa needs a unit class stride: make the last dimension contiguous")
+    if not (0 <= scores.stride(0) < 2 ** 31 and 0 <= scores.stride(1) < 2 ** 31):
+        raise _lib.QeaError("ctc_beam_decode_dfa: the T and N strides must fit 32 bits")
+    if not isinstance(automaton, DeviceAutomaton):
+        raise _lib.QeaError("ctc_beam_decode_dfa takes the object Lexicon.device() returns: the tables it holds are validated")
+    T, N, C_ = scores.shape
+    K, blank = int(K), int(blank)
+    if automaton.device != scores.device:
+        raise _lib.QeaError(f"ctc_beam_decode_dfa: the automaton is on {automaton.device}, the scores on {scores.device}")
+    if automaton.num_classes != C_ or automaton.blank != blank:
+        raise _lib.QeaError(f"ctc_beam_decode_dfa: the automaton has {automaton.num_classes} classes and blank {automaton.blank}, "
+                            f"the scores {C_} and {blank}")
+    rows = max(K, 1)
+    tokens = torch.empty(N, rows, T, dtype=torch.int32, device=scores.device)
+    lengths = torch.empty(N, rows, dtype=torch.int32, device=scores.device)
+    out = torch.empty(N, rows, dtype=torch.float64, device=scores.device)
+    states = torch.empty(N, rows, dtype=torch.int32, device=scores.device)
+    _lib.check(_lib.lib().qea_ctc_beam_decode_dfa(_ptr(scores), scores.stride(0), scores.stride(1), T, N, C_, blank, K, _ptr(automaton.first),
+                                                  _ptr(automaton.label), _ptr(automaton.child), automaton.num_states, automaton.num_edges,
+                                                  _ptr(tokens), _ptr(lengths), _ptr(out), _ptr(states), _stream()), "qea_ctc_beam_decode_dfa")
+    return tokens, lengths, out, states
+
+
 def prof_read_launches(klass, capacity=4096):
     import numpy as np
     ms = np.zeros(capacity)

@@ -7,7 +7,8 @@ GPU-side work goes through the HIP library: greedy CTC decode (one wave per samp
 Python loop with an .item() per (b,t)), crop + pad gather with a scatter-add backward.  [new] beam_decode and the
 beam= / nbest= / return_scores= arguments of pred_to_string and batch_cers add a CTC prefix beam search (csrc/ctc_beam.hip for CUDA
 scores, qea/beam.py on the host), and beam_decode_lm / lm= / lm_weight= / lm_bonus= fuse a character n-gram prior (qea/lm.py) into
-that search; the reference has no beam and the defaults are its greedy decode.  The optional
+that search; beam_decode_lexicon / lexicon= keep it inside a word list (qea/lexicon.py); the reference has no beam and the defaults
+are its greedy decode.  The optional
 third-party pieces of the reference file (wandb, optuna, unidecode, Levenshtein, torchvision) are
 imported lazily and only where the corresponding feature is used."""
 import json
@@ -67,11 +68,64 @@ def beam_decode_lm(scores, beam, lm, alpha=1.0, beta=0.0, blank=0):
     return tuple(v.to(s.device) for v in host_beam.ctc_beam_decode(s, beam, blank, lm.fused(alpha, beta, "cpu"), lm.context))
 
 
-def _beam_to_string(scores, labels, index_to_char, show_text, beam, nbest, return_scores, lm=None, lm_weight=1.0, lm_bonus=0.0):
+def beam_decode_lexicon(scores, beam, lexicon, blank=0):
+    """[new] beam_decode restricted to the paths of `lexicon` (qea.lexicon.Lexicon: a word-list trie or any deterministic automaton
+    over the non-blank classes): an extension that leaves the automaton does not exist -> (tokens int32 [B,K,T], lengths int32
+    [B,K], log-probabilities float64 [B,K], accepted bool [B,K]), the whole last beam, best first; accepted marks the ranks that end
+    in an accepting state (whole words).  The scores are CTC log-likelihoods, as in beam_decode.  CUDA tensors: one launch
+    (qea.ops.ctc_beam_decode_dfa) on tables uploaded once, no synchronisation; CPU tensors, or QEA_BEAM=host: the host loop."""
+    from qea import beam as host_beam
+    from qea._lib import QeaError
+    s = scores.detach()
+    if lexicon.num_classes != s.shape[2] or lexicon.blank != blank:
+        raise QeaError(f"beam_decode_lexicon: the lexicon has {lexicon.num_classes} classes and blank {lexicon.blank}, the scores "
+                       f"{s.shape[2]} and {blank}")
+    if s.is_cuda and not host_beam.use_host():
+        from qea import ops
+        if s.dtype != torch.float32:
+            s = s.float()
+        if s.stride(2) != 1:
+            s = s.contiguous()
+        automaton = lexicon.device(s.device)
+        tokens, lengths, logp, states = ops.ctc_beam_decode_dfa(s, beam, automaton, blank)
+        final = automaton.final
+    else:
+        tokens, lengths, logp, states = (v.to(s.device) for v in host_beam.ctc_beam_decode(s, beam, blank, automaton=lexicon))
+        final = lexicon.device(s.device).final
+    accepted = (states >= 0) & (final[states.clamp(min=0).long()] != 0)
+    return tokens, lengths, logp, accepted
+
+
+def lexicon_best(scores, beam, lexicon, blank=0, nbest=1):
+    """[new] The nbest best-ranked ACCEPTED entries of beam_decode_lexicon per strip -> (tokens int32 [B,n,T], lengths int32 [B,n],
+    log-probabilities float64 [B,n], miss bool [B]); ranks beyond a strip's accepted count have length -1 and score -inf.  A strip
+    with no accepted entry among its K (miss) reads as the plain search of the same K: one extra beam_decode over those strips only."""
+    if not 1 <= nbest <= beam:
+        from qea._lib import QeaError
+        raise QeaError(f"lexicon_best: nbest={nbest} outside 1..beam={beam}")
+    tokens, lengths, logp, accepted = beam_decode_lexicon(scores, beam, lexicon, blank)
+    B, K, T = tokens.shape
+    order = torch.sort((~accepted).to(torch.int32), dim=1, stable=True).indices[:, :nbest]       # accepted ranks first, in rank order
+    count = accepted.sum(dim=1)
+    tokens = tokens.gather(1, order[:, :, None].expand(B, nbest, T))
+    lengths, logp = lengths.gather(1, order), logp.gather(1, order)
+    behind = torch.arange(nbest, device=tokens.device)[None, :] >= count[:, None]
+    tokens[behind], lengths[behind], logp[behind] = -1, -1, -float("inf")
+    miss = count == 0
+    strips = miss.nonzero().flatten()
+    if strips.numel():
+        pt, pl, ps = beam_decode(scores.detach()[:, strips], beam, blank)
+        tokens[strips], lengths[strips], logp[strips] = pt[:, :nbest], pl[:, :nbest], ps[:, :nbest]
+    return tokens, lengths, logp, miss
+
+
+def _beam_to_string(scores, labels, index_to_char, show_text, beam, nbest, return_scores, lm=None, lm_weight=1.0, lm_bonus=0.0, lexicon=None):
     from qea._lib import QeaError
     if not 1 <= nbest <= beam:
         raise QeaError(f"pred_to_string: nbest={nbest} outside 1..beam={beam}")
-    if lm is None:
+    if lexicon is not None:
+        tokens, lengths, logp, _ = lexicon_best(scores, beam, lexicon, 0, nbest)
+    elif lm is None:
         tokens, lengths, logp = beam_decode(scores, beam, 0)
     else:                                                              # the scores returned are the totals: what decided the order
         tokens, lengths, _, logp = beam_decode_lm(scores, beam, lm, lm_weight, lm_bonus, 0)
@@ -90,18 +144,24 @@ def _beam_to_string(scores, labels, index_to_char, show_text, beam, nbest, retur
 
 
 def pred_to_string(scores, labels, index_to_char, show_text=False, beam=0, nbest=1, return_scores=False, lm=None, lm_weight=1.0,
-                   lm_bonus=0.0):
+                   lm_bonus=0.0, lexicon=None):
     """Greedy CTC decode of scores [T,B,C]: per-step argmax, collapse repeats, drop index 0.
     [new] beam=K > 0: CTC prefix beam search with K entries instead (beam_decode) -> the most probable labelling per sample;
     nbest=n <= K: a list of the n best strings per sample instead of one string; return_scores=True: (strings, log-probabilities
     as Python floats of the same nesting).  beam=0 is the greedy path; it has no scores and no second-best reading.
     [new] lm=CharLM (with beam=K): the search with that character n-gram model fused in (beam_decode_lm), weight lm_weight and
-    per-character bonus lm_bonus; the strings are the fused search's and return_scores gives its TOTAL scores."""
+    per-character bonus lm_bonus; the strings are the fused search's and return_scores gives its TOTAL scores.
+    [new] lexicon=Lexicon (with beam=K, not with lm): the search stays inside that word list (beam_decode_lexicon) and the strings are
+    its best-ranked entries that are whole words, with their CTC log-probabilities; a strip with no word among its K reads as the
+    plain search of the same K (lexicon_best)."""
     if lm is not None and not beam:
         from qea._lib import QeaError
         raise QeaError("pred_to_string: lm needs beam=K > 0 (the greedy decode has no search to fuse a prior into)")
+    if lexicon is not None and (lm is not None or not beam):
+        from qea._lib import QeaError
+        raise QeaError("pred_to_string: lexicon needs beam=K > 0 and cannot be combined with lm")
     if beam:
-        return _beam_to_string(scores, labels, index_to_char, show_text, int(beam), int(nbest), return_scores, lm, lm_weight, lm_bonus)
+        return _beam_to_string(scores, labels, index_to_char, show_text, int(beam), int(nbest), return_scores, lm, lm_weight, lm_bonus, lexicon)
     if nbest != 1 or return_scores:
         from qea._lib import QeaError
         raise QeaError("pred_to_string: nbest and return_scores need beam=K > 0 (the greedy decode has neither)")
@@ -155,23 +215,30 @@ def compare_labels(preds, labels):
     return correct, total_cer
 
 
-def batch_cers(scores, labels, char_to_index, blank=0, beam=0, lm=None, lm_weight=1.0, lm_bonus=0.0):
+def batch_cers(scores, labels, char_to_index, blank=0, beam=0, lm=None, lm_weight=1.0, lm_bonus=0.0, lexicon=None):
     """Per-sample CER of the greedy decode of `scores` [T,B,C] against `labels`, entirely on the GPU up to
     the final division: decode kernel -> edit-distance kernel -> one [B] int32 copy to the host.  Equals
     [compare_labels([pred_i], [label_i])[1] for i] of the reference loop (train_nn_patch.py:336-342).
     [new] beam=K > 0: the CER of the best entry of the prefix beam search instead (rank 0 of beam_decode); with lm=CharLM, of the
-    search with that model fused in (rank 0 of beam_decode_lm)."""
+    search with that model fused in (rank 0 of beam_decode_lm); with lexicon=Lexicon (not with lm), of the best-ranked whole word of
+    the search inside that word list, and of the plain search's rank 0 where a strip has none (lexicon_best)."""
     from qea import ops
     if lm is not None and not beam:
         from qea._lib import QeaError
         raise QeaError("batch_cers: lm needs beam=K > 0")
+    if lexicon is not None and (lm is not None or not beam):
+        from qea._lib import QeaError
+        raise QeaError("batch_cers: lexicon needs beam=K > 0 and cannot be combined with lm")
     T, B, C = scores.shape
     s = scores.detach()
     if s.stride(2) != 1:
         s = s.contiguous()
     dev = s.device
     if beam:
-        btok, blen = (beam_decode(s, int(beam), blank) if lm is None else beam_decode_lm(s, int(beam), lm, lm_weight, lm_bonus, blank))[:2]
+        if lexicon is not None:
+            btok, blen = lexicon_best(s, int(beam), lexicon, blank)[:2]
+        else:
+            btok, blen = (beam_decode(s, int(beam), blank) if lm is None else beam_decode_lm(s, int(beam), lm, lm_weight, lm_bonus, blank))[:2]
         # the edit-distance kernel takes rows of at most 128 tokens: rank 0 as a [B][T] slice of its own, not a K * T stride
         # (length -1 = no labelling with a non-zero probability at all: scored as the empty string)
         tokens, plen = btok[:, 0, :].contiguous(), blen[:, 0].clamp(min=0).contiguous()
