@@ -2,7 +2,8 @@
 search") as a numpy fp64 loop.  It decodes CPU tensors for utils.pred_to_string, and QEA_BEAM=host sends CUDA tensors through it too
 (an A/B switch like QEA_SAMPLER=host); the device kernel (csrc/ctc_beam.hip) returns the same beams.
 
-A beam entry is (prefix, pb, pnb): the log-probabilities of the prefix over the alignments that end in blank / in non-blank.  The
+A beam entry is (prefix, pb, pnb, x): the log-probabilities of the prefix over the alignments that end in blank / in non-blank,
+and x, what the mode adds to an entry (None in the plain search, (lm, ctx) in the fused one, the state in the constrained one).  The
 candidates of a step are laid out as a [live, C] table: row = beam rank, column 0 = the prefix itself, column s >= 1 = the prefix
 plus the s-th non-blank class.  Row-major order of that table is the candidate order, and a stable descending sort picks the next
 beam, so equal scores keep that order.
@@ -20,6 +21,8 @@ import os
 
 import numpy as np
 import torch
+
+from ._lib import QeaError
 
 MAX_K, MAX_C, MAX_T = 32, 256, 512           # the limits of qea_ctc_beam_decode
 MAX_LM_CONTEXT, MAX_LM_ENTRIES = 2, 1 << 21  # and of qea_ctc_beam_decode_lm: C ** (context + 1) fp64 table entries, 16 MB
@@ -40,7 +43,6 @@ def lse(a, b):
 
 
 def check_limits(T, C, K, blank):
-    from ._lib import QeaError
     if not 1 <= K <= MAX_K:
         raise QeaError(f"ctc_beam_decode: K={K} outside 1..{MAX_K}")
     if not 2 <= C <= MAX_C:
@@ -53,7 +55,6 @@ def check_limits(T, C, K, blank):
 
 def check_lm_limits(C, context, table_shape=None):
     """The fused search's own limits; table_shape, where given, must be (C ** context, C)."""
-    from ._lib import QeaError
     if not 0 <= context <= MAX_LM_CONTEXT:
         raise QeaError(f"ctc_beam_decode_lm: lm_context={context} outside 0..{MAX_LM_CONTEXT}")
     if C ** (context + 1) > MAX_LM_ENTRIES:
@@ -91,46 +92,48 @@ def automaton_edges(automaton, C, blank):
     return edges
 
 
+def _refuse_both(lm_table, automaton):
+    if lm_table is not None and automaton is not None:
+        raise QeaError("ctc_beam_decode: an automaton together with an lm_table is not supported")
+
+
 def decode_sample(lp, K, blank=0, lm_table=None, lm_context=0, automaton=None):
     """lp [T][C] float32 (numpy) -> [(prefix tuple, score)] of at most K entries, best first.  With lm_table (fp64 numpy
     [C ** lm_context, C]) the search is the fused one and the entries are (prefix tuple, ctc, total).  With automaton (see
     automaton_edges; not together with lm_table) the search is the constrained one and the entries are (prefix tuple, score, state)."""
     T, C = lp.shape
-    edges = None
+    _refuse_both(lm_table, automaton)
+    fused, edges, start = lm_table is not None, None, None                          # start: the mode's part x of the first entry
     if automaton is not None:
-        if lm_table is not None:
-            from ._lib import QeaError
-            raise QeaError("ctc_beam_decode: an automaton together with an lm_table is not supported")
         edges = automaton if callable(automaton) else automaton_edges(automaton, C, blank)
-        dfa = [0]                                                                   # the state of every beam entry
+        start = 0                                                                   # x = the state
     lp = lp.astype(np.float64)
     lp[np.isnan(lp)] = _NEG
     classes = np.array([c for c in range(C) if c != blank], dtype=np.int64)          # column s of the table holds classes[s - 1]
     column = {int(c): s + 1 for s, c in enumerate(classes)}
-    fused = lm_table is not None
     if fused:
         W = np.where(np.isnan(lm_table), _NEG, lm_table)
         mod = C ** lm_context
-        state = [(0.0, start_context(C, lm_context, blank))]                       # (lm, ctx) per beam entry
-    beam = [((), 0.0, _NEG)]
+        start = (0.0, start_context(C, lm_context, blank))                         # x = (lm, ctx)
+    beam = [((), 0.0, _NEG, start)]
     for t in range(T):
         row = lp[t]
         live = len(beam)
-        rank = {p: j for j, (p, _, _) in enumerate(beam)}
-        tot = [lse(pb, pnb) for _, pb, pnb in beam]
+        rank = {e[0]: j for j, e in enumerate(beam)}
+        tot = [lse(pb, pnb) for _, pb, pnb, _ in beam]
         stay_pb = [tot[i] + row[blank] for i in range(live)]
         stay_pnb = [beam[i][2] + row[beam[i][0][-1]] if beam[i][0] else _NEG for i in range(live)]
         table = np.empty((live, C))
-        for i, (p, pb, _) in enumerate(beam):
+        for i, (p, pb, _, x) in enumerate(beam):
             table[i, 1:] = tot[i] + row[classes]
             if p:
                 table[i, column[p[-1]]] = pb + row[p[-1]]                          # a repeat of the last token needs a blank between
             if edges is not None:                                                   # a slot without an edge does not exist
                 gone = np.ones(C, dtype=bool)
-                gone[[column[c] for c in edges(dfa[i])]] = False
+                gone[[column[c] for c in edges(x)]] = False
                 gone[0] = False
                 table[i, gone] = _NEG
-        for j, (p, _, _) in enumerate(beam):                                        # an extension that is entry j: fold it into j
+        for j, (p, _, _, _) in enumerate(beam):                                     # an extension that is entry j: fold it into j
             i = rank.get(p[:-1]) if p else None
             if i is not None:
                 stay_pnb[j] = lse(stay_pnb[j], float(table[i, column[p[-1]]]))
@@ -139,7 +142,7 @@ def decode_sample(lp, K, blank=0, lm_table=None, lm_context=0, automaton=None):
         if fused:                                                                   # ranking = CTC term + lm', lm' formed first
             lm2 = np.empty((live, C))
             with np.errstate(invalid="ignore"):
-                for i, (lm, ctx) in enumerate(state):
+                for i, (_, _, _, (lm, ctx)) in enumerate(beam):
                     lm2[i, 0] = lm
                     lm2[i, 1:] = lm + W[ctx, classes]
                 flat = (table + lm2).ravel()
@@ -147,29 +150,27 @@ def decode_sample(lp, K, blank=0, lm_table=None, lm_context=0, automaton=None):
             flat = table.ravel()
         flat[np.isnan(flat)] = _NEG
         order = np.argsort(-flat, kind="stable")[:K]
-        nxt, nstate, ndfa = [], [], []
+        nxt = []
         for idx in order.tolist():
             if flat[idx] == _NEG:
                 break
             i, s = divmod(idx, C)
-            if edges is not None:                                                   # a stay keeps its state, an extension takes the edge
-                ndfa.append(dfa[i] if s == 0 else edges(dfa[i])[int(classes[s - 1])])
-            if s == 0:
-                nxt.append((beam[i][0], stay_pb[i], stay_pnb[i]))
-            else:
-                nxt.append((beam[i][0] + (int(classes[s - 1]),), _NEG, float(table[i, s])))
+            p, _, _, x = beam[i]
+            if s == 0:                                                              # a stay keeps the mode's part as it is
+                nxt.append((p, stay_pb[i], stay_pnb[i], x))
+                continue
+            c = int(classes[s - 1])
             if fused:
-                nstate.append((float(lm2[i, s]), state[i][1] if s == 0 else (state[i][1] * C + int(classes[s - 1])) % mod))
+                x = (float(lm2[i, s]), (x[1] * C + c) % mod)
+            elif edges is not None:                                                 # an extension takes the edge
+                x = edges(x)[c]
+            nxt.append((p + (c,), _NEG, float(table[i, s]), x))
         beam = nxt
-        if fused:
-            state = nstate
-        if edges is not None:
-            dfa = ndfa
-    if edges is not None:
-        return [(p, lse(pb, pnb), st) for (p, pb, pnb), st in zip(beam, dfa)]
-    if fused:
-        return [(p, lse(pb, pnb), lse(pb, pnb) + lm) for (p, pb, pnb), (lm, _) in zip(beam, state)]
-    return [(p, lse(pb, pnb)) for p, pb, pnb in beam]
+    out = []
+    for p, pb, pnb, x in beam:
+        score = lse(pb, pnb)
+        out.append((p, score) + (() if x is None else (score + x[0],) if fused else (x,)))
+    return out
 
 
 def ctc_beam_decode(scores, K, blank=0, lm_table=None, lm_context=0, automaton=None):
@@ -181,45 +182,29 @@ def ctc_beam_decode(scores, K, blank=0, lm_table=None, lm_context=0, automaton=N
     constrained search, in the layout of qea.ops.ctc_beam_decode_dfa, (tokens, lengths, scores, states int32 [N,K], -1 beyond the
     live count)."""
     T, N, C = scores.shape
-    check_limits(T, C, int(K), int(blank))
+    K, blank, lm_context = int(K), int(blank), int(lm_context)
+    check_limits(T, C, K, blank)
+    _refuse_both(lm_table, automaton)
+    fourth = None                                                                   # the mode's column behind the scores
     if automaton is not None:
-        from ._lib import QeaError
-        if lm_table is not None:
-            raise QeaError("ctc_beam_decode: an automaton together with an lm_table is not supported")
-        edges = automaton_edges(automaton, C, int(blank))
-        lp = scores.detach().to("cpu", torch.float32).numpy()
-        tokens = np.full((N, K, T), -1, dtype=np.int32)
-        lengths = np.full((N, K), -1, dtype=np.int32)
-        out = np.full((N, K), _NEG, dtype=np.float64)
-        states = np.full((N, K), -1, dtype=np.int32)
-        for n in range(N):
-            for k, (p, s, st) in enumerate(decode_sample(lp[:, n, :], int(K), int(blank), automaton=edges)):
-                tokens[n, k, :len(p)] = p
-                lengths[n, k], out[n, k], states[n, k] = len(p), s, st
-        return torch.from_numpy(tokens), torch.from_numpy(lengths), torch.from_numpy(out), torch.from_numpy(states)
-    fused = lm_table is not None
-    if fused:
-        lm_context = int(lm_context)
+        automaton = automaton_edges(automaton, C, blank)
+        fourth = np.full((N, K), -1, dtype=np.int32)
+    if lm_table is not None:
         check_lm_limits(C, lm_context, tuple(lm_table.shape))
         if torch.is_tensor(lm_table):
             lm_table = lm_table.detach().to("cpu", torch.float64).numpy()
         lm_table = np.asarray(lm_table, dtype=np.float64)
+        fourth = np.full((N, K), _NEG, dtype=np.float64)
     elif lm_context:
-        from ._lib import QeaError
         raise QeaError("ctc_beam_decode: lm_context without an lm_table")
     lp = scores.detach().to("cpu", torch.float32).numpy()
     tokens = np.full((N, K, T), -1, dtype=np.int32)
     lengths = np.full((N, K), -1, dtype=np.int32)
     out = np.full((N, K), _NEG, dtype=np.float64)
-    total = np.full((N, K), _NEG, dtype=np.float64)
     for n in range(N):
-        for k, entry in enumerate(decode_sample(lp[:, n, :], int(K), int(blank), lm_table, lm_context)):
-            p = entry[0]
+        for k, (p, s, *x) in enumerate(decode_sample(lp[:, n, :], K, blank, lm_table, lm_context, automaton)):
             tokens[n, k, :len(p)] = p
-            lengths[n, k] = len(p)
-            out[n, k] = entry[1]
-            if fused:
-                total[n, k] = entry[2]
-    if fused:
-        return torch.from_numpy(tokens), torch.from_numpy(lengths), torch.from_numpy(out), torch.from_numpy(total)
-    return torch.from_numpy(tokens), torch.from_numpy(lengths), torch.from_numpy(out)
+            lengths[n, k], out[n, k] = len(p), s
+            if x:
+                fourth[n, k] = x[0]
+    return tuple(torch.from_numpy(a) for a in (tokens, lengths, out, fourth) if a is not None)

@@ -9,7 +9,7 @@ import weakref
 
 import torch
 
-from . import _lib
+from . import _lib, beam
 
 OUT_NHWC, OUT_TBC, OUT_CONVT = 0, 1, 2
 PROF_CONV_IGEMM, PROF_CONV_WGRAD, PROF_LSTM_STEP = 0, 1, 2
@@ -869,57 +869,53 @@ def greedy_decode(scores, ld_t, ld_n, T, N, C_, blank, tokens, lengths):
                "qea_greedy_decode")
 
 
+def _beam_search(name, scores, K, blank, mode=None, extra=None):
+    """The one launch path of the three prefix beam searches.  name = the library function; its signature is the plain one with the
+    mode's arguments between K and tokens and the mode's output column behind the scores.  Validates scores, then calls mode() (the
+    wrapper's own checks; it returns the mode's arguments), allocates tokens / lengths / scores and one [N, rows] column of dtype
+    `extra` where the mode has one, launches, and returns the outputs.  Nothing is launched before every check has passed."""
+    who = name[len("qea_"):]
+    if scores.dim() != 3 or not scores.is_cuda or scores.dtype != torch.float32:
+        raise _lib.QeaError(f"{who} needs a CUDA float32 tensor [T,N,C] (there is no CPU path here: qea.beam has one)")
+    if scores.stride(2) != 1:
+        raise _lib.QeaError(f"{who} needs a unit class stride: make the last dimension contiguous")
+    if not (0 <= scores.stride(0) < 2 ** 31 and 0 <= scores.stride(1) < 2 ** 31):
+        raise _lib.QeaError(f"{who}: the T and N strides must fit 32 bits")
+    T, N, C_ = scores.shape
+    K = int(K)
+    args = mode() if mode else ()
+    rows = max(K, 1)
+    out = [torch.empty(N, rows, T, dtype=torch.int32, device=scores.device), torch.empty(N, rows, dtype=torch.int32, device=scores.device),
+           torch.empty(N, rows, dtype=torch.float64, device=scores.device)]
+    if extra is not None:
+        out.append(torch.empty(N, rows, dtype=extra, device=scores.device))
+    _lib.check(getattr(_lib.lib(), name)(_ptr(scores), scores.stride(0), scores.stride(1), T, N, C_, int(blank), K, *args,
+                                         *[_ptr(t) for t in out], _stream()), name)
+    return tuple(out)
+
+
 def ctc_beam_decode(scores, K, blank=0):
     """CTC prefix beam search (include/qea_hip.h: qea_ctc_beam_decode) of scores [T,N,C] (CUDA, float32, any T / N strides, unit class
     stride) -> (tokens int32 [N,K,T] with -1 behind every prefix, lengths int32 [N,K], scores float64 [N,K]), best first, on the
     device and without a synchronisation.  Raises QeaError for K outside 1..32, C outside 2..256, T outside 1..512, blank outside
     0..C-1."""
-    if scores.dim() != 3 or not scores.is_cuda or scores.dtype != torch.float32:
-        raise _lib.QeaError("ctc_beam_decode needs a CUDA float32 tensor [T,N,C] (there is no CPU path here: qea.beam has one)")
-    if scores.stride(2) != 1:
-        raise _lib.QeaError("ctc_beam_decode needs a unit class stride: make the last dimension contiguous")
-    if not (0 <= scores.stride(0) < 2 ** 31 and 0 <= scores.stride(1) < 2 ** 31):
-        raise _lib.QeaError("ctc_beam_decode: the T and N strides must fit 32 bits")
-    T, N, C_ = scores.shape
-    K = int(K)
-    rows = max(K, 1)
-    tokens = torch.empty(N, rows, T, dtype=torch.int32, device=scores.device)
-    lengths = torch.empty(N, rows, dtype=torch.int32, device=scores.device)
-    out = torch.empty(N, rows, dtype=torch.float64, device=scores.device)
-    _lib.check(_lib.lib().qea_ctc_beam_decode(_ptr(scores), scores.stride(0), scores.stride(1), T, N, C_, int(blank), K, _ptr(tokens),
-                                              _ptr(lengths), _ptr(out), _stream()), "qea_ctc_beam_decode")
-    return tokens, lengths, out
+    return _beam_search("qea_ctc_beam_decode", scores, K, blank)
 
 
 def ctc_beam_decode_lm(scores, K, table, context, blank=0):
     """The prefix beam search with a character n-gram prior fused in (include/qea_hip.h: qea_ctc_beam_decode_lm): scores as for
     ctc_beam_decode, table = the fused W [C ** context, C] (CUDA, float64, contiguous; qea.lm.CharLM.fused), context 0..2 ->
     (tokens int32 [N,K,T], lengths int32 [N,K], ctc float64 [N,K], total float64 [N,K]), best first by total, on the device and
-    without a synchronisation.  Raises QeaError for what ctc_beam_decode refuses, context outside 0..2, C ** (context + 1) > 2 ** 21
-    and a table of another device, dtype, layout or shape."""
-    if scores.dim() != 3 or not scores.is_cuda or scores.dtype != torch.float32:
-        raise _lib.QeaError("ctc_beam_decode_lm needs a CUDA float32 tensor [T,N,C] (there is no CPU path here: qea.beam has one)")
-    if scores.stride(2) != 1:
-        raise _lib.QeaError("ctc_beam_decode_lm needs a unit class stride: make the last dimension contiguous")
-    if not (0 <= scores.stride(0) < 2 ** 31 and 0 <= scores.stride(1) < 2 ** 31):
-        raise _lib.QeaError("ctc_beam_decode_lm: the T and N strides must fit 32 bits")
-    T, N, C_ = scores.shape
-    K, context = int(K), int(context)
-    if not 0 <= context <= 2:
-        raise _lib.QeaError(f"ctc_beam_decode_lm: context={context} outside 0..2")
-    if C_ ** (context + 1) > 2 ** 21:
-        raise _lib.QeaError(f"ctc_beam_decode_lm: a table of C^(m+1) = {C_ ** (context + 1)} entries, more than {2 ** 21}")
-    if not (torch.is_tensor(table) and table.is_cuda and table.device == scores.device and table.dtype == torch.float64
-            and table.is_contiguous() and tuple(table.shape) == (C_ ** context, C_)):
-        raise _lib.QeaError(f"ctc_beam_decode_lm needs a contiguous CUDA float64 table [C**context, C] = {(C_ ** context, C_)} on the scores' device")
-    rows = max(K, 1)
-    tokens = torch.empty(N, rows, T, dtype=torch.int32, device=scores.device)
-    lengths = torch.empty(N, rows, dtype=torch.int32, device=scores.device)
-    ctc = torch.empty(N, rows, dtype=torch.float64, device=scores.device)
-    total = torch.empty(N, rows, dtype=torch.float64, device=scores.device)
-    _lib.check(_lib.lib().qea_ctc_beam_decode_lm(_ptr(scores), scores.stride(0), scores.stride(1), T, N, C_, int(blank), K, _ptr(table), context,
-                                                 _ptr(tokens), _ptr(lengths), _ptr(ctc), _ptr(total), _stream()), "qea_ctc_beam_decode_lm")
-    return tokens, lengths, ctc, total
+    without a synchronisation.  Raises QeaError for what ctc_beam_decode refuses, what qea.beam.check_lm_limits refuses (context outside
+    0..MAX_LM_CONTEXT, C ** (context + 1) > MAX_LM_ENTRIES) and a table of another device, dtype, layout or shape."""
+    def mode():
+        C_, m = scores.shape[2], int(context)
+        beam.check_lm_limits(C_, m)
+        if not (torch.is_tensor(table) and table.is_cuda and table.device == scores.device and table.dtype == torch.float64
+                and table.is_contiguous() and tuple(table.shape) == (C_ ** m, C_)):
+            raise _lib.QeaError(f"ctc_beam_decode_lm needs a contiguous CUDA float64 table [C**context, C] = {(C_ ** m, C_)} on the scores' device")
+        return _ptr(table), m
+    return _beam_search("qea_ctc_beam_decode_lm", scores, K, blank, mode, torch.float64)
 
 
 def ctc_beam_decode_dfa(scores, K, automaton, blank=0):
@@ -929,31 +925,18 @@ def ctc_beam_decode_dfa(scores, K, automaton, blank=0):
     first, on the device and without a synchronisation.  The whole last beam is returned: automaton.final[state] says which ranks
     are accepted.  Raises QeaError for what ctc_beam_decode refuses, anything but a DeviceAutomaton, and one of another device, class
     count or blank."""
-    from .lexicon import DeviceAutomaton
-    if scores.dim() != 3 or not scores.is_cuda or scores.dtype != torch.float32:
-        raise _lib.QeaError("ctc_beam_decode_dfa needs a CUDA float32 tensor [T,N,C] (there is no CPU path here: qea.beam has one)")
-    if scores.stride(2) != 1:
-        raise _lib.QeaError("ctc_beam_decode_dfa needs a unit class stride: make the last dimension contiguous")
-    if not (0 <= scores.stride(0) < 2 ** 31 and 0 <= scores.stride(1) < 2 ** 31):
-        raise _lib.QeaError("ctc_beam_decode_dfa: the T and N strides must fit 32 bits")
-    if not isinstance(automaton, DeviceAutomaton):
-        raise _lib.QeaError("ctc_beam_decode_dfa takes the object Lexicon.device() returns: the tables it holds are validated")
-    T, N, C_ = scores.shape
-    K, blank = int(K), int(blank)
-    if automaton.device != scores.device:
-        raise _lib.QeaError(f"ctc_beam_decode_dfa: the automaton is on {automaton.device}, the scores on {scores.device}")
-    if automaton.num_classes != C_ or automaton.blank != blank:
-        raise _lib.QeaError(f"ctc_beam_decode_dfa: the automaton has {automaton.num_classes} classes and blank {automaton.blank}, "
-                            f"the scores {C_} and {blank}")
-    rows = max(K, 1)
-    tokens = torch.empty(N, rows, T, dtype=torch.int32, device=scores.device)
-    lengths = torch.empty(N, rows, dtype=torch.int32, device=scores.device)
-    out = torch.empty(N, rows, dtype=torch.float64, device=scores.device)
-    states = torch.empty(N, rows, dtype=torch.int32, device=scores.device)
-    _lib.check(_lib.lib().qea_ctc_beam_decode_dfa(_ptr(scores), scores.stride(0), scores.stride(1), T, N, C_, blank, K, _ptr(automaton.first),
-                                                  _ptr(automaton.label), _ptr(automaton.child), automaton.num_states, automaton.num_edges,
-                                                  _ptr(tokens), _ptr(lengths), _ptr(out), _ptr(states), _stream()), "qea_ctc_beam_decode_dfa")
-    return tokens, lengths, out, states
+    def mode():
+        from .lexicon import DeviceAutomaton
+        a = automaton
+        if not isinstance(a, DeviceAutomaton):
+            raise _lib.QeaError("ctc_beam_decode_dfa takes the object Lexicon.device() returns: the tables it holds are validated")
+        if a.device != scores.device:
+            raise _lib.QeaError(f"ctc_beam_decode_dfa: the automaton is on {a.device}, the scores on {scores.device}")
+        if a.num_classes != scores.shape[2] or a.blank != int(blank):
+            raise _lib.QeaError(f"ctc_beam_decode_dfa: the automaton has {a.num_classes} classes and blank {a.blank}, "
+                                f"the scores {scores.shape[2]} and {int(blank)}")
+        return _ptr(a.first), _ptr(a.label), _ptr(a.child), a.num_states, a.num_edges
+    return _beam_search("qea_ctc_beam_decode_dfa", scores, K, blank, mode, torch.int32)
 
 
 def prof_read_launches(klass, capacity=4096):

@@ -31,21 +31,32 @@ def get_char_maps(vocabulary=None):
 
 
 # ----------------------------------------------------------------------------- decode / CER
-def beam_decode(scores, beam, blank=0):
-    """[new] CTC prefix beam search of scores [T,B,C] with `beam` entries per sample -> (tokens int32 [B,K,T], lengths int32 [B,K],
-    log-probabilities float64 [B,K]), best first.  CUDA tensors: one launch (qea.ops.ctc_beam_decode), results stay on the device;
-    CPU tensors, or QEA_BEAM=host: the same specification as a host loop (qea/beam.py)."""
+def _beam_search(who, scores, beam, blank, model, on_device, on_host):
+    """The one path of beam_decode / beam_decode_lm / beam_decode_lexicon.  model: None, or the CharLM / Lexicon whose class count
+    and blank must be the scores'.  CUDA scores (and not QEA_BEAM=host): on_device(ops, float32 scores with a unit class stride),
+    results stay on the device; otherwise on_host(qea.beam, scores), moved to the scores' device."""
     from qea import beam as host_beam
     s = scores.detach()
+    if model is not None and (model.num_classes != s.shape[2] or model.blank != blank):
+        from qea._lib import QeaError
+        raise QeaError(f"{who}: the {type(model).__name__} has {model.num_classes} classes and blank {model.blank}, the scores "
+                       f"{s.shape[2]} and {blank}")
     if s.is_cuda and not host_beam.use_host():
         from qea import ops
         if s.dtype != torch.float32:
             s = s.float()
         if s.stride(2) != 1:
             s = s.contiguous()
-        return ops.ctc_beam_decode(s, beam, blank)
-    tokens, lengths, logp = host_beam.ctc_beam_decode(s, beam, blank)
-    return tokens.to(s.device), lengths.to(s.device), logp.to(s.device)
+        return on_device(ops, s)
+    return tuple(v.to(s.device) for v in on_host(host_beam, s))
+
+
+def beam_decode(scores, beam, blank=0):
+    """[new] CTC prefix beam search of scores [T,B,C] with `beam` entries per sample -> (tokens int32 [B,K,T], lengths int32 [B,K],
+    log-probabilities float64 [B,K]), best first.  CUDA tensors: one launch (qea.ops.ctc_beam_decode), results stay on the device;
+    CPU tensors, or QEA_BEAM=host: the same specification as a host loop (qea/beam.py)."""
+    return _beam_search("beam_decode", scores, beam, blank, None, lambda ops, s: ops.ctc_beam_decode(s, beam, blank),
+                        lambda host, s: host.ctc_beam_decode(s, beam, blank))
 
 
 def beam_decode_lm(scores, beam, lm, alpha=1.0, beta=0.0, blank=0):
@@ -53,19 +64,9 @@ def beam_decode_lm(scores, beam, lm, alpha=1.0, beta=0.0, blank=0):
     log-probability plus alpha * log P(c | context) + beta per character -> (tokens int32 [B,K,T], lengths int32 [B,K],
     ctc float64 [B,K], total float64 [B,K]), best first by total.  CUDA tensors: one launch (qea.ops.ctc_beam_decode_lm); CPU
     tensors, or QEA_BEAM=host: the same specification as a host loop (qea/beam.py)."""
-    from qea import beam as host_beam
-    from qea._lib import QeaError
-    s = scores.detach()
-    if lm.num_classes != s.shape[2] or lm.blank != blank:
-        raise QeaError(f"beam_decode_lm: the model has {lm.num_classes} classes and blank {lm.blank}, the scores {s.shape[2]} and {blank}")
-    if s.is_cuda and not host_beam.use_host():
-        from qea import ops
-        if s.dtype != torch.float32:
-            s = s.float()
-        if s.stride(2) != 1:
-            s = s.contiguous()
-        return ops.ctc_beam_decode_lm(s, beam, lm.fused(alpha, beta, s.device), lm.context, blank)
-    return tuple(v.to(s.device) for v in host_beam.ctc_beam_decode(s, beam, blank, lm.fused(alpha, beta, "cpu"), lm.context))
+    return _beam_search("beam_decode_lm", scores, beam, blank, lm,
+                        lambda ops, s: ops.ctc_beam_decode_lm(s, beam, lm.fused(alpha, beta, s.device), lm.context, blank),
+                        lambda host, s: host.ctc_beam_decode(s, beam, blank, lm.fused(alpha, beta, "cpu"), lm.context))
 
 
 def beam_decode_lexicon(scores, beam, lexicon, blank=0):
@@ -74,24 +75,11 @@ def beam_decode_lexicon(scores, beam, lexicon, blank=0):
     [B,K], log-probabilities float64 [B,K], accepted bool [B,K]), the whole last beam, best first; accepted marks the ranks that end
     in an accepting state (whole words).  The scores are CTC log-likelihoods, as in beam_decode.  CUDA tensors: one launch
     (qea.ops.ctc_beam_decode_dfa) on tables uploaded once, no synchronisation; CPU tensors, or QEA_BEAM=host: the host loop."""
-    from qea import beam as host_beam
-    from qea._lib import QeaError
-    s = scores.detach()
-    if lexicon.num_classes != s.shape[2] or lexicon.blank != blank:
-        raise QeaError(f"beam_decode_lexicon: the lexicon has {lexicon.num_classes} classes and blank {lexicon.blank}, the scores "
-                       f"{s.shape[2]} and {blank}")
-    if s.is_cuda and not host_beam.use_host():
-        from qea import ops
-        if s.dtype != torch.float32:
-            s = s.float()
-        if s.stride(2) != 1:
-            s = s.contiguous()
-        automaton = lexicon.device(s.device)
-        tokens, lengths, logp, states = ops.ctc_beam_decode_dfa(s, beam, automaton, blank)
-        final = automaton.final
-    else:
-        tokens, lengths, logp, states = (v.to(s.device) for v in host_beam.ctc_beam_decode(s, beam, blank, automaton=lexicon))
-        final = lexicon.device(s.device).final
+    tokens, lengths, logp, states = _beam_search(
+        "beam_decode_lexicon", scores, beam, blank, lexicon,
+        lambda ops, s: ops.ctc_beam_decode_dfa(s, beam, lexicon.device(s.device), blank),
+        lambda host, s: host.ctc_beam_decode(s, beam, blank, automaton=lexicon))
+    final = lexicon.device(states.device).final
     accepted = (states >= 0) & (final[states.clamp(min=0).long()] != 0)
     return tokens, lengths, logp, accepted
 
@@ -119,16 +107,30 @@ def lexicon_best(scores, beam, lexicon, blank=0, nbest=1):
     return tokens, lengths, logp, miss
 
 
-def _beam_to_string(scores, labels, index_to_char, show_text, beam, nbest, return_scores, lm=None, lm_weight=1.0, lm_bonus=0.0, lexicon=None):
+def _check_beam_arguments(who, beam, lm, lexicon):
+    """The rules of the beam= / lm= / lexicon= arguments of pred_to_string and batch_cers."""
     from qea._lib import QeaError
-    if not 1 <= nbest <= beam:
-        raise QeaError(f"pred_to_string: nbest={nbest} outside 1..beam={beam}")
+    if lm is not None and not beam:
+        raise QeaError(f"{who}: lm needs beam=K > 0 (the greedy decode has no search to fuse a prior into)")
+    if lexicon is not None and (lm is not None or not beam):
+        raise QeaError(f"{who}: lexicon needs beam=K > 0 and cannot be combined with lm")
+
+
+def _beam_readings(scores, beam, blank, nbest, lm, lm_weight, lm_bonus, lexicon):
+    """(tokens, lengths, log-scores) of the readings of the search that (lm, lexicon) choose; at least nbest ranks per strip."""
     if lexicon is not None:
-        tokens, lengths, logp, _ = lexicon_best(scores, beam, lexicon, 0, nbest)
-    elif lm is None:
-        tokens, lengths, logp = beam_decode(scores, beam, 0)
-    else:                                                              # the scores returned are the totals: what decided the order
-        tokens, lengths, _, logp = beam_decode_lm(scores, beam, lm, lm_weight, lm_bonus, 0)
+        return lexicon_best(scores, beam, lexicon, blank, nbest)[:3]
+    if lm is None:
+        return beam_decode(scores, beam, blank)
+    tokens, lengths, _, total = beam_decode_lm(scores, beam, lm, lm_weight, lm_bonus, blank)
+    return tokens, lengths, total                                      # the totals: what decided the order
+
+
+def _beam_to_string(scores, labels, index_to_char, show_text, beam, nbest, return_scores, lm=None, lm_weight=1.0, lm_bonus=0.0, lexicon=None):
+    if not 1 <= nbest <= beam:
+        from qea._lib import QeaError
+        raise QeaError(f"pred_to_string: nbest={nbest} outside 1..beam={beam}")
+    tokens, lengths, logp = _beam_readings(scores, beam, 0, nbest, lm, lm_weight, lm_bonus, lexicon)
     tk, ln, lp = tokens.cpu().tolist(), lengths.cpu().tolist(), logp.cpu().tolist()
     B = len(tk)
     # a rank beyond the live count (length -1, score -inf: fewer than `beam` labellings have a non-zero probability) reads ""
@@ -154,12 +156,7 @@ def pred_to_string(scores, labels, index_to_char, show_text=False, beam=0, nbest
     [new] lexicon=Lexicon (with beam=K, not with lm): the search stays inside that word list (beam_decode_lexicon) and the strings are
     its best-ranked entries that are whole words, with their CTC log-probabilities; a strip with no word among its K reads as the
     plain search of the same K (lexicon_best)."""
-    if lm is not None and not beam:
-        from qea._lib import QeaError
-        raise QeaError("pred_to_string: lm needs beam=K > 0 (the greedy decode has no search to fuse a prior into)")
-    if lexicon is not None and (lm is not None or not beam):
-        from qea._lib import QeaError
-        raise QeaError("pred_to_string: lexicon needs beam=K > 0 and cannot be combined with lm")
+    _check_beam_arguments("pred_to_string", beam, lm, lexicon)
     if beam:
         return _beam_to_string(scores, labels, index_to_char, show_text, int(beam), int(nbest), return_scores, lm, lm_weight, lm_bonus, lexicon)
     if nbest != 1 or return_scores:
@@ -223,26 +220,18 @@ def batch_cers(scores, labels, char_to_index, blank=0, beam=0, lm=None, lm_weigh
     search with that model fused in (rank 0 of beam_decode_lm); with lexicon=Lexicon (not with lm), of the best-ranked whole word of
     the search inside that word list, and of the plain search's rank 0 where a strip has none (lexicon_best)."""
     from qea import ops
-    if lm is not None and not beam:
-        from qea._lib import QeaError
-        raise QeaError("batch_cers: lm needs beam=K > 0")
-    if lexicon is not None and (lm is not None or not beam):
-        from qea._lib import QeaError
-        raise QeaError("batch_cers: lexicon needs beam=K > 0 and cannot be combined with lm")
+    _check_beam_arguments("batch_cers", beam, lm, lexicon)
     T, B, C = scores.shape
     s = scores.detach()
-    if s.stride(2) != 1:
-        s = s.contiguous()
     dev = s.device
     if beam:
-        if lexicon is not None:
-            btok, blen = lexicon_best(s, int(beam), lexicon, blank)[:2]
-        else:
-            btok, blen = (beam_decode(s, int(beam), blank) if lm is None else beam_decode_lm(s, int(beam), lm, lm_weight, lm_bonus, blank))[:2]
+        btok, blen, _ = _beam_readings(s, int(beam), blank, 1, lm, lm_weight, lm_bonus, lexicon)
         # the edit-distance kernel takes rows of at most 128 tokens: rank 0 as a [B][T] slice of its own, not a K * T stride
         # (length -1 = no labelling with a non-zero probability at all: scored as the empty string)
         tokens, plen = btok[:, 0, :].contiguous(), blen[:, 0].clamp(min=0).contiguous()
     else:
+        if s.stride(2) != 1:
+            s = s.contiguous()
         tokens = torch.empty(B, T, dtype=torch.int32, device=dev)
         plen = torch.empty(B, dtype=torch.int32, device=dev)
         ops.greedy_decode(s, s.stride(0), s.stride(1), T, B, C, blank, tokens, plen)

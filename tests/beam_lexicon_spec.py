@@ -75,14 +75,7 @@ def decode(lp, K, aut, blank=0):
 
 def decode_batch(scores, K, aut, blank=0):
     """scores: a [T,N,C] float32 tensor -> ([beam of sample n], the smallest gap of all samples)."""
-    T, N, C = scores.shape
-    lp = scores.detach().cpu().float().permute(1, 0, 2).tolist()
-    out, gap = [], math.inf
-    for n in range(N):
-        b, g = decode(lp[n], K, aut, blank)
-        out.append(b)
-        gap = min(gap, g)
-    return out, gap
+    return beam_spec.decode_batch(scores, K, aut, blank, search=decode)
 
 
 def as_arrays(beams, K, T):

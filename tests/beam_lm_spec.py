@@ -67,15 +67,7 @@ def decode(lp, K, W, m, blank=0):
 
 def decode_batch(scores, K, W, m, blank=0):
     """scores: a [T,N,C] float32 tensor, W: a [C**m, C] fp64 tensor or nested list -> ([beam of sample n], the smallest gap)."""
-    T, N, C = scores.shape
-    lp = scores.detach().cpu().float().permute(1, 0, 2).tolist()
-    W = W.tolist() if torch.is_tensor(W) else W
-    out, gap = [], math.inf
-    for n in range(N):
-        b, g = decode(lp[n], K, W, m, blank)
-        out.append(b)
-        gap = min(gap, g)
-    return out, gap
+    return beam_spec.decode_batch(scores, K, W.tolist() if torch.is_tensor(W) else W, m, blank, search=decode)
 
 
 def as_arrays(beams, K, T):

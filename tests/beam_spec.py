@@ -67,16 +67,12 @@ def decode(lp, K, blank=0):
     return [(p, lse(pb, pnb)) for p, pb, pnb in beam], gap
 
 
-def decode_batch(scores, K, blank=0):
-    """scores: a [T,N,C] float32 tensor -> ([beam of sample n], the smallest gap of all samples)."""
-    T, N, C = scores.shape
+def decode_batch(scores, K, *args, search=None, **kwargs):
+    """scores: a [T,N,C] float32 tensor -> ([beam of sample n], the smallest gap of all samples).  search: the per-sample decode, this
+    module's unless beam_lm_spec or beam_lexicon_spec hands in its own; args, kwargs: what that one takes behind K."""
     lp = scores.detach().cpu().float().permute(1, 0, 2).tolist()
-    out, gap = [], math.inf
-    for n in range(N):
-        b, g = decode(lp[n], K, blank)
-        out.append(b)
-        gap = min(gap, g)
-    return out, gap
+    found = [(search or decode)(rows, K, *args, **kwargs) for rows in lp]
+    return [b for b, _ in found], min((g for _, g in found), default=math.inf)
 
 
 def as_arrays(beams, K, T):

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 import beam_spec
 import helpers as H
+from beam_checks import same_scores as _same_scores
 
 
 _log_probs, _ctc_log_likelihood = beam_spec.log_probs, beam_spec.ctc_log_likelihood
@@ -41,10 +42,7 @@ def test_host_loop_equals_the_spec(T, C, K):
     assert tokens.shape == (N, K, T) and tokens.dtype == torch.int32 and lengths.shape == (N, K) and lengths.dtype == torch.int32
     assert scores.shape == (N, K) and scores.dtype == torch.float64
     wt, wl, ws = beam_spec.as_arrays(want, K, T)
-    assert tokens.tolist() == wt and lengths.tolist() == wl
-    for got_row, want_row in zip(scores.tolist(), ws):
-        for a, b in zip(got_row, want_row):
-            assert a == b or abs(a - b) <= 1e-12 * max(1.0, abs(b)), (a, b)
+    assert tokens.tolist() == wt and lengths.tolist() == wl and _same_scores(scores.tolist(), ws)
     if (T, C, K) == (5, 3, 32):
         assert (lengths == -1).any() and (scores[lengths == -1] == -math.inf).all()      # fewer labellings than K: padded rows
 
@@ -58,7 +56,7 @@ def test_host_loop_with_another_blank_and_with_minus_inf():
     tokens, lengths, scores = host.ctc_beam_decode(lp, 8, blank=3)
     wt, wl, ws = beam_spec.as_arrays(want, 8, 6)
     assert tokens.tolist() == wt and lengths.tolist() == wl and not torch.isnan(scores).any()
-    assert all(a == b or abs(a - b) <= 1e-12 * max(1.0, abs(b)) for r, w in zip(scores.tolist(), ws) for a, b in zip(r, w))
+    assert _same_scores(scores.tolist(), ws)
     assert all(1 not in p and 3 not in p for b in want for p, _ in b)
 
 

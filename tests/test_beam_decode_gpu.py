@@ -11,12 +11,13 @@ import math
 import pytest
 import torch
 
+import beam_checks
 import beam_spec
 import helpers as H
 
 pytestmark = pytest.mark.gpu
 
-MIN_GAP = 1e-7
+MIN_GAP = beam_checks.MIN_GAP
 
 
 @functools.lru_cache(maxsize=None)
@@ -35,23 +36,7 @@ def _case(T, N, C, K, seed, blank=0, variant=""):
 
 def _check_against_spec(dev_scores, K, blank, beams, gap):
     from qea import ops
-    T, N, C = dev_scores.shape
-    assert gap >= MIN_GAP, f"input too close to a tie for an exact comparison: gap {gap:.3e}"
-    tokens, lengths, scores = ops.ctc_beam_decode(dev_scores, K, blank)
-    assert tokens.shape == (N, K, T) and tokens.dtype == torch.int32 and lengths.shape == (N, K) and lengths.dtype == torch.int32
-    assert scores.shape == (N, K) and scores.dtype == torch.float64 and tokens.is_cuda
-    wt, wl, ws = beam_spec.as_arrays(beams, K, T)
-    tokens, lengths, scores = tokens.cpu(), lengths.cpu(), scores.cpu()
-    assert not torch.isnan(scores).any()
-    assert lengths.tolist() == wl
-    assert torch.equal(tokens, torch.tensor(wt, dtype=torch.int32))
-    want = torch.tensor(ws, dtype=torch.float64)
-    dead = lengths < 0
-    assert (scores[dead] == -math.inf).all() and (want[dead] == -math.inf).all()
-    err = (scores[~dead] - want[~dead]).abs() / want[~dead].abs().clamp(min=1.0)
-    print(f"max score error {err.max().item():.3e} (relative to max(1, |s|)), smallest gap {gap:.3e}")
-    assert err.max().item() <= 1e-9
-    return tokens, lengths, scores
+    return beam_checks.check_against_spec(ops.ctc_beam_decode(dev_scores, K, blank), beam_spec.as_arrays(beams, K, dev_scores.shape[0]), gap)
 
 
 # (T, N, C, K, seed): one sample; more samples than CUs; K = 1; each candidate-register variant (1, 4, 12, 32 per thread); the longest

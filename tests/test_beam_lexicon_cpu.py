@@ -11,15 +11,12 @@ import torch
 import beam_lexicon_spec as spec
 import beam_spec
 import helpers as H
+from beam_checks import same_scores as _same_scores
 
 
 def _host(lp, K, aut, blank=0):
     from qea import beam as host
     return host.ctc_beam_decode(lp, K, blank, automaton=aut)
-
-
-def _same_scores(got, want):
-    return all(a == b or abs(a - b) <= 1e-12 * max(1.0, abs(b)) for r, w in zip(got, want) for a, b in zip(r, w))
 
 
 def _vocab(C, blank=0):

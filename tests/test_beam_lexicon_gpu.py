@@ -12,13 +12,14 @@ import math
 import pytest
 import torch
 
+import beam_checks
 import beam_lexicon_spec as spec
 import beam_spec
 import helpers as H
 
 pytestmark = pytest.mark.gpu
 
-MIN_GAP = 1e-7
+MIN_GAP = beam_checks.MIN_GAP
 
 
 def _words(C, blank, n_words, max_len, seed, variant):
@@ -48,29 +49,13 @@ def _lexicon(aut, C, blank=0):
 
 
 def _compare(got, beams, K, T, gap):
-    assert gap >= MIN_GAP, f"input too close to a tie for an exact comparison: gap {gap:.3e}"
-    tokens, lengths, scores, states = (v.cpu() for v in got)
-    N = len(beams)
-    assert tokens.shape == (N, K, T) and tokens.dtype == torch.int32 and lengths.shape == states.shape == (N, K)
-    assert lengths.dtype == states.dtype == torch.int32 and scores.shape == (N, K) and scores.dtype == torch.float64
-    wt, wl, ws, wst = spec.as_arrays(beams, K, T)
-    assert not torch.isnan(scores).any()
-    assert lengths.tolist() == wl and states.tolist() == wst
-    assert torch.equal(tokens, torch.tensor(wt, dtype=torch.int32))
-    dead, want = lengths < 0, torch.tensor(ws, dtype=torch.float64)
-    assert (scores[dead] == -math.inf).all() and (want[dead] == -math.inf).all() and (states[dead] == -1).all()
-    err = (scores[~dead] - want[~dead]).abs() / want[~dead].abs().clamp(min=1.0)
-    print(f"max score error {err.max().item():.3e} (relative to max(1, |s|)), smallest gap {gap:.3e}")
-    assert err.max().item() <= 1e-9
-    return tokens, lengths, scores, states
+    return beam_checks.check_against_spec(got, spec.as_arrays(beams, K, T), gap, (("score", torch.float64), ("state", torch.int32)))
 
 
 def _check_against_spec(dev_scores, K, aut, blank, beams, gap):
     from qea import ops
     T, N, C = dev_scores.shape
-    got = ops.ctc_beam_decode_dfa(dev_scores, K, _lexicon(aut, C, blank).device("cuda"), blank)
-    assert all(v.is_cuda for v in got)
-    return _compare(got, beams, K, T, gap)
+    return _compare(ops.ctc_beam_decode_dfa(dev_scores, K, _lexicon(aut, C, blank).device("cuda"), blank), beams, K, T, gap)
 
 
 # (T, N, C, K, seed, n_words, max_len, variant): smallest everything; more samples than CUs; the workload's T and C (R = 4) with 500

@@ -10,15 +10,12 @@ import torch
 import beam_lm_spec
 import beam_spec
 import helpers as H
+from beam_checks import same_scores as _same_scores
 
 
 def _host(lp, K, W, m, blank=0):
     from qea import beam as host
     return host.ctc_beam_decode(lp, K, blank, W, m)
-
-
-def _same_scores(got, want):
-    return all(a == b or abs(a - b) <= 1e-12 * max(1.0, abs(b)) for r, w in zip(got, want) for a, b in zip(r, w))
 
 
 @pytest.mark.parametrize("m", [0, 1, 2])

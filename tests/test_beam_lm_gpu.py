@@ -11,13 +11,14 @@ import math
 import pytest
 import torch
 
+import beam_checks
 import beam_lm_spec
 import beam_spec
 import helpers as H
 
 pytestmark = pytest.mark.gpu
 
-MIN_GAP = 1e-7
+MIN_GAP = beam_checks.MIN_GAP
 
 
 @functools.lru_cache(maxsize=None)
@@ -33,23 +34,8 @@ def _case(T, N, C, K, m, seed, blank=0, variant=""):
 
 def _check_against_spec(dev_scores, K, W, m, blank, beams, gap):
     from qea import ops
-    T, N, C = dev_scores.shape
-    assert gap >= MIN_GAP, f"input too close to a tie for an exact comparison: gap {gap:.3e}"
-    tokens, lengths, ctc, total = ops.ctc_beam_decode_lm(dev_scores, K, W.cuda(), m, blank)
-    assert tokens.shape == (N, K, T) and tokens.dtype == torch.int32 and lengths.shape == (N, K) and lengths.dtype == torch.int32
-    assert ctc.shape == total.shape == (N, K) and ctc.dtype == total.dtype == torch.float64 and tokens.is_cuda and total.is_cuda
-    wt, wl, wc, wtot = beam_lm_spec.as_arrays(beams, K, T)
-    tokens, lengths, ctc, total = tokens.cpu(), lengths.cpu(), ctc.cpu(), total.cpu()
-    assert not torch.isnan(ctc).any() and not torch.isnan(total).any()
-    assert lengths.tolist() == wl
-    assert torch.equal(tokens, torch.tensor(wt, dtype=torch.int32))
-    dead = lengths < 0
-    for name, got, want in (("ctc", ctc, torch.tensor(wc, dtype=torch.float64)), ("total", total, torch.tensor(wtot, dtype=torch.float64))):
-        assert (got[dead] == -math.inf).all() and (want[dead] == -math.inf).all()
-        err = (got[~dead] - want[~dead]).abs() / want[~dead].abs().clamp(min=1.0)
-        print(f"max {name} error {err.max().item():.3e} (relative to max(1, |s|)), smallest gap {gap:.3e}")
-        assert err.max().item() <= 1e-9
-    return tokens, lengths, ctc, total
+    return beam_checks.check_against_spec(ops.ctc_beam_decode_lm(dev_scores, K, W.cuda(), m, blank), beam_lm_spec.as_arrays(beams, K, dev_scores.shape[0]),
+                                          gap, (("ctc", torch.float64), ("total", torch.float64)))
 
 
 # (T, N, C, K, m, seed): smallest everything; more samples than CUs and the trigram wrap of ctx; the workload's T and C (R = 4);
