@@ -731,6 +731,47 @@ int qea_page_tiles_scatter(const float* tiles, int32_t N, int32_t TH, int32_t TW
                            const int32_t* h, const int32_t* w, int32_t n_pages, int64_t store_elems, float* out_f32, uint8_t* out_u8,
                            void* stream);
 
+/* Classic binarisation baselines over the same page store (csrc/binarize.hip; qea/binarize.py: binarize_pages; the statement, which all
+ * three reproduce bit for bit, is tests/binarize_spec.py and DESIGN.md "Binarisation baselines").  store / store_elems / offset / h / w /
+ * n_pages are those of qea_page_tiles_*; an fp32 pixel is read as its 8-bit value (uint8)(min(max(x, 0), 1) * 255.0f), NaN as 0.  Ink is
+ * foreground: a foreground pixel is written as 0 / 0.0f, a background pixel as 255 / 1.0f, to out_u8 and / or out_f32 (either may be NULL,
+ * not both), which are packed like the store with the same offsets; what lies between the pages is never written.  host_h / host_w are
+ * the caller's HOST copies of h / w: the entry point validates the page sizes and sizes its grid from them, the kernels read the device
+ * tables.  The block-to-page map is a prefix table on the device, int32 [n_pages + 1] with first[0] = 0, uploaded with the page table:
+ *   tile_first[p + 1] - tile_first[p]   = ceil(h[p] / QEA_BINARIZE_TILE_H) * ceil(w[p] / QEA_BINARIZE_TILE_W)   (Sauvola)
+ *   chunk_first[p + 1] - chunk_first[p] = ceil(h[p] * w[p] / QEA_BINARIZE_CHUNK)                                 (Otsu)
+ * Device tables that disagree with the host copies leave pixels unwritten; they never cause an access outside the buffers.
+ * qea_binarize_sauvola — ONE launch for all pages.  Per pixel v, over the win x win window centred on it and clipped to the page (n pixels,
+ *   S1 = sum v, S2 = sum v^2, Q = n S2 - S1^2, all exact integers): A = double(n v) - double(S1) * (1.0 - k); foreground iff A <= 0 or
+ *   L * L <= (G * G) * double(Q) with L = A * (R * double(n)), G = k * double(S1): the textbook v <= m (1 + k (s / R - 1)) without sqrt or
+ *   division, every fp64 operation rounded as written.  win is odd in 3..QEA_BINARIZE_MAX_WINDOW, 0 < k < 1, R > 0 and finite.  LDS:
+ *   33.5 KiB at win = 25, 110.5 KiB at win = 127 (the largest is reserved once per process).
+ * qea_otsu_histogram — launch 1 of Otsu: zeroes hist (uint32 [n_pages][256], hipMemsetAsync on the stream) and counts every page's pixels
+ *   into its row with integer atomics (deterministic).
+ * qea_binarize_otsu — launch 2: every workgroup derives its page's t* from the 256 bins (N = sum hist, S = sum v hist[v]; for t = 0..254
+ *   ascending with w0 = sum hist[..t] > 0 and w1 = N - w0 > 0: d = s0 N - S w0 in int64, num = double(d)^2, den = double(w0) double(w1); t
+ *   replaces the best iff num * den_best > num_best * den, so ties keep the smaller t) and writes foreground iff v <= t*.  thresholds
+ *   (int32 [n_pages]) receives t*, or -1 for a page of a single grey level, which is all background.
+ * Nothing synchronises, no workspace.  Refused before any launch: a NULL pointer, a flag that is neither 0 nor 1, n_pages outside 1..2^24,
+ * store_elems < 1, an empty page, a page of more than QEA_BINARIZE_MAX_PAGE_PIXELS pixels (the bound that keeps 255 N^2 < 2^63), more
+ * than 2^31 - 1 workgroups, win even or outside its range, k or R outside their ranges or not finite, both outputs NULL, a misaligned
+ * fp32 store / out_f32 / hist / thresholds.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects these three by symbol.) */
+#define QEA_BINARIZE_TILE_H 32
+#define QEA_BINARIZE_TILE_W 64
+#define QEA_BINARIZE_CHUNK 32768
+#define QEA_BINARIZE_MAX_WINDOW 127
+#define QEA_BINARIZE_MAX_PAGE_PIXELS (1 << 27)
+int qea_binarize_sauvola(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h,
+                         const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first,
+                         int32_t win, double k, double R, float* out_f32, uint8_t* out_u8, void* stream);
+int qea_otsu_histogram(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h,
+                       const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* chunk_first,
+                       uint32_t* hist, void* stream);
+int qea_binarize_otsu(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h,
+                      const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* chunk_first,
+                      const uint32_t* hist, float* out_f32, uint8_t* out_u8, int32_t* thresholds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

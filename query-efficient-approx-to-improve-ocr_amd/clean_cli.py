@@ -1,18 +1,23 @@
 """[new] Clean a folder of scans with a trained preprocessor (flags: qea/cli_flags.py tag "n").
 
     python clean_cli.py --prep_path PREP --in_dir scans --out_dir cleaned [--tile H W] [--batch_pages N]
+    python clean_cli.py --method {otsu,sauvola} [--window W --k K] --in_dir scans --out_dir binarised [--batch_pages N]
 
 Every png / jpg / jpeg of --in_dir, in name order, is decoded to 8-bit grey, sent through the tiled eval-mode pass of qea/pages.py
 (clean_pages: pages of any size, --batch_pages of them per call so that tiles of different pages share UNet passes) and written to
 --out_dir as an 8-bit grey PNG of the same size and stem.  PIL does the file I/O only: the p / 255 normalisation, the tiling and the
 (uint8)(clamp(x, 0, 1) * 255) quantisation run on the device.  `backend` is the injection seam of the other drivers (the default is
 the HIP path; the oracle backend runs the same plan on the host).
+
+--method otsu / sauvola writes the classic baseline instead (qea/binarize.py: binarize_pages, one call per --batch_pages group): no
+checkpoint is loaded and --tile is ignored; same output names, sizes and 8-bit PNG format, ink 0 and background 255.
 """
 import os
 
 import numpy as np
 import torch
 
+from qea.binarize import binarize_pages, check_params
 from qea.pages import clean_pages
 from qea.trainer_core import hip_backend
 
@@ -25,7 +30,12 @@ class CleanPages:
         self.tile = tuple(args.tile)
         self.batch_pages = max(1, int(args.batch_pages))
         self.device = (backend or hip_backend()).device
-        self.prep_model = torch.load(args.prep_path, map_location=self.device, weights_only=False).to(self.device).eval()
+        self.method = getattr(args, "method", "unet")
+        if self.method == "unet":
+            self.prep_model = torch.load(args.prep_path, map_location=self.device, weights_only=False).to(self.device).eval()
+        else:
+            self.window, self.k = args.window, args.k
+            check_params(self.method, self.window, self.k)
         self.names = sorted(n for n in os.listdir(self.in_dir) if n.lower().endswith(EXTENSIONS))
         stems = [os.path.splitext(n)[0] for n in self.names]
         twice = sorted({s for s in stems if stems.count(s) > 1})
@@ -43,7 +53,10 @@ class CleanPages:
             for n in names:
                 with Image.open(os.path.join(self.in_dir, n)) as img:
                     pages.append(torch.from_numpy(np.array(img.convert("L"), dtype=np.uint8)))
-            cleaned = clean_pages(self.prep_model, pages, tile=self.tile, out="u8")
+            if self.method == "unet":
+                cleaned = clean_pages(self.prep_model, pages, tile=self.tile, out="u8")
+            else:
+                cleaned = binarize_pages(pages, self.method, window=self.window, k=self.k, out="u8", device=self.device)
             for n, page in zip(names, cleaned):
                 path = os.path.join(self.out_dir, os.path.splitext(n)[0] + ".png")
                 Image.fromarray(page.cpu().numpy()).save(path)

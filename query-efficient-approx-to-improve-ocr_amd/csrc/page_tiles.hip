@@ -18,29 +18,10 @@
 //
 // Both kernels skip a page that does not lie inside the store (offset < 0 or offset + h * w > store_elems): a bad table gives white
 // tiles / unwritten outputs, never an access outside the caller's buffers.
+#include "page_store.h"
 #include "window_gather.h"
 
 namespace {
-
-struct Page {
-  long long off;
-  int h, w;     // 0 x 0: no such page
-};
-
-__device__ __forceinline__ Page page_of(int p, const int64_t* __restrict__ offset, const int32_t* __restrict__ h, const int32_t* __restrict__ w,
-                                        int n_pages, long long store_elems) {
-  Page g = {0, 0, 0};
-  if (p >= 0 && p < n_pages) {
-    const long long off = offset[p];
-    const int ph = h[p], pw = w[p];
-    if (off >= 0 && ph > 0 && pw > 0 && off <= store_elems && (long long)ph * pw <= store_elems - off) {
-      g.off = off;
-      g.h = ph;
-      g.w = pw;
-    }
-  }
-  return g;
-}
 
 template <typename T>
 __global__ __launch_bounds__(WG_THREADS) void page_tiles_gather_kernel(const T* __restrict__ store, long long store_elems,
@@ -56,11 +37,6 @@ __global__ __launch_bounds__(WG_THREADS) void page_tiles_gather_kernel(const T* 
     const auto cut = [](int a, int o, int hi) { return o >= a ? 0 : (int)min((unsigned)a - (unsigned)o, (unsigned)hi); };
     return Window{g.off + (long long)oy * g.w + ox, g.w, cut(0, ox, TW), cut(0, oy, TH), cut(g.w, ox, TW), cut(g.h, oy, TH)};
   });
-}
-
-__device__ __forceinline__ uint8_t to_u8(float x) {
-  const float c = fminf(fmaxf(x, 0.f), 1.f);           // fmaxf(NaN, 0) = 0
-  return (uint8_t)(int)__fmul_rn(c, 255.0f);           // one fp32 multiply, then truncation
 }
 
 __global__ __launch_bounds__(WG_THREADS) void page_tiles_scatter_kernel(const float* __restrict__ tiles, int N, int TH, int TW,

@@ -16,6 +16,11 @@ Returns (accuracy, cer) of the cleaned strips, as the reference's patch flow doe
   * [new] --tile H W sends the images of both flows through the tiled whole-page pass (qea/pages.py: clean_pages) instead: a document
     of ANY size evaluates, as the eval-mode pass over the page padded with white to the next multiple of 16 and cropped back.  Without
     the flag nothing changes, the ValueError included.
+  * [new] --baseline {otsu,sauvola} [--baseline_window W --baseline_k K] also sends the same images through a classic binariser
+    (qea/binarize.py: binarize_pages) and the OCR engine, prints "Correct count from <method> images" / "Average CER from <method>
+    images" and sets self.baseline_result = (accuracy, cer).  Area flow: every strip of the batch is its own page.  Patch flow: the
+    document the model sees is binarised as a whole, then cut by get_text_stack, so window statistics come from the page, not from
+    the crop.  Return values and the other prints stay as they are.
   * [new] --synthetic_size N evaluates on N synthetic strips / documents (datasets/synthetic.py).
   * The loaders run in the main process (the reference asks for properties.num_workers workers).
 `backend` / `dataset` / `ocr` are injection seams for tests, as in the trainers; the default backend is the HIP path.
@@ -26,6 +31,7 @@ import torch
 
 import properties
 from qea._lib import QeaError
+from qea.binarize import binarize_pages, check_params
 from qea.pages import clean_pages
 from qea.trainer_core import hip_backend
 from utils import compare_labels, get_ocr_helper, get_text_stack, show_img
@@ -42,6 +48,11 @@ class EvalPrep:
         self.show_orig = args.show_orig
         self.tile = tuple(args.tile) if getattr(args, "tile", None) else None
         self.input_size = properties.input_size
+        self.baseline = getattr(args, "baseline", None)
+        self.baseline_args = dict(window=getattr(args, "baseline_window", 25), k=getattr(args, "baseline_k", 0.2))
+        self.baseline_result = None
+        if self.baseline:
+            check_params(self.baseline, **self.baseline_args)
         if self.dataset_name == "vgg":
             self.test_set = os.path.join(args.data_base_path, properties.vgg_text_dataset_test)
         elif self.dataset_name == "patch_dataset":
@@ -83,10 +94,20 @@ class EvalPrep:
             labels = [lbl.replace(" ", "") for lbl in labels]
         return labels
 
+    def _binarize(self, pages):
+        """the --baseline binariser over a list of [1, h, w] images -> the same list binarised (fp32 0 / 1), on the backend's device"""
+        return binarize_pages(pages, self.baseline, out="float", device=self.device, **self.baseline_args)
+
+    def _print_baseline(self, correct, cer, n, brackets):
+        print("Correct count from {} images: {:d}/{:d} ({:.5f})".format(self.baseline, correct, n, correct / n))
+        print(("Average CER from {} images: ({:.5f})" if brackets else "Average CER from {} images: {:.5f}").format(self.baseline, cer / n))
+        self.baseline_result = (correct / n, cer / n)
+
     def eval_area(self):
         print("Eval with ", self.ocr_name)
         self.prep_model.eval()
         pred_correct_count, ori_correct_count, ori_cer, pred_cer = 0, 0, 0.0, 0.0
+        base_correct_count, base_cer = 0, 0.0
         with torch.no_grad():
             for batch in self.loader_eval:
                 images, labels = batch[0], list(batch[1])
@@ -101,6 +122,10 @@ class EvalPrep:
                     c, e = compare_labels(ocr_lbl_ori, labels)
                     ori_correct_count += c
                     ori_cer += e
+                if self.baseline:
+                    c, e = compare_labels(self.ocr.get_labels(torch.stack(self._binarize(list(images))).cpu()), labels)
+                    base_correct_count += c
+                    base_cer += e
                 c, e = compare_labels(ocr_lbl_pred, labels)
                 pred_correct_count += c
                 pred_cer += e
@@ -115,6 +140,8 @@ class EvalPrep:
             print("Correct count from original images: {:d}/{:d} ({:.5f})".format(ori_correct_count, n, ori_correct_count / n))
             print("Average CER from original images: {:.5f}".format(ori_cer / n))
         print("Average CER from predicted images: {:.5f}".format(pred_cer / n))
+        if self.baseline:
+            self._print_baseline(base_correct_count, base_cer, n, brackets=False)
         self.orig_result = (ori_correct_count / n, ori_cer / n) if self.show_orig else None
         return pred_correct_count / n, pred_cer / n
 
@@ -122,6 +149,7 @@ class EvalPrep:
         print("Eval with ", self.ocr_name)
         self.prep_model.eval()
         ori_lbl_crt_count, ori_lbl_cer, prd_lbl_crt_count, prd_lbl_cer, lbl_count = 0, 0.0, 0, 0.0, 0
+        base_crt_count, base_cer = 0, 0.0
         with torch.no_grad():
             for i in range(len(self.dataset)):
                 item = self.dataset[i]
@@ -144,6 +172,11 @@ class EvalPrep:
                 except QeaError as err:
                     raise ValueError(f"{name} ({pred.shape[-2]}x{pred.shape[-1]}): the device crops refuse this page: {err}") from err
                 lbl_count += len(labels)
+                if self.baseline:
+                    base_crops, _ = get_text_stack(self._binarize([image])[0], labels_dict, self.input_size)
+                    c, e = compare_labels(self._ocr(base_crops), labels)
+                    base_crt_count += c
+                    base_cer += e
                 pred_labels = self._ocr(pred_crops)
                 c, e = compare_labels(pred_labels, labels)
                 prd_lbl_crt_count += c
@@ -160,6 +193,8 @@ class EvalPrep:
             print("Correct count from original images: {:d}/{:d} ({:.5f})".format(ori_lbl_crt_count, lbl_count, ori_lbl_crt_count / lbl_count))
             print("Average CER from original images: ({:.5f})".format(ori_lbl_cer / lbl_count))
         print("Average CER from predicted images: ({:.5f})".format(prd_lbl_cer / lbl_count))
+        if self.baseline:
+            self._print_baseline(base_crt_count, base_cer, lbl_count, brackets=True)
         self.orig_result = (ori_lbl_crt_count / lbl_count, ori_lbl_cer / lbl_count) if self.show_orig else None
         return prd_lbl_crt_count / lbl_count, prd_lbl_cer / lbl_count
 

@@ -166,6 +166,19 @@ FLAGS += [
     ("--batch_pages", dict(type=int, default=8, help="[new] pages decoded, cleaned and written per call of clean_pages"), "n"),
 ]
 
+# [new] the classic binarisers as baselines (qea/binarize.py): an extra column of eval_prep.py, another method of clean_cli.py
+FLAGS += [
+    ("--baseline", dict(choices=["otsu", "sauvola"], help="[new] also send the same images through this classic binariser (qea/binarize.py: "
+                                                         "binarize_pages) and the OCR engine, and print its correct count and CER beside the cleaner's"), "v"),
+    ("--baseline_window", dict(type=int, default=25, help="[new] --baseline sauvola: window side, odd, 3..127"), "v"),
+    ("--baseline_k", dict(type=float, default=0.2, help="[new] --baseline sauvola: k, strictly between 0 and 1"), "v"),
+    ("--method", dict(choices=["unet", "otsu", "sauvola"], default="unet",
+                      help="[new] unet: the trained preprocessor of --prep_path; otsu / sauvola: a classic binariser instead (no checkpoint is "
+                           "loaded, --tile is ignored)"), "n"),
+    ("--window", dict(type=int, default=25, help="[new] --method sauvola: window side, odd, 3..127"), "n"),
+    ("--k", dict(type=float, default=0.2, help="[new] --method sauvola: k, strictly between 0 and 1"), "n"),
+]
+
 
 def build_parser(which, description):
     import argparse

@@ -6,7 +6,9 @@ stream to libqea_hip.so and raises on any error.  No CPU implementation exists h
 import ctypes as C
 import os
 import weakref
+from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import _lib, beam
@@ -1199,3 +1201,74 @@ def seq_entropy(scores):
                "qea_seq_entropy")
     SAMPLER_LAUNCHES["entropy"] += 1
     return out
+
+
+BINARIZE_TILE, BINARIZE_CHUNK = (32, 64), 32768             # QEA_BINARIZE_TILE_H / _W / _CHUNK of include/qea_hip.h
+BINARIZE_MAX_WINDOW, BINARIZE_MAX_PAGE_PIXELS = 127, 1 << 27
+BINARIZE_LAUNCHES = {"sauvola": 0, "histogram": 0, "otsu": 0}    # launches of csrc/binarize.hip issued through this module (tests, tools)
+
+PageTable = namedtuple("PageTable", "n host_h host_w offset h w tile_first chunk_first words")
+
+
+def binarize_page_table(offset, h, w, device):
+    """The page table of a packed store (HOST arrays: element offset int64 [n], h / w int32 [n]) plus the two block-to-page prefix tables
+    of csrc/binarize.hip, in ONE upload: -> PageTable (device pointers into one int32 tensor, which it keeps alive, and the host copies
+    of h / w the entry points validate).  Page sizes are checked by the entry points, not here."""
+    if torch.device(device).type != "cuda":
+        raise _lib.QeaError(f"the binarisation kernels need a CUDA device (qea/binarize.py has the host path), not {device}")
+    offset, h, w = (np.ascontiguousarray(np.asarray(a), dt) for a, dt in ((offset, np.int64), (h, np.int32), (w, np.int32)))
+    n = offset.size
+    if n < 1 or h.shape != (n,) or w.shape != (n,) or offset.shape != (n,):
+        raise _lib.QeaError(f"page table: offset {offset.shape}, h {h.shape}, w {w.shape} are not three arrays of one length >= 1")
+    h64, w64 = np.maximum(h.astype(np.int64), 0), np.maximum(w.astype(np.int64), 0)
+    tiles = -(-h64 // BINARIZE_TILE[0]) * -(-w64 // BINARIZE_TILE[1])
+    chunks = -(-(h64 * w64) // BINARIZE_CHUNK)
+    if int(tiles.sum()) >= 2 ** 31 or int(chunks.sum()) >= 2 ** 31:
+        raise _lib.QeaError(f"page table: {int(tiles.sum())} tiles / {int(chunks.sum())} chunks, more than 2^31 - 1 workgroups")
+    first = [np.concatenate([[0], np.cumsum(c)]).astype(np.int32) for c in (tiles, chunks)]
+    words = torch.from_numpy(np.concatenate([offset.view(np.int32), h, w] + first)).to(device)      # the int64 offsets lead: 8-byte aligned
+    at = np.cumsum([0, 2 * n, n, n, n + 1]) * 4 + words.data_ptr()
+    return PageTable(n, h, w, *(int(a) for a in at), words)
+
+
+def _binarize_args(who, store, table, *outs):
+    """-> the leading arguments the three entry points of csrc/binarize.hip share; outs: (name, tensor or None, dtype), as large as the store"""
+    if not torch.is_tensor(store) or store.dtype not in (torch.uint8, torch.float32) or store.dim() != 1 or not store.is_cuda:
+        raise _lib.QeaError(f"{who} needs a one-dimensional uint8 or float32 CUDA store")
+    if table.words.device != store.device:
+        raise _lib.QeaError(f"{who}: the page table is on {table.words.device}, the store on {store.device}")
+    _tensors(who, store.device, ("store", store, store.dtype), *((name, t, dt, store.numel()) for name, t, dt in outs if t is not None))
+    return (store.data_ptr(), int(store.dtype == torch.float32), store.numel(), table.offset, table.h, table.w, table.n,
+            table.host_h.ctypes.data, table.host_w.ctypes.data)
+
+
+def binarize_sauvola(store, table, window=25, k=0.2, R=128.0, out_f32=None, out_u8=None):
+    """include/qea_hip.h: qea_binarize_sauvola — every page of the packed `store` (uint8 or fp32; `table`: binarize_page_table) through
+    Sauvola's rule in ONE launch on the current stream: 0 / 0.0 for ink, 255 / 1.0 for background into out_u8 and / or out_f32, packed
+    like the store."""
+    args = _binarize_args("binarize_sauvola", store, table, ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
+    _lib.check(_lib.lib().qea_binarize_sauvola(*args, table.tile_first, int(window), float(k), float(R), _ptr(out_f32), _ptr(out_u8), _stream()),
+               "qea_binarize_sauvola")
+    BINARIZE_LAUNCHES["sauvola"] += 1
+
+
+def otsu_histogram(store, table):
+    """include/qea_hip.h: qea_otsu_histogram — launch 1 of Otsu -> the pages' grey-level counts, int32 [n][256] on the device (the entry
+    point zeroes the table itself)."""
+    args = _binarize_args("otsu_histogram", store, table)
+    hist = torch.empty(table.n, 256, dtype=torch.int32, device=store.device)
+    _lib.check(_lib.lib().qea_otsu_histogram(*args, table.chunk_first, hist.data_ptr(), _stream()), "qea_otsu_histogram")
+    BINARIZE_LAUNCHES["histogram"] += 1
+    return hist
+
+
+def binarize_otsu(store, table, hist, out_f32=None, out_u8=None):
+    """include/qea_hip.h: qea_binarize_otsu — launch 2 of Otsu: every workgroup derives its page's threshold from `hist` (otsu_histogram)
+    and writes ink as 0 / 0.0, background as 255 / 1.0 -> the thresholds, int32 [n] on the device (-1: a page of one grey level)."""
+    args = _binarize_args("binarize_otsu", store, table, ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
+    (hist_p,) = _tensors("binarize_otsu", store.device, ("hist", hist, torch.int32, table.n * 256))
+    thresholds = torch.empty(table.n, dtype=torch.int32, device=store.device)
+    _lib.check(_lib.lib().qea_binarize_otsu(*args, table.chunk_first, hist_p, _ptr(out_f32), _ptr(out_u8), thresholds.data_ptr(), _stream()),
+               "qea_binarize_otsu")
+    BINARIZE_LAUNCHES["otsu"] += 1
+    return thresholds
