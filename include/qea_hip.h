@@ -772,6 +772,49 @@ int qea_binarize_otsu(const void* store, int32_t store_is_f32, int64_t store_ele
                       const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* chunk_first,
                       const uint32_t* hist, float* out_f32, uint8_t* out_u8, int32_t* thresholds, void* stream);
 
+/* Connected components over the same page store (csrc/components.hip; qea/components.py: label_pages, page_components, despeckle_pages,
+ * word_boxes; the statement, which the device, the host path and tests/components_spec.py reproduce bit for bit, is DESIGN.md "Connected
+ * components").  The leading arguments, host_h / host_w and tile_first are those of qea_binarize_sauvola (tiles of QEA_BINARIZE_TILE_H x
+ * QEA_BINARIZE_TILE_W).  A pixel is ink iff its 8-bit value is <= ink_max (0..254), or, where a uint8 mask packed like the store is given
+ * (ink_mask / in_mask, may be NULL), iff its mask byte is not 0.  labels and area are int32 arrays packed like the store (page p's element
+ * i at offset[p] + i); what lies between the pages is never written, by any of the five.
+ * qea_cc_label — three launches (tile, border, flatten): labels[i] = the smallest row-major index y * w + x within the page over the pixels
+ *   of pixel i's component at connectivity 4 or 8, -1 for background.  The border launch is a lock-free min-index union-find with agent-scope
+ *   atomics; no kernel waits for another workgroup, every walk moves to a strictly smaller index.  If area is not NULL its in-page elements
+ *   are cleared to 0 by the first launch, which is what qea_cc_stats expects.
+ * qea_cc_stats — one launch: ADDS every component's pixel count to area[its root] (one integer atomic per tile and distinct root: exact),
+ *   so that after qea_cc_label(..., area) + qea_cc_stats area holds the component's area at its root and 0 at every other in-page element.
+ * qea_cc_despeckle — one launch: ink pixels of components with area >= min_area (>= 1) are written as 0 / 0.0f, everything else in the
+ *   pages as 255 / 1.0f, to out_u8 and / or out_f32 (either may be NULL, not both), as qea_binarize_sauvola writes.
+ * qea_cc_smear — one launch, one direction of run-length smoothing (vertical = 0: along rows, 1: along columns): out_mask (uint8, 1 = ink,
+ *   0 = background) = the ink, plus every background pixel with ink at distance a >= 1 before and b >= 1 after it in its row / column and
+ *   a + b - 1 <= gap (0..QEA_CC_MAX_GAP).  Outside the page is background.  out_mask must not be in_mask.
+ * qea_cc_boxes — one launch: roots is the caller's ascending list of page-relative roots of all pages, int32 [n_roots], page p's being
+ *   roots[root_first[p] .. root_first[p + 1]) (root_first: int32 [n_pages + 1] on the device); boxes is int32 [n_roots][4] =
+ *   (x_min, y_min, x_max, y_max), which the caller fills with (INT32_MAX, INT32_MAX, -1, -1); every pixel whose label is listed lowers /
+ *   raises its row with integer atomicMin / atomicMax (one per tile, distinct root and bound).  Labels that are not listed are skipped.
+ * Nothing synchronises, no workspace; the launches of a call do not depend on the page count or content.  Refused before any launch: what
+ * the binarisers refuse of the leading arguments (a NULL pointer, n_pages < 1, an empty page, a page over 2^27 pixels, ...), a NULL or
+ * misaligned labels / area / roots / root_first / boxes / out_f32, both outputs NULL, connectivity other than 4 or 8, ink_max outside
+ * 0..254, min_area < 1, a gap outside 0..QEA_CC_MAX_GAP, n_roots < 0.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects these five by symbol.) */
+#define QEA_CC_MAX_GAP 127
+int qea_cc_label(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h, const int32_t* w,
+                 int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first, const uint8_t* ink_mask,
+                 int32_t ink_max, int32_t connectivity, int32_t* labels, int32_t* area, void* stream);
+int qea_cc_stats(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h, const int32_t* w,
+                 int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first, const int32_t* labels,
+                 int32_t* area, void* stream);
+int qea_cc_despeckle(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h,
+                     const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first,
+                     const int32_t* labels, const int32_t* area, int32_t min_area, float* out_f32, uint8_t* out_u8, void* stream);
+int qea_cc_smear(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h, const int32_t* w,
+                 int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first, const uint8_t* in_mask,
+                 int32_t ink_max, int32_t gap, int32_t vertical, uint8_t* out_mask, void* stream);
+int qea_cc_boxes(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h, const int32_t* w,
+                 int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first, const int32_t* labels,
+                 const int32_t* roots, const int32_t* root_first, int32_t n_roots, int32_t* boxes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

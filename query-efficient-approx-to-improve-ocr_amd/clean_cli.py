@@ -11,12 +11,22 @@ the HIP path; the oracle backend runs the same plan on the host).
 
 --method otsu / sauvola writes the classic baseline instead (qea/binarize.py: binarize_pages, one call per --batch_pages group): no
 checkpoint is loaded and --tile is ignored; same output names, sizes and 8-bit PNG format, ink 0 and background 255.
+
+[new] --despeckle N (with --method otsu / sauvola) also turns connected components of fewer than N ink pixels into background
+(binarize_pages(despeckle=N)); with the UNet, whose output is grey, it is a ValueError at construction.
+[new] --boxes [--boxes_gap G --boxes_min_area A], with any method: the word boxes of every WRITTEN page (8-bit, ink = 127 or darker;
+qea/components.py: word_boxes, one call per --batch_pages group) go into <stem>.json beside the PNG as a list of {"label": "", "x_min",
+"y_min", "x_max", "y_max"}, the form datasets/patch_dataset.py reads.  x_max / y_max are EXCLUSIVE, one past the component's last column
+and row, because the crops (utils.get_text_stack, the crop kernel) cut image[y_min:y_max, x_min:x_max]: the crop of a box holds every
+pixel of its component.
 """
+import json
 import os
 
 import numpy as np
 import torch
 
+from qea import components
 from qea.binarize import binarize_pages, check_params
 from qea.pages import clean_pages
 from qea.trainer_core import hip_backend
@@ -31,6 +41,15 @@ class CleanPages:
         self.batch_pages = max(1, int(args.batch_pages))
         self.device = (backend or hip_backend()).device
         self.method = getattr(args, "method", "unet")
+        self.despeckle = int(getattr(args, "despeckle", 0) or 0)
+        self.boxes = bool(getattr(args, "boxes", False))
+        self.boxes_gap, self.boxes_min_area = getattr(args, "boxes_gap", 8), getattr(args, "boxes_min_area", 16)
+        if self.despeckle:
+            if self.method == "unet":
+                raise ValueError("--despeckle needs --method otsu or sauvola: the UNet's output is grey, and despeckling would binarise it")
+            components.check_params(min_area=self.despeckle)
+        if self.boxes:
+            components.check_params(min_area=self.boxes_min_area, gap_x=self.boxes_gap)
         if self.method == "unet":
             self.prep_model = torch.load(args.prep_path, map_location=self.device, weights_only=False).to(self.device).eval()
         else:
@@ -56,11 +75,17 @@ class CleanPages:
             if self.method == "unet":
                 cleaned = clean_pages(self.prep_model, pages, tile=self.tile, out="u8")
             else:
-                cleaned = binarize_pages(pages, self.method, window=self.window, k=self.k, out="u8", device=self.device)
-            for n, page in zip(names, cleaned):
+                cleaned = binarize_pages(pages, self.method, window=self.window, k=self.k, out="u8", device=self.device,
+                                         despeckle=self.despeckle)
+            boxes = components.word_boxes(cleaned, gap_x=self.boxes_gap, min_area=self.boxes_min_area, device=self.device) if self.boxes else None
+            for i, (n, page) in enumerate(zip(names, cleaned)):
                 path = os.path.join(self.out_dir, os.path.splitext(n)[0] + ".png")
                 Image.fromarray(page.cpu().numpy()).save(path)
                 written.append(path)
+                if boxes is not None:                          # x_max / y_max one past the last pixel: the crops' slicing convention
+                    rows = [dict(label="", x_min=a, y_min=b, x_max=c + 1, y_max=d + 1) for a, b, c, d in boxes[i].cpu().tolist()]
+                    with open(os.path.splitext(path)[0] + ".json", "w") as f:
+                        json.dump(rows, f)
         print(f"{len(written)} pages cleaned into {self.out_dir}")
         return written
 

@@ -21,6 +21,9 @@ Returns (accuracy, cer) of the cleaned strips, as the reference's patch flow doe
     images" and sets self.baseline_result = (accuracy, cer).  Area flow: every strip of the batch is its own page.  Patch flow: the
     document the model sees is binarised as a whole, then cut by get_text_stack, so window statistics come from the page, not from
     the crop.  Return values and the other prints stay as they are.
+  * [new] --baseline_despeckle N (only with --baseline) puts the area filter of every classic pipeline behind the binariser: connected
+    components of fewer than N ink pixels become background (binarize_pages(despeckle=N)); the printed method name becomes e.g.
+    "sauvola+despeckle4".
   * [new] --synthetic_size N evaluates on N synthetic strips / documents (datasets/synthetic.py).
   * The loaders run in the main process (the reference asks for properties.num_workers workers).
 `backend` / `dataset` / `ocr` are injection seams for tests, as in the trainers; the default backend is the HIP path.
@@ -32,6 +35,7 @@ import torch
 import properties
 from qea._lib import QeaError
 from qea.binarize import binarize_pages, check_params
+from qea.components import check_params as components_check
 from qea.pages import clean_pages
 from qea.trainer_core import hip_backend
 from utils import compare_labels, get_ocr_helper, get_text_stack, show_img
@@ -51,8 +55,14 @@ class EvalPrep:
         self.baseline = getattr(args, "baseline", None)
         self.baseline_args = dict(window=getattr(args, "baseline_window", 25), k=getattr(args, "baseline_k", 0.2))
         self.baseline_result = None
+        self.baseline_despeckle = int(getattr(args, "baseline_despeckle", 0) or 0)
+        if self.baseline_despeckle and not self.baseline:
+            raise ValueError("--baseline_despeckle needs --baseline otsu or sauvola")
         if self.baseline:
             check_params(self.baseline, **self.baseline_args)
+        if self.baseline_despeckle:
+            components_check(min_area=self.baseline_despeckle)
+        self.baseline_name = (self.baseline or "") + (f"+despeckle{self.baseline_despeckle}" if self.baseline_despeckle else "")
         if self.dataset_name == "vgg":
             self.test_set = os.path.join(args.data_base_path, properties.vgg_text_dataset_test)
         elif self.dataset_name == "patch_dataset":
@@ -96,11 +106,11 @@ class EvalPrep:
 
     def _binarize(self, pages):
         """the --baseline binariser over a list of [1, h, w] images -> the same list binarised (fp32 0 / 1), on the backend's device"""
-        return binarize_pages(pages, self.baseline, out="float", device=self.device, **self.baseline_args)
+        return binarize_pages(pages, self.baseline, out="float", device=self.device, despeckle=self.baseline_despeckle, **self.baseline_args)
 
     def _print_baseline(self, correct, cer, n, brackets):
-        print("Correct count from {} images: {:d}/{:d} ({:.5f})".format(self.baseline, correct, n, correct / n))
-        print(("Average CER from {} images: ({:.5f})" if brackets else "Average CER from {} images: {:.5f}").format(self.baseline, cer / n))
+        print("Correct count from {} images: {:d}/{:d} ({:.5f})".format(self.baseline_name, correct, n, correct / n))
+        print(("Average CER from {} images: ({:.5f})" if brackets else "Average CER from {} images: {:.5f}").format(self.baseline_name, cer / n))
         self.baseline_result = (correct / n, cer / n)
 
     def eval_area(self):

@@ -122,26 +122,35 @@ def _device(pk, dev, method, window, k, R, out):
     return res, ops.binarize_otsu(store, table, ops.otsu_histogram(store, table), **outs)
 
 
-def _run(pages, method, window, k, R, out, device):
+def _run(pages, method, window, k, R, out, device, despeckle=0, despeckle_connectivity=8):
     _check_out(out)
     check_params(method, window, k, R)
+    if despeckle:
+        from . import components
+        components.check_params(despeckle_connectivity, min_area=despeckle)
     _check_sizes(pages)
     pk = pack_pages(pages)
     dev = torch.device(device) if device is not None else pk.store.device
     if dev.type == "cuda":
         res, thr = _device(pk, dev, method, int(window), float(k), float(R), out)
+        if despeckle:                                          # the packed result is the next store: nothing is unpacked or copied
+            from . import ops
+            res = components.despeckle_store(res, ops.binarize_page_table(pk.offset, pk.h, pk.w, dev), despeckle, despeckle_connectivity, out=out)
     else:
         pk = pk._replace(store=pk.store.cpu())
         res, thr = _host(pk, method, int(window), float(k), float(R), out)
+        if despeckle:
+            res = components.despeckle_store_host(pk._replace(store=res), despeckle, despeckle_connectivity, out=out)
     return unpack_pages(res, pk), thr
 
 
-def binarize_pages(pages, method="sauvola", window=25, k=0.2, R=128.0, out="float", device=None):
+def binarize_pages(pages, method="sauvola", window=25, k=0.2, R=128.0, out="float", device=None, despeckle=0, despeckle_connectivity=8):
     """pages: a list of [h, w] uint8 tensors or of [h, w] / [1, h, w] floating tensors, of any sizes (as for clean_pages) -> a list of the
     same sizes: 0.0 / 1.0 fp32 for out="float", 0 / 255 uint8 for out="u8", ink = 0.  method "otsu" (window, k, R unused) or "sauvola".
     The result lives on `device` if given, else where the pages are; a CUDA device runs the kernels, the host runs the same statement
-    in numpy."""
-    return _run(pages, method, window, k, R, out, device)[0]
+    in numpy.  despeckle = N > 0 also turns the ink of connected components (despeckle_connectivity 4 or 8) of fewer than N pixels into
+    background (qea/components.py: the binarised store goes through label, stats and apply where it is); 0 changes nothing."""
+    return _run(pages, method, window, k, R, out, device, despeckle, despeckle_connectivity)[0]
 
 
 def otsu_thresholds(pages, device=None):

@@ -179,6 +179,19 @@ FLAGS += [
     ("--k", dict(type=float, default=0.2, help="[new] --method sauvola: k, strictly between 0 and 1"), "n"),
 ]
 
+# [new] connected components (qea/components.py): the area filter every classic pipeline puts behind its binariser, and word boxes
+FLAGS += [
+    ("--baseline_despeckle", dict(type=int, default=0, help="[new] --baseline: also turn connected components (connectivity 8) of fewer than N ink "
+                                                            "pixels of the binarised image into background; 0 = off"), "v"),
+    ("--despeckle", dict(type=int, default=0, help="[new] --method otsu / sauvola: also turn connected components (connectivity 8) of fewer than N "
+                                                   "ink pixels into background; 0 = off.  Refused with --method unet, whose output is grey"), "n"),
+    ("--boxes", dict(action="store_true", help="[new] also write <stem>.json beside every PNG: the word boxes of the written page (ink = 127 "
+                                               "or darker) by run-length smearing and connected components, in the x_min / y_min / x_max / y_max "
+                                               "form datasets/patch_dataset.py reads, labels empty"), "n"),
+    ("--boxes_gap", dict(type=int, default=8, help="[new] --boxes: horizontal gaps of at most G background pixels join into one word, 0..127"), "n"),
+    ("--boxes_min_area", dict(type=int, default=16, help="[new] --boxes: drop words of fewer than A smeared pixels"), "n"),
+]
+
 
 def build_parser(which, description):
     import argparse

@@ -1272,3 +1272,82 @@ def binarize_otsu(store, table, hist, out_f32=None, out_u8=None):
                "qea_binarize_otsu")
     BINARIZE_LAUNCHES["otsu"] += 1
     return thresholds
+
+
+CC_MAX_GAP = 127                                               # QEA_CC_MAX_GAP of include/qea_hip.h
+# launches of csrc/components.hip issued through this module, one key per kernel (tests, tools)
+COMPONENT_LAUNCHES = {"tile": 0, "border": 0, "flatten": 0, "stats": 0, "despeckle": 0, "smear": 0, "boxes": 0}
+
+
+def _cc_buffer(who, store, name, t, dtype=torch.int32):
+    """a working buffer packed like the store: the given one, checked, or a new one"""
+    if t is None:
+        return torch.empty(store.numel(), dtype=dtype, device=store.device)
+    _tensors(who, store.device, (name, t, dtype, store.numel()))
+    return t
+
+
+def cc_label(store, table, connectivity=8, ink_max=127, ink_mask=None, labels=None, area=None):
+    """include/qea_hip.h: qea_cc_label — three launches (tile, border, flatten) on the current stream -> labels, int32 packed like the
+    store: an ink pixel's label is the smallest page-relative index of its component, background is -1.  `ink_mask` (uint8, packed like
+    the store) replaces the ink_max threshold; `area` (int32, packed like the store) is cleared inside the pages for cc_stats."""
+    args = _binarize_args("cc_label", store, table)
+    labels = _cc_buffer("cc_label", store, "labels", labels)
+    if ink_mask is not None:
+        _tensors("cc_label", store.device, ("ink_mask", ink_mask, torch.uint8, store.numel()))
+    if area is not None:
+        _tensors("cc_label", store.device, ("area", area, torch.int32, store.numel()))
+    _lib.check(_lib.lib().qea_cc_label(*args, table.tile_first, _ptr(ink_mask), int(ink_max), int(connectivity), labels.data_ptr(), _ptr(area),
+                                       _stream()), "qea_cc_label")
+    for key in ("tile", "border", "flatten"):
+        COMPONENT_LAUNCHES[key] += 1
+    return labels
+
+
+def cc_stats(store, table, labels, area):
+    """include/qea_hip.h: qea_cc_stats — one launch: adds every component's pixel count to area[its root]; `area` is the buffer cc_label
+    cleared -> area"""
+    args = _binarize_args("cc_stats", store, table, ("labels", labels, torch.int32), ("area", area, torch.int32))
+    _lib.check(_lib.lib().qea_cc_stats(*args, table.tile_first, labels.data_ptr(), area.data_ptr(), _stream()), "qea_cc_stats")
+    COMPONENT_LAUNCHES["stats"] += 1
+    return area
+
+
+def cc_despeckle(store, table, labels, area, min_area, out_f32=None, out_u8=None):
+    """include/qea_hip.h: qea_cc_despeckle — one launch: ink of components of at least min_area pixels as 0 / 0.0, everything else as
+    255 / 1.0 into out_u8 and / or out_f32, packed like the store."""
+    args = _binarize_args("cc_despeckle", store, table, ("labels", labels, torch.int32), ("area", area, torch.int32),
+                          ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
+    _lib.check(_lib.lib().qea_cc_despeckle(*args, table.tile_first, labels.data_ptr(), area.data_ptr(), int(min_area), _ptr(out_f32),
+                                           _ptr(out_u8), _stream()), "qea_cc_despeckle")
+    COMPONENT_LAUNCHES["despeckle"] += 1
+
+
+def cc_smear(store, table, gap, vertical=False, ink_max=127, in_mask=None, out_mask=None):
+    """include/qea_hip.h: qea_cc_smear — one launch, one direction of run-length smoothing over the ink of the store (or of `in_mask`)
+    -> out_mask, uint8 1 / 0 packed like the store"""
+    args = _binarize_args("cc_smear", store, table)
+    if in_mask is not None:
+        _tensors("cc_smear", store.device, ("in_mask", in_mask, torch.uint8, store.numel()))
+    out_mask = _cc_buffer("cc_smear", store, "out_mask", out_mask, torch.uint8)
+    _lib.check(_lib.lib().qea_cc_smear(*args, table.tile_first, _ptr(in_mask), int(ink_max), int(gap), int(bool(vertical)), out_mask.data_ptr(),
+                                       _stream()), "qea_cc_smear")
+    COMPONENT_LAUNCHES["smear"] += 1
+    return out_mask
+
+
+def cc_boxes(store, table, labels, roots, root_first):
+    """include/qea_hip.h: qea_cc_boxes — one launch.  roots: the ascending page-relative roots of all pages, int32 [n] on the device, page
+    p's being roots[root_first[p]:root_first[p + 1]] (root_first: int32 [pages + 1] on the device) -> int32 [n][4] = (x_min, y_min,
+    x_max, y_max) of the listed components, inclusive"""
+    args = _binarize_args("cc_boxes", store, table, ("labels", labels, torch.int32))
+    n = roots.numel()
+    _tensors("cc_boxes", store.device, ("roots", roots, torch.int32), ("root_first", root_first, torch.int32, table.n + 1))
+    boxes = torch.empty(max(n, 1), 4, dtype=torch.int32, device=store.device)      # one spare row: an empty list still has an address
+    boxes[:, :2] = 2 ** 31 - 1
+    boxes[:, 2:] = -1
+    roots_p = roots.data_ptr() if n else boxes.data_ptr()
+    _lib.check(_lib.lib().qea_cc_boxes(*args, table.tile_first, labels.data_ptr(), roots_p, root_first.data_ptr(), n, boxes.data_ptr(), _stream()),
+               "qea_cc_boxes")
+    COMPONENT_LAUNCHES["boxes"] += 1
+    return boxes[:n]
