@@ -815,6 +815,46 @@ int qea_cc_boxes(const void* store, int32_t store_is_f32, int64_t store_elems, c
                  int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first, const int32_t* labels,
                  const int32_t* roots, const int32_t* root_first, int32_t n_roots, int32_t* boxes, void* stream);
 
+/* Page skew estimation and deskew over the same page store (csrc/deskew.hip; qea/deskew.py: estimate_skew, deskew_pages; the statement,
+ * which the device, the host path and tests/deskew_spec.py reproduce bit for bit, is DESIGN.md "Deskew").  Everything is an integer.  The
+ * leading arguments and host_h / host_w are those of qea_binarize_sauvola; a page is at most QEA_DESKEW_MAX_SIDE rows and columns and
+ * QEA_BINARIZE_MAX_PAGE_PIXELS pixels.  A candidate slope is a / 1024 for a = -A..A, A in 0..QEA_DESKEW_MAX_SLOPE.
+ * qea_skew_strip_sums — one launch, one pass over the pixels: C[j][y] = the number of ink pixels of row y in columns [32 j, 32 j + 32) cut
+ *   to w, for j < ns = ceil(w / 32).  A pixel is ink iff its 8-bit value is <= ink_max; ink_max is ink_max_dev[p] (int32 [n_pages] on the
+ *   device, e.g. the thresholds of qea_binarize_otsu, -1..254, -1 = no ink) where that pointer is given, else the scalar (0..254).  C is a
+ *   byte array PACKED LIKE THE STORE: page p's C[j][y] is byte offset[p] + j * h[p] + y (ns h <= h w); nothing else is written.
+ * qea_skew_scores — zeroes scores (int64 [n_pages][2 A + 1], hipMemsetAsync on the stream), then one launch: with the shift
+ *   d(j, a) = floor((a (32 j + 16 - w div 2) + 512) / 1024) and P_a[r] = sum_j C[j][r + d(j, a)] (rows outside [0, h) count 0),
+ *   scores[p][a + A] = sum_{r = 0}^{h - 2} (P_a[r + 1] - P_a[r])^2.  Partial sums over chunks of rows meet in integer atomics: exact.
+ * qea_skew_pick — one launch: slopes[p] = the a of the largest score, ties to the smallest |a|, then to the negative one; kept only if
+ *   100 (S_a - S_0) >= g S_0 in int64 (g in 0..10000), else 0.  It reads any scores array of that shape.
+ * qea_deskew_rotate — ONE launch for all pages (tiles and tile_first of qea_binarize_sauvola): page p is rotated about its centre by the
+ *   slope a = slopes[p] (device int32 [n_pages]) into outputs packed like the store.  table is int32 [2 A + 1][2] on the device, row
+ *   a + A = (C16, S16) = (round(65536 / n), round(65536 t / n)), t = a / 1024, n = sqrt(1 + t t), built by the HOST.  For output pixel
+ *   (x, y), in int64: dx2 = 2 x - (w - 1), dy2 = 2 y - (h - 1), X = C16 dx2 - S16 dy2 + 65536 (w - 1), Y = S16 dx2 + C16 dy2 + 65536 (h - 1),
+ *   x0 = X >> 17, y0 = Y >> 17, fx = (X >> 9) & 255, fy = (Y >> 9) & 255 (arithmetic shifts) and
+ *   out = ((256 - fx)(256 - fy) p(y0, x0) + fx (256 - fy) p(y0, x0 + 1) + (256 - fx) fy p(y0 + 1, x0) + fx fy p(y0 + 1, x0 + 1) + 32768) >> 16;
+ *   nearest = 1 takes p((Y + 65536) >> 17, (X + 65536) >> 17) instead.  A tap outside the page reads fill (0..255).  out_u8 receives the
+ *   value, out_f32 norm[value] (norm: 256 fp32 values on the device, float32(v) / 255 built by the host); either may be NULL, not both,
+ *   and neither may overlap the store.  A page whose slope lies outside -A..A is left unwritten.
+ * Nothing synchronises, no workspace, no LDS beyond a transpose buffer; the launches do not depend on the content.  Refused before any
+ * launch: what the binarisers refuse of the leading arguments, a side over QEA_DESKEW_MAX_SIDE, A, g, ink_max, fill or nearest outside
+ * their ranges, a NULL or misaligned C / scores / slopes / table / norm / out_f32, both outputs NULL, an output that overlaps the store.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects these four by symbol.) */
+#define QEA_DESKEW_MAX_SIDE 32767
+#define QEA_DESKEW_MAX_SLOPE 256
+#define QEA_DESKEW_MAX_GAIN 10000
+int qea_skew_strip_sums(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h,
+                        const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* ink_max_dev,
+                        int32_t ink_max, uint8_t* C, void* stream);
+int qea_skew_scores(const uint8_t* C, int64_t store_elems, const int64_t* offset, const int32_t* h, const int32_t* w, int32_t n_pages,
+                    const int32_t* host_h, const int32_t* host_w, int32_t A, int64_t* scores, void* stream);
+int qea_skew_pick(const int64_t* scores, int32_t n_pages, int32_t A, int32_t g, int32_t* slopes, void* stream);
+int qea_deskew_rotate(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h,
+                      const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first,
+                      const int32_t* slopes, const int32_t* table, int32_t A, int32_t nearest, int32_t fill, const float* norm,
+                      float* out_f32, uint8_t* out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

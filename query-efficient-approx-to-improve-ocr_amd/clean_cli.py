@@ -19,6 +19,10 @@ qea/components.py: word_boxes, one call per --batch_pages group) go into <stem>.
 "y_min", "x_max", "y_max"}, the form datasets/patch_dataset.py reads.  x_max / y_max are EXCLUSIVE, one past the component's last column
 and row, because the crops (utils.get_text_stack, the crop kernel) cut image[y_min:y_max, x_min:x_max]: the crop of a box holds every
 pixel of its component.
+[new] --deskew [--deskew_max_slope A --deskew_min_gain G --deskew_interp {bilinear,nearest}], with any method: the decoded 8-bit pages of a
+--batch_pages group first go through ONE call of qea/deskew.py: deskew_pages (skew estimate from each page's Otsu ink, rotation about the
+page centre, white fill), so that the UNet or the binariser, and with them --boxes, see and describe the deskewed page that is written;
+a line "<stem>: slope a/1024" is printed per page.  Without the flag nothing changes.
 """
 import json
 import os
@@ -26,7 +30,7 @@ import os
 import numpy as np
 import torch
 
-from qea import components
+from qea import components, deskew
 from qea.binarize import binarize_pages, check_params
 from qea.pages import clean_pages
 from qea.trainer_core import hip_backend
@@ -44,6 +48,11 @@ class CleanPages:
         self.despeckle = int(getattr(args, "despeckle", 0) or 0)
         self.boxes = bool(getattr(args, "boxes", False))
         self.boxes_gap, self.boxes_min_area = getattr(args, "boxes_gap", 8), getattr(args, "boxes_min_area", 16)
+        self.deskew = bool(getattr(args, "deskew", False))
+        self.deskew_max_slope, self.deskew_min_gain = getattr(args, "deskew_max_slope", 90), getattr(args, "deskew_min_gain", 0)
+        self.deskew_interp = getattr(args, "deskew_interp", "bilinear")
+        if self.deskew:
+            deskew.check_params(self.deskew_max_slope, min_gain=self.deskew_min_gain, interp=self.deskew_interp)
         if self.despeckle:
             if self.method == "unet":
                 raise ValueError("--despeckle needs --method otsu or sauvola: the UNet's output is grey, and despeckling would binarise it")
@@ -72,6 +81,11 @@ class CleanPages:
             for n in names:
                 with Image.open(os.path.join(self.in_dir, n)) as img:
                     pages.append(torch.from_numpy(np.array(img.convert("L"), dtype=np.uint8)))
+            if self.deskew:
+                pages, slopes = deskew.deskew_pages(pages, self.deskew_max_slope, min_gain=self.deskew_min_gain, interp=self.deskew_interp,
+                                                    out="u8", device=self.device)
+                for n, a in zip(names, slopes.cpu().tolist()):
+                    print(f"{os.path.splitext(n)[0]}: slope {a}/1024")
             if self.method == "unet":
                 cleaned = clean_pages(self.prep_model, pages, tile=self.tile, out="u8")
             else:

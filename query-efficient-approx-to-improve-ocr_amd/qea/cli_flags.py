@@ -192,6 +192,17 @@ FLAGS += [
     ("--boxes_min_area", dict(type=int, default=16, help="[new] --boxes: drop words of fewer than A smeared pixels"), "n"),
 ]
 
+# [new] page skew estimation and deskew (qea/deskew.py): the first stage of clean_cli.py's page pipeline
+FLAGS += [
+    ("--deskew", dict(action="store_true", help="[new] first estimate every page's skew (projection profiles of its Otsu ink over the slopes "
+                                                "a / 1024) and rotate it about its centre, so that the cleaner or the binariser and --boxes see "
+                                                "horizontal lines; prints '<stem>: slope a/1024' per page"), "n"),
+    ("--deskew_max_slope", dict(type=int, default=90, help="[new] --deskew: the candidates are a = -A..A in 1024ths, 0..256 (90 = +-5.0 degrees)"), "n"),
+    ("--deskew_min_gain", dict(type=int, default=0, help="[new] --deskew: rotate only if the best score exceeds the unrotated page's by G per "
+                                                         "cent, 0..10000"), "n"),
+    ("--deskew_interp", dict(choices=["bilinear", "nearest"], default="bilinear", help="[new] --deskew: how the rotation resamples"), "n"),
+]
+
 
 def build_parser(which, description):
     import argparse

@@ -1351,3 +1351,70 @@ def cc_boxes(store, table, labels, roots, root_first):
                "qea_cc_boxes")
     COMPONENT_LAUNCHES["boxes"] += 1
     return boxes[:n]
+
+
+DESKEW_MAX_SIDE, DESKEW_MAX_SLOPE, DESKEW_MAX_GAIN = 32767, 256, 10000       # QEA_DESKEW_MAX_* of include/qea_hip.h
+# launches of csrc/deskew.hip issued through this module, one key per kernel (tests, tools)
+DESKEW_LAUNCHES = {"strip_sums": 0, "scores": 0, "pick": 0, "rotate": 0}
+
+
+def skew_strip_sums(store, table, ink_max=127, C=None):
+    """include/qea_hip.h: qea_skew_strip_sums — one launch -> C, uint8 packed like the store: page p's C[j][y], the ink pixels of row y in
+    the 32-column strip j, at offset[p] + j * h[p] + y.  ink_max: an integer 0..254, or an int32 [n] tensor on the device (-1..254 per
+    page, e.g. the thresholds binarize_otsu returns), which is read by the kernel, not by the host."""
+    args = _binarize_args("skew_strip_sums", store, table)
+    C = _cc_buffer("skew_strip_sums", store, "C", C, torch.uint8)
+    per_page = None
+    if torch.is_tensor(ink_max):
+        (per_page,) = _tensors("skew_strip_sums", store.device, ("ink_max", ink_max, torch.int32, table.n))
+    _lib.check(_lib.lib().qea_skew_strip_sums(*args, per_page, 0 if per_page else int(ink_max), C.data_ptr(), _stream()), "qea_skew_strip_sums")
+    DESKEW_LAUNCHES["strip_sums"] += 1
+    return C
+
+
+def skew_scores(C, table, A=90, scores=None):
+    """include/qea_hip.h: qea_skew_scores — one launch (the entry point zeroes the table itself) -> int64 [n][2 A + 1]: the differential
+    projection-profile score of every candidate slope a / 1024, a = -A..A, from the strip sums C"""
+    if not torch.is_tensor(C) or C.dim() != 1 or not C.is_cuda or table.words.device != C.device:
+        raise _lib.QeaError("skew_scores needs the one-dimensional uint8 CUDA array skew_strip_sums filled, on the page table's device")
+    _tensors("skew_scores", C.device, ("C", C, torch.uint8))
+    if scores is None:
+        scores = torch.empty(table.n, 2 * int(A) + 1, dtype=torch.int64, device=C.device)
+    _tensors("skew_scores", C.device, ("scores", scores, torch.int64, table.n * (2 * int(A) + 1)))
+    _lib.check(_lib.lib().qea_skew_scores(C.data_ptr(), C.numel(), table.offset, table.h, table.w, table.n, table.host_h.ctypes.data,
+                                          table.host_w.ctypes.data, int(A), scores.data_ptr(), _stream()), "qea_skew_scores")
+    DESKEW_LAUNCHES["scores"] += 1
+    return scores
+
+
+def skew_pick(scores, g=0, slopes=None):
+    """include/qea_hip.h: qea_skew_pick — one launch.  scores: int64 [n][2 A + 1] on the device, any values -> int32 [n]: per row the a of
+    the largest score (ties: the smallest |a|, then the negative one), or 0 where 100 (S_a - S_0) < g S_0"""
+    if not torch.is_tensor(scores) or scores.dim() != 2 or scores.shape[0] < 1 or scores.shape[1] % 2 != 1:
+        raise _lib.QeaError("skew_pick needs an int64 [n][2 A + 1] CUDA tensor")
+    n, A = scores.shape[0], scores.shape[1] // 2
+    _tensors("skew_pick", scores.device, ("scores", scores, torch.int64))
+    if slopes is None:
+        slopes = torch.empty(n, dtype=torch.int32, device=scores.device)
+    _tensors("skew_pick", scores.device, ("slopes", slopes, torch.int32, n))
+    _lib.check(_lib.lib().qea_skew_pick(scores.data_ptr(), n, A, int(g), slopes.data_ptr(), _stream()), "qea_skew_pick")
+    DESKEW_LAUNCHES["pick"] += 1
+    return slopes
+
+
+def deskew_rotate(store, table, slopes, rot_table, interp="bilinear", fill=255, norm=None, out_f32=None, out_u8=None):
+    """include/qea_hip.h: qea_deskew_rotate — ONE launch: every page of the packed store rotated about its centre by its slope
+    (slopes: int32 [n] on the device, read by the kernel only) into out_u8 and / or out_f32, packed like the store.  rot_table: int32
+    [2 A + 1][2] on the device (qea/deskew.py: rotation_table); norm: the 256 fp32 values an fp32 output is read through."""
+    if interp not in ("bilinear", "nearest"):
+        raise _lib.QeaError(f"deskew_rotate: interp={interp!r} is neither 'bilinear' nor 'nearest'")
+    args = _binarize_args("deskew_rotate", store, table, ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
+    if not torch.is_tensor(rot_table) or rot_table.dim() != 2 or rot_table.shape[1] != 2 or rot_table.shape[0] % 2 != 1:
+        raise _lib.QeaError("deskew_rotate: rot_table must be an int32 [2 A + 1][2] tensor")
+    _tensors("deskew_rotate", store.device, ("slopes", slopes, torch.int32, table.n), ("rot_table", rot_table, torch.int32))
+    if norm is not None:
+        _tensors("deskew_rotate", store.device, ("norm", norm, torch.float32, 256))
+    _lib.check(_lib.lib().qea_deskew_rotate(*args, table.tile_first, slopes.data_ptr(), rot_table.data_ptr(), rot_table.shape[0] // 2,
+                                            int(interp == "nearest"), int(fill), _ptr(norm), _ptr(out_f32), _ptr(out_u8), _stream()),
+               "qea_deskew_rotate")
+    DESKEW_LAUNCHES["rotate"] += 1
