@@ -383,17 +383,17 @@ def conv_wgrad(p, q, dw, *, B, PH, PW, QH, QW, R, Cc, KH, KW, pad=(0, 0), stride
         if q_amax is None:
             q_amax = absmax(q, ldq, B * QH * QW, Cc)
         d.p_absmax, d.q_absmax = p_amax.data_ptr(), q_amax.data_ptr()
-    if dbias is not None:
-        if L.qea_conv_wgrad_fuses_bias(C.byref(d)):
-            d.dbias = dbias.data_ptr()
-        else:
-            colsum(p, ldp, B * PH * PW, R, dbias, accumulate=accumulate)
+    fused = dbias is not None and bool(L.qea_conv_wgrad_fuses_bias(C.byref(d)))
+    if fused:
+        d.dbias = dbias.data_ptr()
     need = L.qea_conv_wgrad_workspace_bytes(C.byref(d))
     if need:
         ws = workspace(need, p.device)
         d.workspace = ws.data_ptr()
         d.workspace_bytes = ws.numel()
     _lib.check(L.qea_conv_wgrad(C.byref(d), _stream()), "qea_conv_wgrad")
+    if dbias is not None and not fused:                  # (behind the launch: a refused call leaves dbias as it found it)
+        colsum(p, ldp, B * PH * PW, R, dbias, accumulate=accumulate)
 
 
 # "split_f16" (default since round 3): the LDS-halo 3x3 kernels take the TWO-way fp16 split (ABI v6: three MFMAs per product,
