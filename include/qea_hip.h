@@ -855,6 +855,33 @@ int qea_deskew_rotate(const void* store, int32_t store_is_f32, int64_t store_ele
                       const int32_t* slopes, const int32_t* table, int32_t A, int32_t nearest, int32_t fill, const float* norm,
                       float* out_f32, uint8_t* out_u8, void* stream);
 
+/* Word boxes of the same page store cut into CRNN strips (csrc/word_strips.hip; qea/reading.py: word_strips, read_pages; the statement,
+ * which the device, the host path and tests/word_strips_spec.py reproduce bit for bit, is DESIGN.md "Word strips").
+ * qea_word_strips — ONE launch writes every element of out, fp32 [n][QEA_WORD_STRIP_H][OW].  store / store_is_f32 / store_elems / offset /
+ *   h / w / n_pages are the leading arguments of qea_binarize_sauvola (an fp32 element is read as the 8-bit value
+ *   (uint8)(min(max(x, 0), 1) * 255.0f)); boxes is int32 [n][5] = (page, x0, y0, x1, y1) on the device, x1 / y1 EXCLUSIVE, any int32 values;
+ *   norm is the 256 fp32 values a grey level is written as (float32(v) / 255 built by the host).  Per box: clipped to its page,
+ *   cw = x1 - x0, ch = y1 - y0; an empty box, a page index outside 0..n_pages-1, a page that does not lie inside the store or has a side
+ *   over QEA_WORD_STRIP_MAX_SIDE give an all-white (1.0f) strip.  ch <= 32: the crop centred in 32 x OW with Python floor division (left =
+ *   floor((OW - cw) / 2): an oversize width loses its extra pixel on the left), white elsewhere — the strip of qea_crop_pad_gather.
+ *   ch > 32: shrunk by ch / 32 in both axes by the exact area average, lengths in units of 1 / 32 source pixel: sw = ceil(32 cw / ch)
+ *   columns; row oy covers [oy ch, (oy + 1) ch), column j covers [j ch, (j + 1) ch) cut to [0, 32 cw); with the integer overlap lengths
+ *   wy(oy, r) with source row [32 r, 32 r + 32) and wx(j, c) likewise, S = sum wy wx p(y0 + r, x0 + c), Area = ch min(ch, 32 cw - j ch),
+ *   level = floor((2 S + Area) / (2 Area)) in 0..255, value norm[level]; the sw columns are centred in OW by the same rule.  Integers
+ *   throughout (64-bit where ch > 2048 needs them), so the result does not depend on any order of summation.
+ * No workspace, no atomics, nothing synchronises.  Refused before any launch: a NULL or misaligned pointer (out: 16 bytes), store_is_f32
+ * other than 0 / 1, n_pages < 1, store_elems < 1, n < 0 or n > QEA_WORD_STRIP_MAX_BOXES, OW not a multiple of 16 in
+ * QEA_WORD_STRIP_MIN_W..QEA_WORD_STRIP_MAX_W.  n = 0 is accepted and launches nothing.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects it by symbol.) */
+#define QEA_WORD_STRIP_H 32
+#define QEA_WORD_STRIP_MIN_W 64
+#define QEA_WORD_STRIP_MAX_W 512
+#define QEA_WORD_STRIP_MAX_BOXES (1 << 20)
+#define QEA_WORD_STRIP_MAX_SIDE 32767
+int qea_word_strips(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h,
+                    const int32_t* w, int32_t n_pages, const int32_t* boxes, int32_t n, int32_t OW, const float* norm, float* out,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

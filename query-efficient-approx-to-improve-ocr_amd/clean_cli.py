@@ -23,6 +23,17 @@ pixel of its component.
 --batch_pages group first go through ONE call of qea/deskew.py: deskew_pages (skew estimate from each page's Otsu ink, rotation about the
 page centre, white fill), so that the UNet or the binariser, and with them --boxes, see and describe the deskewed page that is written;
 a line "<stem>: slope a/1024" is printed per page.  Without the flag nothing changes.
+[new] --read CRNN_CHECKPOINT [--read_beam K [--read_lm PATH --read_lm_weight a --read_lm_bonus b | --read_lexicon PATH]] [--read_buckets
+W ...], with any method; implies --boxes: the word boxes of the WRITTEN pages of a --batch_pages group go through ONE call of
+qea/reading.py: read_pages (every box cut into a 32-row strip on the device, taller boxes shrunk by the exact area average; the strips
+through the eval-mode CRNN bucket by bucket; greedy, beam, n-gram-fused or lexicon-constrained decoding as in eval_crnn.py, with its
+exclusion rules) and "label" holds what the CRNN reads; with a beam "score" (the log-score the search ranked by) is added.  A line
+"<stem>: N words read, M cut" is printed per page (cut: wider than the last bucket).  Without the flag nothing changes: the same JSON
+bytes.
+
+    python clean_cli.py --deskew --method sauvola --boxes --read out/crnn/model_1_0.00 --in_dir scans --out_dir read
+
+is a complete OCR run, and the written folder loads as a labelled PatchDataset.
 """
 import json
 import os
@@ -30,7 +41,7 @@ import os
 import numpy as np
 import torch
 
-from qea import components, deskew
+from qea import components, deskew, reading
 from qea.binarize import binarize_pages, check_params
 from qea.pages import clean_pages
 from qea.trainer_core import hip_backend
@@ -53,6 +64,21 @@ class CleanPages:
         self.deskew_interp = getattr(args, "deskew_interp", "bilinear")
         if self.deskew:
             deskew.check_params(self.deskew_max_slope, min_gain=self.deskew_min_gain, interp=self.deskew_interp)
+        self.read_path = getattr(args, "read", None)
+        self.read_beam = int(getattr(args, "read_beam", 0) or 0)
+        self.read_lm_path, self.read_lexicon_path = getattr(args, "read_lm", None), getattr(args, "read_lexicon", None)
+        self.read_lm_weight, self.read_lm_bonus = float(getattr(args, "read_lm_weight", 1.0)), float(getattr(args, "read_lm_bonus", 0.0))
+        self.read_buckets = tuple(getattr(args, "read_buckets", None) or reading.default_buckets())
+        self.read_lm = self.read_lexicon = self.read_model = None
+        if self.read_path:
+            self.boxes = True
+            reading.check_params(self.read_buckets, beam=self.read_beam)
+            if self.read_lm_path and not self.read_beam:
+                raise ValueError("--read_lm needs --read_beam K: the model is fused into the prefix beam search")
+            if self.read_lexicon_path and (not self.read_beam or self.read_lm_path):
+                raise ValueError("--read_lexicon needs --read_beam K and cannot be combined with --read_lm")
+        elif self.read_beam or self.read_lm_path or self.read_lexicon_path or getattr(args, "read_buckets", None):
+            raise ValueError("--read_beam, --read_lm, --read_lexicon and --read_buckets need --read CRNN_CHECKPOINT")
         if self.despeckle:
             if self.method == "unet":
                 raise ValueError("--despeckle needs --method otsu or sauvola: the UNet's output is grey, and despeckling would binarise it")
@@ -64,6 +90,17 @@ class CleanPages:
         else:
             self.window, self.k = args.window, args.k
             check_params(self.method, self.window, self.k)
+        if self.read_path:
+            import properties
+            from utils import get_char_maps
+            self.read_model = torch.load(self.read_path, map_location=self.device, weights_only=False).to(self.device).eval()
+            char_to_index, self.index_to_char, _ = get_char_maps(properties.char_set)
+            if self.read_lm_path:
+                from qea.lm import CharLM
+                self.read_lm = CharLM.load(self.read_lm_path, char_to_index)
+            if self.read_lexicon_path:
+                from qea.lexicon import Lexicon
+                self.read_lexicon = Lexicon.load(self.read_lexicon_path, char_to_index)
         self.names = sorted(n for n in os.listdir(self.in_dir) if n.lower().endswith(EXTENSIONS))
         stems = [os.path.splitext(n)[0] for n in self.names]
         twice = sorted({s for s in stems if stems.count(s) > 1})
@@ -92,12 +129,26 @@ class CleanPages:
                 cleaned = binarize_pages(pages, self.method, window=self.window, k=self.k, out="u8", device=self.device,
                                          despeckle=self.despeckle)
             boxes = components.word_boxes(cleaned, gap_x=self.boxes_gap, min_area=self.boxes_min_area, device=self.device) if self.boxes else None
+            texts = scores = None
+            if self.read_model is not None:
+                texts, *scores, _ = reading.read_pages(self.read_model, cleaned, boxes, self.index_to_char, buckets=self.read_buckets,
+                                                       beam=self.read_beam, lm=self.read_lm, lm_weight=self.read_lm_weight,
+                                                       lm_bonus=self.read_lm_bonus, lexicon=self.read_lexicon)
+                table = reading.box_table(boxes)
+                plan = reading.strip_plan(table, [p.shape[-2] for p in cleaned], [p.shape[-1] for p in cleaned], self.read_buckets)
+                for n, t, m in zip(names, texts, np.bincount(table[plan.cut, 0], minlength=len(names)).tolist()):
+                    print(f"{os.path.splitext(n)[0]}: {len(t)} words read, {m} cut")
             for i, (n, page) in enumerate(zip(names, cleaned)):
                 path = os.path.join(self.out_dir, os.path.splitext(n)[0] + ".png")
                 Image.fromarray(page.cpu().numpy()).save(path)
                 written.append(path)
                 if boxes is not None:                          # x_max / y_max one past the last pixel: the crops' slicing convention
                     rows = [dict(label="", x_min=a, y_min=b, x_max=c + 1, y_max=d + 1) for a, b, c, d in boxes[i].cpu().tolist()]
+                    if texts is not None:
+                        for row, t in zip(rows, texts[i]):
+                            row["label"] = t
+                        for row, s in zip(rows, scores[0][i] if scores else []):
+                            row["score"] = s
                     with open(os.path.splitext(path)[0] + ".json", "w") as f:
                         json.dump(rows, f)
         print(f"{len(written)} pages cleaned into {self.out_dir}")

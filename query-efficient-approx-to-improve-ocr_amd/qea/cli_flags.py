@@ -203,6 +203,23 @@ FLAGS += [
     ("--deskew_interp", dict(choices=["bilinear", "nearest"], default="bilinear", help="[new] --deskew: how the rotation resamples"), "n"),
 ]
 
+# [new] reading the word boxes with the CRNN (qea/reading.py): the last stage of clean_cli.py's page pipeline
+FLAGS += [
+    ("--read", dict(metavar="CRNN_CHECKPOINT", help="[new] implies --boxes: cut every word box of the written page into a 32-row strip (taller "
+                                                    "boxes shrunk by the exact area average), read the strips with this CRNN (a whole-module "
+                                                    "checkpoint) and write what it reads as the boxes' labels; prints '<stem>: N words read, M "
+                                                    "cut' per page"), "n"),
+    ("--read_beam", dict(type=int, default=0, help="[new] --read: decode with a CTC prefix beam search of K entries (1..32) and also write each "
+                                                   "label's log-score; 0 = greedy"), "n"),
+    ("--read_lm", dict(help="[new] --read --read_beam K: fuse the character n-gram model of this file (written by lm_cli.py) into the search"), "n"),
+    ("--read_lm_weight", dict(type=float, default=1.0, help="[new] --read_lm: weight of the model's log-probabilities"), "n"),
+    ("--read_lm_bonus", dict(type=float, default=0.0, help="[new] --read_lm: bonus per character"), "n"),
+    ("--read_lexicon", dict(help="[new] --read --read_beam K: keep the search inside the word list of this file (written by lexicon_cli.py).  Not "
+                                 "together with --read_lm"), "n"),
+    ("--read_buckets", dict(type=int, nargs="+", metavar="W", help="[new] --read: the strip widths, ascending multiples of 16 in 64..512 "
+                                                                   "(default 128 256 384 512); a word wider than the last loses its sides"), "n"),
+]
+
 
 def build_parser(which, description):
     import argparse

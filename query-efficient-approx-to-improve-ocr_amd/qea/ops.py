@@ -1418,3 +1418,36 @@ def deskew_rotate(store, table, slopes, rot_table, interp="bilinear", fill=255, 
                                             int(interp == "nearest"), int(fill), _ptr(norm), _ptr(out_f32), _ptr(out_u8), _stream()),
                "qea_deskew_rotate")
     DESKEW_LAUNCHES["rotate"] += 1
+
+
+# QEA_WORD_STRIP_* of include/qea_hip.h
+WORD_STRIP_H, WORD_STRIP_MIN_W, WORD_STRIP_MAX_W, WORD_STRIP_MAX_BOXES, WORD_STRIP_MAX_SIDE = 32, 64, 512, 1 << 20, 32767
+WORD_STRIP_LAUNCHES = {"strips": 0}          # launches of csrc/word_strips.hip issued through this module (tests, tools)
+
+
+def word_strips(store, table, boxes, OW, norm, out=None):
+    """include/qea_hip.h: qea_word_strips — the packed `store` (uint8 or fp32; `table`: binarize_page_table), boxes int32 [n][5] =
+    (page, x0, y0, x1, y1) on the device with x1 / y1 exclusive, and norm, the 256 fp32 values a grey level is written as -> out
+    [n, 1, 32, OW] fp32, written whole by ONE launch on the current stream: every box clipped to its page, copied 1:1 where it has at
+    most 32 rows, shrunk to 32 rows by the exact area average where it has more, centred in OW on a white ground."""
+    if not torch.is_tensor(store) or store.dtype not in (torch.uint8, torch.float32) or store.dim() != 1 or not store.is_cuda:
+        raise _lib.QeaError("word_strips needs a one-dimensional uint8 or float32 CUDA store")
+    if table.words.device != store.device:
+        raise _lib.QeaError(f"word_strips: the page table is on {table.words.device}, the store on {store.device}")
+    if not torch.is_tensor(boxes) or boxes.dim() != 2 or boxes.shape[1] != 5:
+        raise _lib.QeaError("word_strips: boxes must be an int32 [n][5] tensor = (page, x0, y0, x1, y1)")
+    n, OW = boxes.shape[0], int(OW)
+    if OW % 16 or not WORD_STRIP_MIN_W <= OW <= WORD_STRIP_MAX_W:
+        raise _lib.QeaError(f"word_strips: OW={OW} must be a multiple of 16 in {WORD_STRIP_MIN_W}..{WORD_STRIP_MAX_W}")
+    if out is None:
+        out = torch.empty(n, 1, WORD_STRIP_H, OW, dtype=torch.float32, device=store.device)
+    if out.dim() != 4 or tuple(out.shape[:3]) != (n, 1, WORD_STRIP_H) or out.shape[3] != OW:
+        raise _lib.QeaError(f"word_strips: out {tuple(out.shape)} for {n} boxes at width {OW}")
+    store_p, boxes_p, norm_p, out_p = _tensors("word_strips", store.device, ("store", store, store.dtype), ("boxes", boxes, torch.int32),
+                                               ("norm", norm, torch.float32, 256), ("out", out, torch.float32))
+    if n == 0:                                                 # nothing to write, and an empty tensor has no pointer to hand over
+        return out
+    _lib.check(_lib.lib().qea_word_strips(store_p, int(store.dtype == torch.float32), store.numel(), table.offset, table.h, table.w, table.n,
+                                          boxes_p, n, OW, norm_p, out_p, _stream()), "qea_word_strips")
+    WORD_STRIP_LAUNCHES["strips"] += 1
+    return out
