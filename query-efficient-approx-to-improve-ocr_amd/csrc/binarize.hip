@@ -1,12 +1,12 @@
 // Classic binarisers over the packed page store, bit for bit the statement tests/binarize_spec.py (include/qea_hip.h: qea_binarize_sauvola,
 // qea_otsu_histogram, qea_binarize_otsu; qea/binarize.py: binarize_pages, whose host path is the same statement in numpy).
 //
-// A pixel is its 8-bit value v (an fp32 store is read through the project's 8-bit rule, csrc/page_store.h: to_u8); ink is foreground and is
-// written as 0 / 0.0, background as 255 / 1.0, into outputs packed like the store.  Every sum is an integer, so no order of summation
+// A pixel is its 8-bit value v (csrc/page_store.h: value_of); ink is foreground and is written as 0 / 0.0, background as 255 / 1.0, into
+// outputs packed like the store (put_ink).  Every sum is an integer, so no order of summation
 // matters; the two decisions are fp64 products and one subtraction, compiled without fused multiply-adds.
 //
-// sauvola_kernel: ONE launch for all pages.  Workgroup b owns one TH x TW output tile of one page: tile_first[p] <= b < tile_first[p + 1]
-// names the page (binary search over the uniform prefix table), b - tile_first[p] the tile, row after row.  With r = win / 2 the LDS plan is
+// sauvola_kernel: ONE launch for all pages.  Workgroup b owns one TH x TW output tile of one page (csrc/page_store.h: tile_of_block).
+// With r = win / 2 the LDS plan is
 //     px  [TH + 2r][PB] bytes       the tile and its halo, 0 outside the page; PB = the row length rounded up to 4 with PB / 4 odd
 //     H1  [TH + 2r][TW + 1] uint32  sums of v over the win columns around each of the tile's columns (<= 127 * 255)
 //     H2  [TH + 2r][TW + 1] uint32  sums of v * v (<= 127 * 65025)
@@ -37,24 +37,6 @@ __host__ __device__ constexpr int byte_pitch(int win) { return (((TW + win - 1 +
 __host__ __device__ constexpr int sauvola_lds_bytes(int win) { return (TH + win - 1) * (byte_pitch(win) + 2 * HP * 4); }
 static_assert(sauvola_lds_bytes(QEA_BINARIZE_MAX_WINDOW) <= 160 * 1024, "the plan must fit the CU's LDS at the largest window");
 
-__device__ __forceinline__ uint8_t pixel_of(const uint8_t* __restrict__ s, long long i) { return s[i]; }
-__device__ __forceinline__ uint8_t pixel_of(const float* __restrict__ s, long long i) { return to_u8(s[i]); }
-
-// largest p in [0, n_pages) with first[p] <= b (first[0] = 0): uniform over the workgroup
-__device__ __forceinline__ int page_of_block(const int32_t* __restrict__ first, int n_pages, int b) {
-  int lo = 0, hi = n_pages;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (first[mid] <= b) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ void put(float* __restrict__ out_f32, uint8_t* __restrict__ out_u8, long long i, bool fg) {
-  if (out_f32) out_f32[i] = fg ? 0.f : 1.f;
-  if (out_u8) out_u8[i] = fg ? 0 : 255;
-}
-
 // The statement's rule: foreground iff v <= m (1 + k (s / R - 1)), without sqrt or division, every operation rounded as written.
 __device__ __forceinline__ bool sauvola_foreground(int n, int v, unsigned S1, unsigned S2, double k, double R) {
 #pragma clang fp contract(off)
@@ -66,8 +48,7 @@ __device__ __forceinline__ bool sauvola_foreground(int n, int v, unsigned S1, un
 }
 
 template <typename T>
-__global__ __launch_bounds__(THREADS) void sauvola_kernel(const T* __restrict__ store, long long store_elems, const int64_t* __restrict__ offset,
-                                                          const int32_t* __restrict__ h, const int32_t* __restrict__ w, int n_pages,
+__global__ __launch_bounds__(THREADS) void sauvola_kernel(const T* __restrict__ store, const PageStore ps,
                                                           const int32_t* __restrict__ tile_first, int win, double k, double R,
                                                           float* __restrict__ out_f32, uint8_t* __restrict__ out_u8) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -77,18 +58,17 @@ __global__ __launch_bounds__(THREADS) void sauvola_kernel(const T* __restrict__ 
   unsigned* const H2 = H1 + SH * HP;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
-  const int p = page_of_block(tile_first, n_pages, blockIdx.x);
-  const Page g = page_of(p, offset, h, w, n_pages, store_elems);
-  const int t = (int)blockIdx.x - tile_first[p], tiles_x = (g.w + TW - 1) / TW;
-  if (g.h == 0 || t < 0 || t / tiles_x >= (g.h + TH - 1) / TH) return;     // uniform
-  const int ty0 = t / tiles_x * TH, tx0 = t % tiles_x * TW;
+  const Tile t = tile_of_block(ps, tile_first, TH, TW);
+  if (t.g.h == 0) return;                                      // uniform
+  const Page g = t.g;
+  const int ty0 = t.y0, tx0 = t.x0;
 
   for (int sy = wave; sy < SH; sy += 4) {
     const int py = ty0 - r + sy;
     const bool row_in = py >= 0 && py < g.h;
     for (int sx = lane; sx < SW; sx += 64) {
       const int qx = tx0 - r + sx;
-      px[sy * PB + sx] = row_in && qx >= 0 && qx < g.w ? pixel_of(store, g.off + (long long)py * g.w + qx) : (uint8_t)0;
+      px[sy * PB + sx] = row_in && qx >= 0 && qx < g.w ? (uint8_t)value_of(store[g.off + (long long)py * g.w + qx]) : (uint8_t)0;
     }
   }
   __syncthreads();
@@ -127,7 +107,7 @@ __global__ __launch_bounds__(THREADS) void sauvola_kernel(const T* __restrict__ 
     const int py = ty0 + y;
     if (py < g.h && qx < g.w) {
       const int n = nx * (min(py + r, g.h - 1) - max(py - r, 0) + 1);
-      put(out_f32, out_u8, g.off + (long long)py * g.w + qx, sauvola_foreground(n, px[(y + r) * PB + lane + r], S1, S2, k, R));
+      put_ink(out_f32, out_u8, g.off + (long long)py * g.w + qx, sauvola_foreground(n, px[(y + r) * PB + lane + r], S1, S2, k, R));
     }
     if (y == y0 + 7) break;
     S1 += H1[(y + win) * HP + lane] - H1[y * HP + lane];
@@ -141,11 +121,10 @@ struct Chunk {
   long long begin, end;      // elements of the page this workgroup owns; begin >= end: nothing
 };
 
-__device__ __forceinline__ Chunk chunk_of_block(const int64_t* __restrict__ offset, const int32_t* __restrict__ h, const int32_t* __restrict__ w,
-                                                int n_pages, long long store_elems, const int32_t* __restrict__ chunk_first) {
+__device__ __forceinline__ Chunk chunk_of_block(const PageStore& ps, const int32_t* __restrict__ chunk_first) {
   Chunk c;
-  c.page = page_of_block(chunk_first, n_pages, blockIdx.x);
-  c.g = page_of(c.page, offset, h, w, n_pages, store_elems);
+  c.page = page_of_block(chunk_first, ps.n_pages, blockIdx.x);
+  c.g = page_of(ps, c.page);
   const long long size = (long long)c.g.h * c.g.w, at = (long long)((int)blockIdx.x - chunk_first[c.page]) * CHUNK;
   c.begin = at < 0 ? size : at;
   c.end = min(size, c.begin + CHUNK);
@@ -153,17 +132,15 @@ __device__ __forceinline__ Chunk chunk_of_block(const int64_t* __restrict__ offs
 }
 
 template <typename T>
-__global__ __launch_bounds__(THREADS) void otsu_histogram_kernel(const T* __restrict__ store, long long store_elems,
-                                                                 const int64_t* __restrict__ offset, const int32_t* __restrict__ h,
-                                                                 const int32_t* __restrict__ w, int n_pages,
+__global__ __launch_bounds__(THREADS) void otsu_histogram_kernel(const T* __restrict__ store, const PageStore ps,
                                                                  const int32_t* __restrict__ chunk_first, unsigned* __restrict__ hist) {
   __shared__ unsigned bins[4][256];
-  const Chunk c = chunk_of_block(offset, h, w, n_pages, store_elems, chunk_first);
+  const Chunk c = chunk_of_block(ps, chunk_first);
   if (c.begin >= c.end) return;                                // uniform
   for (int i = threadIdx.x; i < 4 * 256; i += THREADS) (&bins[0][0])[i] = 0;
   __syncthreads();
   unsigned* mine = bins[threadIdx.x >> 6];
-  for (long long i = c.begin + threadIdx.x; i < c.end; i += THREADS) atomicAdd(&mine[pixel_of(store, c.g.off + i)], 1u);
+  for (long long i = c.begin + threadIdx.x; i < c.end; i += THREADS) atomicAdd(&mine[value_of(store[c.g.off + i])], 1u);
   __syncthreads();
   const unsigned n = bins[0][threadIdx.x] + bins[1][threadIdx.x] + bins[2][threadIdx.x] + bins[3][threadIdx.x];
   if (n) atomicAdd(&hist[(long long)c.page * 256 + threadIdx.x], n);
@@ -210,43 +187,16 @@ __device__ __forceinline__ int otsu_threshold(unsigned bin) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(THREADS) void otsu_apply_kernel(const T* __restrict__ store, long long store_elems, const int64_t* __restrict__ offset,
-                                                             const int32_t* __restrict__ h, const int32_t* __restrict__ w, int n_pages,
+__global__ __launch_bounds__(THREADS) void otsu_apply_kernel(const T* __restrict__ store, const PageStore ps,
                                                              const int32_t* __restrict__ chunk_first, const unsigned* __restrict__ hist,
                                                              float* __restrict__ out_f32, uint8_t* __restrict__ out_u8,
                                                              int32_t* __restrict__ thresholds) {
-  const Chunk c = chunk_of_block(offset, h, w, n_pages, store_elems, chunk_first);
+  const Chunk c = chunk_of_block(ps, chunk_first);
   if (c.begin >= c.end) return;                                // uniform
   const int ts = otsu_threshold(hist[(long long)c.page * 256 + threadIdx.x]);
   if (c.begin == 0 && threadIdx.x == 0) thresholds[c.page] = ts;
   for (long long i = c.begin + threadIdx.x; i < c.end; i += THREADS)
-    put(out_f32, out_u8, c.g.off + i, (int)pixel_of(store, c.g.off + i) <= ts);
-}
-
-// What the three entry points check alike; -> the number of tiles (Sauvola) or chunks (Otsu) of all pages in *blocks.
-int check_pages(const char* who, const void* store, int store_is_f32, long long store_elems, const void* offset, const void* h, const void* w,
-                int n_pages, const int32_t* host_h, const int32_t* host_w, const void* first, bool tiles, long long* blocks) {
-  QEA_REQUIRE(store && offset && h && w && host_h && host_w && first, "%s: null pointer", who);
-  QEA_REQUIRE(store_is_f32 == 0 || store_is_f32 == 1, "%s: store_is_f32=%d is neither 0 nor 1", who, store_is_f32);
-  QEA_REQUIRE(!store_is_f32 || ((uintptr_t)store & 3) == 0, "%s: an fp32 store must be 4-byte aligned", who);
-  QEA_REQUIRE(n_pages >= 1 && n_pages <= (1 << 24), "%s: n_pages=%d outside 1..2^24", who, n_pages);
-  QEA_REQUIRE(store_elems >= 1, "%s: store_elems=%lld", who, store_elems);
-  long long total = 0;
-  for (int p = 0; p < n_pages; ++p) {
-    const long long ph = host_h[p], pw = host_w[p];
-    QEA_REQUIRE(ph >= 1 && pw >= 1, "%s: page %d is empty (%lld x %lld)", who, p, ph, pw);
-    QEA_REQUIRE(ph * pw <= QEA_BINARIZE_MAX_PAGE_PIXELS, "%s: page %d has %lld x %lld pixels, more than 2^27", who, p, ph, pw);
-    total += tiles ? ((ph + TH - 1) / TH) * ((pw + TW - 1) / TW) : (ph * pw + CHUNK - 1) / CHUNK;
-  }
-  QEA_REQUIRE(total <= 0x7fffffffll, "%s: %lld workgroups, more than 2^31 - 1", who, total);
-  *blocks = total;
-  return QEA_OK;
-}
-
-int check_outputs(const char* who, const void* out_f32, const void* out_u8) {
-  QEA_REQUIRE(out_f32 || out_u8, "%s: neither an fp32 nor an 8-bit output", who);
-  QEA_REQUIRE(((uintptr_t)out_f32 & 3) == 0, "%s: out_f32 must be 4-byte aligned", who);
-  return QEA_OK;
+    put_ink(out_f32, out_u8, c.g.off + i, value_of(store[c.g.off + i]) <= ts);
 }
 
 }  // namespace
@@ -255,24 +205,24 @@ extern "C" int qea_binarize_sauvola(const void* store, int32_t store_is_f32, int
                                     const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first,
                                     int32_t win, double k, double R, float* out_f32, uint8_t* out_u8, void* stream) {
   const char* who = "qea_binarize_sauvola";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
   long long blocks = 0;
-  if (int rc = check_pages(who, store, store_is_f32, store_elems, offset, h, w, n_pages, host_h, host_w, tile_first, true, &blocks)) return rc;
+  if (int rc = check_paged_launch(who, store, store_is_f32, ps, host_h, host_w, tile_first, true, &blocks)) return rc;
   if (int rc = check_outputs(who, out_f32, out_u8)) return rc;
   QEA_REQUIRE(win >= 3 && win <= QEA_BINARIZE_MAX_WINDOW && win % 2 == 1, "%s: window %d must be odd and in 3..%d", who, win,
               QEA_BINARIZE_MAX_WINDOW);
   QEA_REQUIRE(k > 0.0 && k < 1.0, "%s: k=%g must lie strictly between 0 and 1", who, k);       // false for NaN
   QEA_REQUIRE(R > 0.0 && R <= 1.7976931348623157e308, "%s: R=%g must be positive and finite", who, R);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t lds = sauvola_lds_bytes(win);
-  if (store_is_f32) {
-    if (int rc = reserve_lds<sauvola_kernel<float>>(who, sauvola_lds_bytes(QEA_BINARIZE_MAX_WINDOW))) return rc;
-    sauvola_kernel<float><<<dim3((unsigned)blocks), dim3(THREADS), lds, s>>>((const float*)store, (long long)store_elems, offset, h, w, n_pages,
-                                                                            tile_first, win, k, R, out_f32, out_u8);
-  } else {
-    if (int rc = reserve_lds<sauvola_kernel<uint8_t>>(who, sauvola_lds_bytes(QEA_BINARIZE_MAX_WINDOW))) return rc;
-    sauvola_kernel<uint8_t><<<dim3((unsigned)blocks), dim3(THREADS), lds, s>>>((const uint8_t*)store, (long long)store_elems, offset, h, w,
-                                                                              n_pages, tile_first, win, k, R, out_f32, out_u8);
-  }
+  const int reserved = dispatch_store(store_is_f32, store, [&](auto* typed) {
+    // reserve_lds takes the kernel as a template argument, so the instance needs a constant name: the call alone would not pick it
+    constexpr auto kernel = sauvola_kernel<StoreElem<decltype(typed)>>;
+    const int rc = reserve_lds<kernel>(who, sauvola_lds_bytes(QEA_BINARIZE_MAX_WINDOW));
+    if (rc == QEA_OK)
+      kernel<<<dim3((unsigned)blocks), dim3(THREADS), sauvola_lds_bytes(win), (hipStream_t)stream>>>(typed, ps, tile_first, win, k, R, out_f32,
+                                                                                                    out_u8);
+    return rc;
+  });
+  if (reserved != QEA_OK) return reserved;
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -281,20 +231,18 @@ extern "C" int qea_otsu_histogram(const void* store, int32_t store_is_f32, int64
                                   const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* chunk_first,
                                   uint32_t* hist, void* stream) {
   const char* who = "qea_otsu_histogram";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
   long long blocks = 0;
-  if (int rc = check_pages(who, store, store_is_f32, store_elems, offset, h, w, n_pages, host_h, host_w, chunk_first, false, &blocks)) return rc;
+  if (int rc = check_paged_launch(who, store, store_is_f32, ps, host_h, host_w, chunk_first, false, &blocks)) return rc;
   QEA_REQUIRE(hist && ((uintptr_t)hist & 3) == 0, "%s: hist must be a 4-byte aligned table of n_pages x 256 counts", who);
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(hist, 0, (size_t)n_pages * 256 * sizeof(uint32_t), s) != hipSuccess) {
     qea_set_error("%s: cannot zero the histogram table", who);
     return QEA_ERR_LAUNCH;
   }
-  if (store_is_f32)
-    otsu_histogram_kernel<float><<<dim3((unsigned)blocks), dim3(THREADS), 0, s>>>((const float*)store, (long long)store_elems, offset, h, w,
-                                                                                 n_pages, chunk_first, hist);
-  else
-    otsu_histogram_kernel<uint8_t><<<dim3((unsigned)blocks), dim3(THREADS), 0, s>>>((const uint8_t*)store, (long long)store_elems, offset, h, w,
-                                                                                   n_pages, chunk_first, hist);
+  dispatch_store(store_is_f32, store, [&](auto* typed) {
+    otsu_histogram_kernel<<<dim3((unsigned)blocks), dim3(THREADS), 0, s>>>(typed, ps, chunk_first, hist);
+  });
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -303,18 +251,16 @@ extern "C" int qea_binarize_otsu(const void* store, int32_t store_is_f32, int64_
                                  const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* chunk_first,
                                  const uint32_t* hist, float* out_f32, uint8_t* out_u8, int32_t* thresholds, void* stream) {
   const char* who = "qea_binarize_otsu";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
   long long blocks = 0;
-  if (int rc = check_pages(who, store, store_is_f32, store_elems, offset, h, w, n_pages, host_h, host_w, chunk_first, false, &blocks)) return rc;
+  if (int rc = check_paged_launch(who, store, store_is_f32, ps, host_h, host_w, chunk_first, false, &blocks)) return rc;
   if (int rc = check_outputs(who, out_f32, out_u8)) return rc;
   QEA_REQUIRE(hist && ((uintptr_t)hist & 3) == 0, "%s: hist must be the 4-byte aligned table qea_otsu_histogram filled", who);
   QEA_REQUIRE(thresholds && ((uintptr_t)thresholds & 3) == 0, "%s: thresholds must be a 4-byte aligned array of n_pages values", who);
-  hipStream_t s = (hipStream_t)stream;
-  if (store_is_f32)
-    otsu_apply_kernel<float><<<dim3((unsigned)blocks), dim3(THREADS), 0, s>>>((const float*)store, (long long)store_elems, offset, h, w, n_pages,
-                                                                             chunk_first, hist, out_f32, out_u8, thresholds);
-  else
-    otsu_apply_kernel<uint8_t><<<dim3((unsigned)blocks), dim3(THREADS), 0, s>>>((const uint8_t*)store, (long long)store_elems, offset, h, w,
-                                                                               n_pages, chunk_first, hist, out_f32, out_u8, thresholds);
+  dispatch_store(store_is_f32, store, [&](auto* typed) {
+    otsu_apply_kernel<<<dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream>>>(typed, ps, chunk_first, hist, out_f32, out_u8,
+                                                                                         thresholds);
+  });
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

@@ -2,11 +2,11 @@
 // qea_cc_label, qea_cc_stats, qea_cc_despeckle, qea_cc_smear, qea_cc_boxes; qea/components.py is the product interface, whose host path is
 // the same statement in numpy).
 //
-// A pixel is ink iff its 8-bit value (csrc/page_store.h: to_u8 for an fp32 store) is <= ink_max, or, when a uint8 ink mask packed like the
+// A pixel is ink iff its 8-bit value (csrc/page_store.h: ink_of) is <= ink_max, or, when a uint8 ink mask packed like the
 // store is given, iff its mask byte is not 0.  The label of an ink pixel is the smallest row-major index y * w + x WITHIN ITS PAGE over the
 // pixels of its component, background is -1: one labelling, whatever the order in which workgroups run.  `labels` and `area` are int32
 // arrays packed like the store; what lies between the pages is never written.  Every kernel but the border kernel gives workgroup b one
-// TH x TW tile of one page through the tile_first prefix table of csrc/binarize.hip (QEA_BINARIZE_TILE_H / _W).
+// TH x TW tile of one page through the tile_first prefix table (csrc/page_store.h: tile_of_block; QEA_BINARIZE_TILE_H / _W).
 //
 // qea_cc_label, three launches:
 //   tile_kernel     the tile's pixels become a union-find forest in LDS (L[i] = i for ink, -1 otherwise); every ink pixel is united with
@@ -50,40 +50,6 @@ constexpr int SMEAR_LDS = (TH + 2 * MAX_GAP) * TW > TH * (TW + 2 * MAX_GAP) ? (T
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 #define RLX_GROUP __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
 
-__device__ __forceinline__ int page_of_block(const int32_t* __restrict__ first, int n_pages, int b) {
-  int lo = 0, hi = n_pages;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (first[mid] <= b) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-struct Tile {
-  Page g;
-  int page, y0, x0;     // g.h == 0: nothing to do (uniform over the workgroup)
-};
-
-__device__ __forceinline__ Tile tile_of_block(const int64_t* __restrict__ offset, const int32_t* __restrict__ h, const int32_t* __restrict__ w,
-                                              int n_pages, long long store_elems, const int32_t* __restrict__ tile_first) {
-  Tile t;
-  t.page = page_of_block(tile_first, n_pages, blockIdx.x);
-  t.g = page_of(t.page, offset, h, w, n_pages, store_elems);
-  t.y0 = t.x0 = 0;
-  if (t.g.h == 0) return t;
-  const int i = (int)blockIdx.x - tile_first[t.page], tiles_x = (t.g.w + TW - 1) / TW;
-  if (i < 0 || i / tiles_x >= (t.g.h + TH - 1) / TH) {
-    t.g.h = 0;
-    return t;
-  }
-  t.y0 = i / tiles_x * TH;
-  t.x0 = i % tiles_x * TW;
-  return t;
-}
-
-__device__ __forceinline__ bool ink_of(const uint8_t* __restrict__ s, long long i, int ink_max) { return (int)s[i] <= ink_max; }
-__device__ __forceinline__ bool ink_of(const float* __restrict__ s, long long i, int ink_max) { return (int)to_u8(s[i]) <= ink_max; }
-
 // ---- the union-find, once for a tile in LDS (workgroup scope) and once for a page in global memory (agent scope)
 struct LdsForest {
   int* L;
@@ -123,12 +89,11 @@ __device__ __forceinline__ void unite(const F f, int a, int b) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(THREADS) void cc_tile_kernel(const T* __restrict__ store, long long store_elems, const int64_t* __restrict__ offset,
-                                                          const int32_t* __restrict__ h, const int32_t* __restrict__ w, int n_pages,
+__global__ __launch_bounds__(THREADS) void cc_tile_kernel(const T* __restrict__ store, const PageStore ps,
                                                           const int32_t* __restrict__ tile_first, const uint8_t* __restrict__ ink_mask,
                                                           int ink_max, int conn8, int32_t* __restrict__ labels, int32_t* __restrict__ area) {
   __shared__ int L[TILE];
-  const Tile t = tile_of_block(offset, h, w, n_pages, store_elems, tile_first);
+  const Tile t = tile_of_block(ps, tile_first, TH, TW);
   if (t.g.h == 0) return;                                      // uniform
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int px = t.x0 + lane;
@@ -171,10 +136,9 @@ __global__ __launch_bounds__(THREADS) void cc_tile_kernel(const T* __restrict__ 
 }
 
 // one workgroup per tile: threads 0..63 own the pixels of its bottom row, threads 64..95 those of its right column
-__global__ __launch_bounds__(EDGE_THREADS) void cc_border_kernel(const int64_t* __restrict__ offset, const int32_t* __restrict__ h,
-                                                                 const int32_t* __restrict__ w, int n_pages, long long store_elems,
-                                                                 const int32_t* __restrict__ tile_first, int conn8, int32_t* labels) {
-  const Tile t = tile_of_block(offset, h, w, n_pages, store_elems, tile_first);
+__global__ __launch_bounds__(EDGE_THREADS) void cc_border_kernel(const PageStore ps, const int32_t* __restrict__ tile_first, int conn8,
+                                                                 int32_t* labels) {
+  const Tile t = tile_of_block(ps, tile_first, TH, TW);
   if (t.g.h == 0) return;
   const int k = threadIdx.x, W = t.g.w, H = t.g.h;
   const PageForest f = {labels + t.g.off};
@@ -197,10 +161,8 @@ __global__ __launch_bounds__(EDGE_THREADS) void cc_border_kernel(const int64_t* 
   }
 }
 
-__global__ __launch_bounds__(THREADS) void cc_flatten_kernel(const int64_t* __restrict__ offset, const int32_t* __restrict__ h,
-                                                             const int32_t* __restrict__ w, int n_pages, long long store_elems,
-                                                             const int32_t* __restrict__ tile_first, int32_t* labels) {
-  const Tile t = tile_of_block(offset, h, w, n_pages, store_elems, tile_first);
+__global__ __launch_bounds__(THREADS) void cc_flatten_kernel(const PageStore ps, const int32_t* __restrict__ tile_first, int32_t* labels) {
+  const Tile t = tile_of_block(ps, tile_first, TH, TW);
   if (t.g.h == 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, px = t.x0 + lane;
   // Other threads of this launch replace labels by their roots meanwhile: a walk meets old parents or new roots, members of the same
@@ -235,12 +197,10 @@ __device__ __forceinline__ int label_at(const int32_t* __restrict__ labels, cons
   return l >= 0 && l < g.h * g.w ? l : -1;
 }
 
-__global__ __launch_bounds__(THREADS) void cc_stats_kernel(const int64_t* __restrict__ offset, const int32_t* __restrict__ h,
-                                                           const int32_t* __restrict__ w, int n_pages, long long store_elems,
-                                                           const int32_t* __restrict__ tile_first, const int32_t* __restrict__ labels,
-                                                           int32_t* __restrict__ area) {
+__global__ __launch_bounds__(THREADS) void cc_stats_kernel(const PageStore ps, const int32_t* __restrict__ tile_first,
+                                                           const int32_t* __restrict__ labels, int32_t* __restrict__ area) {
   __shared__ int keys[SLOTS], count[SLOTS];
-  const Tile t = tile_of_block(offset, h, w, n_pages, store_elems, tile_first);
+  const Tile t = tile_of_block(ps, tile_first, TH, TW);
   if (t.g.h == 0) return;
   for (int s = threadIdx.x; s < SLOTS; s += THREADS) {
     keys[s] = -1;
@@ -267,12 +227,10 @@ __global__ __launch_bounds__(THREADS) void cc_stats_kernel(const int64_t* __rest
     if (keys[s] >= 0) atomicAdd(&area[t.g.off + keys[s]], count[s]);
 }
 
-__global__ __launch_bounds__(THREADS) void cc_despeckle_kernel(const int64_t* __restrict__ offset, const int32_t* __restrict__ h,
-                                                               const int32_t* __restrict__ w, int n_pages, long long store_elems,
-                                                               const int32_t* __restrict__ tile_first, const int32_t* __restrict__ labels,
-                                                               const int32_t* __restrict__ area, int min_area, float* __restrict__ out_f32,
-                                                               uint8_t* __restrict__ out_u8) {
-  const Tile t = tile_of_block(offset, h, w, n_pages, store_elems, tile_first);
+__global__ __launch_bounds__(THREADS) void cc_despeckle_kernel(const PageStore ps, const int32_t* __restrict__ tile_first,
+                                                               const int32_t* __restrict__ labels, const int32_t* __restrict__ area,
+                                                               int min_area, float* __restrict__ out_f32, uint8_t* __restrict__ out_u8) {
+  const Tile t = tile_of_block(ps, tile_first, TH, TW);
   if (t.g.h == 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, px = t.x0 + lane;
 #pragma unroll
@@ -281,19 +239,16 @@ __global__ __launch_bounds__(THREADS) void cc_despeckle_kernel(const int64_t* __
     if (py >= t.g.h || px >= t.g.w) continue;
     const int l = label_at(labels, t.g, py, px);
     const bool keep = l >= 0 && area[t.g.off + l] >= min_area;
-    const long long at = t.g.off + (long long)py * t.g.w + px;
-    if (out_f32) out_f32[at] = keep ? 0.f : 1.f;
-    if (out_u8) out_u8[at] = keep ? 0 : 255;
+    put_ink(out_f32, out_u8, t.g.off + (long long)py * t.g.w + px, keep);
   }
 }
 
 template <typename T>
-__global__ __launch_bounds__(THREADS) void cc_smear_kernel(const T* __restrict__ store, long long store_elems, const int64_t* __restrict__ offset,
-                                                           const int32_t* __restrict__ h, const int32_t* __restrict__ w, int n_pages,
+__global__ __launch_bounds__(THREADS) void cc_smear_kernel(const T* __restrict__ store, const PageStore ps,
                                                            const int32_t* __restrict__ tile_first, const uint8_t* __restrict__ in_mask,
                                                            int ink_max, int gap, int vertical, uint8_t* __restrict__ out_mask) {
   __shared__ uint8_t px[SMEAR_LDS];
-  const Tile t = tile_of_block(offset, h, w, n_pages, store_elems, tile_first);
+  const Tile t = tile_of_block(ps, tile_first, TH, TW);
   if (t.g.h == 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gy = vertical ? gap : 0, gx = vertical ? 0 : gap, SH = TH + 2 * gy, SW = TW + 2 * gx;     // SH * SW <= SMEAR_LDS
@@ -337,13 +292,11 @@ __global__ __launch_bounds__(THREADS) void cc_smear_kernel(const T* __restrict__
   }
 }
 
-__global__ __launch_bounds__(THREADS) void cc_boxes_kernel(const int64_t* __restrict__ offset, const int32_t* __restrict__ h,
-                                                           const int32_t* __restrict__ w, int n_pages, long long store_elems,
-                                                           const int32_t* __restrict__ tile_first, const int32_t* __restrict__ labels,
-                                                           const int32_t* __restrict__ roots, const int32_t* __restrict__ root_first,
-                                                           int n_roots, int32_t* __restrict__ boxes) {
+__global__ __launch_bounds__(THREADS) void cc_boxes_kernel(const PageStore ps, const int32_t* __restrict__ tile_first,
+                                                           const int32_t* __restrict__ labels, const int32_t* __restrict__ roots,
+                                                           const int32_t* __restrict__ root_first, int n_roots, int32_t* __restrict__ boxes) {
   __shared__ int keys[SLOTS], lo_x[SLOTS], lo_y[SLOTS], hi_x[SLOTS], hi_y[SLOTS];
-  const Tile t = tile_of_block(offset, h, w, n_pages, store_elems, tile_first);
+  const Tile t = tile_of_block(ps, tile_first, TH, TW);
   if (t.g.h == 0) return;
   for (int s = threadIdx.x; s < SLOTS; s += THREADS) {
     keys[s] = -1;
@@ -388,26 +341,6 @@ __global__ __launch_bounds__(THREADS) void cc_boxes_kernel(const int64_t* __rest
   }
 }
 
-// What the five entry points check alike; -> the number of tiles of all pages in *blocks.
-int check_pages(const char* who, const void* store, int store_is_f32, long long store_elems, const void* offset, const void* h, const void* w,
-                int n_pages, const int32_t* host_h, const int32_t* host_w, const void* tile_first, long long* blocks) {
-  QEA_REQUIRE(store && offset && h && w && host_h && host_w && tile_first, "%s: null pointer", who);
-  QEA_REQUIRE(store_is_f32 == 0 || store_is_f32 == 1, "%s: store_is_f32=%d is neither 0 nor 1", who, store_is_f32);
-  QEA_REQUIRE(!store_is_f32 || ((uintptr_t)store & 3) == 0, "%s: an fp32 store must be 4-byte aligned", who);
-  QEA_REQUIRE(n_pages >= 1 && n_pages <= (1 << 24), "%s: n_pages=%d outside 1..2^24", who, n_pages);
-  QEA_REQUIRE(store_elems >= 1, "%s: store_elems=%lld", who, store_elems);
-  long long total = 0;
-  for (int p = 0; p < n_pages; ++p) {
-    const long long ph = host_h[p], pw = host_w[p];
-    QEA_REQUIRE(ph >= 1 && pw >= 1, "%s: page %d is empty (%lld x %lld)", who, p, ph, pw);
-    QEA_REQUIRE(ph * pw <= QEA_BINARIZE_MAX_PAGE_PIXELS, "%s: page %d has %lld x %lld pixels, more than 2^27", who, p, ph, pw);
-    total += ((ph + TH - 1) / TH) * ((pw + TW - 1) / TW);
-  }
-  QEA_REQUIRE(total <= 0x7fffffffll, "%s: %lld workgroups, more than 2^31 - 1", who, total);
-  *blocks = total;
-  return QEA_OK;
-}
-
 int check_words(const char* who, const char* name, const void* p, bool required) {
   QEA_REQUIRE(p || !required, "%s: %s is NULL", who, name);
   QEA_REQUIRE(((uintptr_t)p & 3) == 0, "%s: %s must be 4-byte aligned", who, name);
@@ -420,8 +353,9 @@ extern "C" int qea_cc_label(const void* store, int32_t store_is_f32, int64_t sto
                             const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first,
                             const uint8_t* ink_mask, int32_t ink_max, int32_t connectivity, int32_t* labels, int32_t* area, void* stream) {
   const char* who = "qea_cc_label";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
   long long blocks = 0;
-  if (int rc = check_pages(who, store, store_is_f32, store_elems, offset, h, w, n_pages, host_h, host_w, tile_first, &blocks)) return rc;
+  if (int rc = check_paged_launch(who, store, store_is_f32, ps, host_h, host_w, tile_first, true, &blocks)) return rc;
   if (int rc = check_words(who, "labels", labels, true)) return rc;
   if (int rc = check_words(who, "area", area, false)) return rc;
   QEA_REQUIRE(connectivity == 4 || connectivity == 8, "%s: connectivity=%d is neither 4 nor 8", who, connectivity);
@@ -429,16 +363,13 @@ extern "C" int qea_cc_label(const void* store, int32_t store_is_f32, int64_t sto
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)blocks);
   const int conn8 = connectivity == 8;
-  if (store_is_f32)
-    cc_tile_kernel<float><<<grid, dim3(THREADS), 0, s>>>((const float*)store, (long long)store_elems, offset, h, w, n_pages, tile_first, ink_mask,
-                                                        ink_max, conn8, labels, area);
-  else
-    cc_tile_kernel<uint8_t><<<grid, dim3(THREADS), 0, s>>>((const uint8_t*)store, (long long)store_elems, offset, h, w, n_pages, tile_first,
-                                                          ink_mask, ink_max, conn8, labels, area);
+  dispatch_store(store_is_f32, store, [&](auto* typed) {
+    cc_tile_kernel<<<grid, dim3(THREADS), 0, s>>>(typed, ps, tile_first, ink_mask, ink_max, conn8, labels, area);
+  });
   QEA_CHECK_LAUNCH();
-  cc_border_kernel<<<grid, dim3(EDGE_THREADS), 0, s>>>(offset, h, w, n_pages, (long long)store_elems, tile_first, conn8, labels);
+  cc_border_kernel<<<grid, dim3(EDGE_THREADS), 0, s>>>(ps, tile_first, conn8, labels);
   QEA_CHECK_LAUNCH();
-  cc_flatten_kernel<<<grid, dim3(THREADS), 0, s>>>(offset, h, w, n_pages, (long long)store_elems, tile_first, labels);
+  cc_flatten_kernel<<<grid, dim3(THREADS), 0, s>>>(ps, tile_first, labels);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -447,12 +378,12 @@ extern "C" int qea_cc_stats(const void* store, int32_t store_is_f32, int64_t sto
                             const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first,
                             const int32_t* labels, int32_t* area, void* stream) {
   const char* who = "qea_cc_stats";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
   long long blocks = 0;
-  if (int rc = check_pages(who, store, store_is_f32, store_elems, offset, h, w, n_pages, host_h, host_w, tile_first, &blocks)) return rc;
+  if (int rc = check_paged_launch(who, store, store_is_f32, ps, host_h, host_w, tile_first, true, &blocks)) return rc;
   if (int rc = check_words(who, "labels", labels, true)) return rc;
   if (int rc = check_words(who, "area", area, true)) return rc;
-  cc_stats_kernel<<<dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream>>>(offset, h, w, n_pages, (long long)store_elems, tile_first,
-                                                                                     labels, area);
+  cc_stats_kernel<<<dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream>>>(ps, tile_first, labels, area);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -461,15 +392,15 @@ extern "C" int qea_cc_despeckle(const void* store, int32_t store_is_f32, int64_t
                                 const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first,
                                 const int32_t* labels, const int32_t* area, int32_t min_area, float* out_f32, uint8_t* out_u8, void* stream) {
   const char* who = "qea_cc_despeckle";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
   long long blocks = 0;
-  if (int rc = check_pages(who, store, store_is_f32, store_elems, offset, h, w, n_pages, host_h, host_w, tile_first, &blocks)) return rc;
+  if (int rc = check_paged_launch(who, store, store_is_f32, ps, host_h, host_w, tile_first, true, &blocks)) return rc;
   if (int rc = check_words(who, "labels", labels, true)) return rc;
   if (int rc = check_words(who, "area", area, true)) return rc;
-  QEA_REQUIRE(out_f32 || out_u8, "%s: neither an fp32 nor an 8-bit output", who);
-  QEA_REQUIRE(((uintptr_t)out_f32 & 3) == 0, "%s: out_f32 must be 4-byte aligned", who);
+  if (int rc = check_outputs(who, out_f32, out_u8)) return rc;
   QEA_REQUIRE(min_area >= 1, "%s: min_area=%d must be at least 1", who, min_area);
-  cc_despeckle_kernel<<<dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream>>>(offset, h, w, n_pages, (long long)store_elems,
-                                                                                         tile_first, labels, area, min_area, out_f32, out_u8);
+  cc_despeckle_kernel<<<dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream>>>(ps, tile_first, labels, area, min_area, out_f32,
+                                                                                         out_u8);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -478,20 +409,18 @@ extern "C" int qea_cc_smear(const void* store, int32_t store_is_f32, int64_t sto
                             const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* tile_first,
                             const uint8_t* in_mask, int32_t ink_max, int32_t gap, int32_t vertical, uint8_t* out_mask, void* stream) {
   const char* who = "qea_cc_smear";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
   long long blocks = 0;
-  if (int rc = check_pages(who, store, store_is_f32, store_elems, offset, h, w, n_pages, host_h, host_w, tile_first, &blocks)) return rc;
+  if (int rc = check_paged_launch(who, store, store_is_f32, ps, host_h, host_w, tile_first, true, &blocks)) return rc;
   QEA_REQUIRE(out_mask, "%s: out_mask is NULL", who);
   QEA_REQUIRE(out_mask != in_mask, "%s: a pass cannot run in place", who);
   QEA_REQUIRE(ink_max >= 0 && ink_max <= 254, "%s: ink_max=%d outside 0..254", who, ink_max);
   QEA_REQUIRE(gap >= 0 && gap <= MAX_GAP, "%s: gap=%d outside 0..%d", who, gap, MAX_GAP);
   QEA_REQUIRE(vertical == 0 || vertical == 1, "%s: vertical=%d is neither 0 nor 1", who, vertical);
-  hipStream_t s = (hipStream_t)stream;
-  if (store_is_f32)
-    cc_smear_kernel<float><<<dim3((unsigned)blocks), dim3(THREADS), 0, s>>>((const float*)store, (long long)store_elems, offset, h, w, n_pages,
-                                                                           tile_first, in_mask, ink_max, gap, vertical, out_mask);
-  else
-    cc_smear_kernel<uint8_t><<<dim3((unsigned)blocks), dim3(THREADS), 0, s>>>((const uint8_t*)store, (long long)store_elems, offset, h, w,
-                                                                             n_pages, tile_first, in_mask, ink_max, gap, vertical, out_mask);
+  dispatch_store(store_is_f32, store, [&](auto* typed) {
+    cc_smear_kernel<<<dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream>>>(typed, ps, tile_first, in_mask, ink_max, gap, vertical,
+                                                                                       out_mask);
+  });
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -501,15 +430,15 @@ extern "C" int qea_cc_boxes(const void* store, int32_t store_is_f32, int64_t sto
                             const int32_t* labels, const int32_t* roots, const int32_t* root_first, int32_t n_roots, int32_t* boxes,
                             void* stream) {
   const char* who = "qea_cc_boxes";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
   long long blocks = 0;
-  if (int rc = check_pages(who, store, store_is_f32, store_elems, offset, h, w, n_pages, host_h, host_w, tile_first, &blocks)) return rc;
+  if (int rc = check_paged_launch(who, store, store_is_f32, ps, host_h, host_w, tile_first, true, &blocks)) return rc;
   if (int rc = check_words(who, "labels", labels, true)) return rc;
   if (int rc = check_words(who, "roots", roots, true)) return rc;
   if (int rc = check_words(who, "root_first", root_first, true)) return rc;
   if (int rc = check_words(who, "boxes", boxes, true)) return rc;
   QEA_REQUIRE(n_roots >= 0, "%s: n_roots=%d is negative", who, n_roots);
-  cc_boxes_kernel<<<dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream>>>(offset, h, w, n_pages, (long long)store_elems, tile_first,
-                                                                                     labels, roots, root_first, n_roots, boxes);
+  cc_boxes_kernel<<<dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream>>>(ps, tile_first, labels, roots, root_first, n_roots, boxes);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

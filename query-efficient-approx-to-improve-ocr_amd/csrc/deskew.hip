@@ -19,8 +19,8 @@
 //                     A = 256 and w = 32767) would not fit for the widest pages and was not kept.
 // pick_kernel         One wave per page: every lane keeps the best of its candidates under the total order (larger S, then smaller |a|,
 //                     then smaller a), a butterfly merges them, lane 0 applies the gain gate.
-// rotate_kernel       ONE launch for all pages.  Workgroup b owns one 32 x 64 tile of one page through the tile_first table of
-//                     csrc/binarize.hip; lane = column, a wave owns eight rows.  X and Y are int64 products for a thread's first row and advance
+// rotate_kernel       ONE launch for all pages.  Workgroup b owns one 32 x 64 tile of one page through the tile_first table
+//                     (csrc/page_store.h: tile_of_block); lane = column, a wave owns eight rows.  X and Y are int64 products for a thread's first row and advance
 //                     by -2 S16 / +2 C16 per row, which are the same integers.  The four taps are
 //                     read where they lie: at slopes of a few degrees the source rows of a tile are the tile's own rows plus a few, which
 //                     L1 holds; an LDS copy of the footprint would be read once per tap all the same.
@@ -34,18 +34,6 @@ namespace {
 constexpr int TH = QEA_BINARIZE_TILE_H, TW = QEA_BINARIZE_TILE_W, THREADS = 256;
 constexpr int SUM_ROWS = 32, SUM_STRIPS = 8, SCORE_ROWS = 63, SCORE_CANDIDATES = 32;
 static_assert(TW == 64 && TH == 32 && THREADS == 256 && SUM_ROWS * SUM_STRIPS == THREADS, "a wave owns eight rows of a tile and a lane one column");
-
-__device__ __forceinline__ int page_of_block(const int32_t* __restrict__ first, int n_pages, int b) {
-  int lo = 0, hi = n_pages;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (first[mid] <= b) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ int value_of(uint8_t v) { return v; }
-__device__ __forceinline__ int value_of(float v) { return to_u8(v); }
 
 struct alignas(16) Bytes16 { uint8_t v[16]; };
 struct alignas(16) Floats4 { float v[4]; };
@@ -78,13 +66,11 @@ __device__ __forceinline__ int strip_count(const T* __restrict__ store, long lon
 }
 
 template <typename T>
-__global__ __launch_bounds__(THREADS) void strip_sums_kernel(const T* __restrict__ store, long long store_elems, const int64_t* __restrict__ offset,
-                                                             const int32_t* __restrict__ h, const int32_t* __restrict__ w, int n_pages,
-                                                             int blocks, const int32_t* __restrict__ ink_max_dev, int ink_max,
-                                                             uint8_t* __restrict__ C) {
+__global__ __launch_bounds__(THREADS) void strip_sums_kernel(const T* __restrict__ store, const PageStore ps, int blocks,
+                                                             const int32_t* __restrict__ ink_max_dev, int ink_max, uint8_t* __restrict__ C) {
   __shared__ uint8_t cnt[SUM_STRIPS][SUM_ROWS + 1];
   const int p = (int)(blockIdx.x / (unsigned)blocks), y0 = (int)(blockIdx.x % (unsigned)blocks) * SUM_ROWS;
-  const Page g = page_of(p, offset, h, w, n_pages, store_elems);
+  const Page g = page_of(ps, p);
   if (g.h == 0 || y0 >= g.h) return;                                          // uniform
   if (ink_max_dev) ink_max = ink_max_dev[p];
   const int ns = (g.w + 31) >> 5;
@@ -93,18 +79,17 @@ __global__ __launch_bounds__(THREADS) void strip_sums_kernel(const T* __restrict
   for (int j0 = 0; j0 < ns; j0 += SUM_STRIPS) {
     const int j = j0 + rj, y = y0 + ry;
     if (j < ns && y < g.h)
-      cnt[rj][ry] = (uint8_t)strip_count(store, store_elems, g.off + (long long)y * g.w + 32 * j, min(32, g.w - 32 * j), ink_max);
+      cnt[rj][ry] = (uint8_t)strip_count(store, ps.store_elems, g.off + (long long)y * g.w + 32 * j, min(32, g.w - 32 * j), ink_max);
     __syncthreads();
     if (j0 + wj < ns && y0 + wy < g.h) C[g.off + (long long)(j0 + wj) * g.h + y0 + wy] = cnt[wj][wy];
     __syncthreads();
   }
 }
 
-__global__ __launch_bounds__(THREADS) void scores_kernel(const uint8_t* __restrict__ C, long long store_elems, const int64_t* __restrict__ offset,
-                                                         const int32_t* __restrict__ h, const int32_t* __restrict__ w, int n_pages, int blocks,
-                                                         int A, unsigned long long* __restrict__ scores) {
+__global__ __launch_bounds__(THREADS) void scores_kernel(const uint8_t* __restrict__ C, const PageStore ps, int blocks, int A,
+                                                         unsigned long long* __restrict__ scores) {
   const int p = (int)(blockIdx.x / (unsigned)blocks), r0 = (int)(blockIdx.x % (unsigned)blocks) * SCORE_ROWS;
-  const Page g = page_of(p, offset, h, w, n_pages, store_elems);
+  const Page g = page_of(ps, p);
   if (g.h == 0 || r0 >= g.h) return;                                          // uniform
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = r0 + lane, ns = (g.w + 31) >> 5, half = g.w >> 1;
   const uint8_t* const Cp = C + g.off;
@@ -163,19 +148,17 @@ __device__ __forceinline__ int tap(const T* __restrict__ page, int h, int w, lon
 }
 
 template <typename T>
-__global__ __launch_bounds__(THREADS) void rotate_kernel(const T* __restrict__ store, long long store_elems, const int64_t* __restrict__ offset,
-                                                         const int32_t* __restrict__ h, const int32_t* __restrict__ w, int n_pages,
-                                                         const int32_t* __restrict__ tile_first, const int32_t* __restrict__ slopes,
-                                                         const int32_t* __restrict__ table, int A, int nearest, int fill,
-                                                         const float* __restrict__ norm, float* __restrict__ out_f32, uint8_t* __restrict__ out_u8) {
-  const int p = page_of_block(tile_first, n_pages, blockIdx.x);
-  const Page g = page_of(p, offset, h, w, n_pages, store_elems);
-  const int t = (int)blockIdx.x - tile_first[p], tiles_x = (g.w + TW - 1) / TW;
-  if (g.h == 0 || t < 0 || t / tiles_x >= (g.h + TH - 1) / TH) return;        // uniform
-  const int a = slopes[p];
+__global__ __launch_bounds__(THREADS) void rotate_kernel(const T* __restrict__ store, const PageStore ps, const int32_t* __restrict__ tile_first,
+                                                         const int32_t* __restrict__ slopes, const int32_t* __restrict__ table, int A,
+                                                         int nearest, int fill, const float* __restrict__ norm, float* __restrict__ out_f32,
+                                                         uint8_t* __restrict__ out_u8) {
+  const Tile t = tile_of_block(ps, tile_first, TH, TW);
+  if (t.g.h == 0) return;                                                     // uniform
+  const Page g = t.g;
+  const int a = slopes[t.page];
   if (a < -A || a > A) return;                                                // uniform
   const long long C16 = table[2 * (a + A)], S16 = table[2 * (a + A) + 1];
-  const int x = t % tiles_x * TW + (threadIdx.x & 63), y0 = t / tiles_x * TH + 8 * (threadIdx.x >> 6);
+  const int x = t.x0 + (threadIdx.x & 63), y0 = t.y0 + 8 * (threadIdx.x >> 6);
   if (x >= g.w) return;
   const T* const page = store + g.off;
   const long long dx2 = 2ll * x - (g.w - 1), dy2 = 2ll * y0 - (g.h - 1);
@@ -196,32 +179,6 @@ __global__ __launch_bounds__(THREADS) void rotate_kernel(const T* __restrict__ s
   }
 }
 
-// What the entry points check of the page table alike; -> the largest h in *max_h.
-int check_pages(const char* who, long long store_elems, const void* offset, const void* h, const void* w, int n_pages, const int32_t* host_h,
-                const int32_t* host_w, int* max_h) {
-  QEA_REQUIRE(offset && h && w && host_h && host_w, "%s: null pointer", who);
-  QEA_REQUIRE(n_pages >= 1 && n_pages <= (1 << 24), "%s: n_pages=%d outside 1..2^24", who, n_pages);
-  QEA_REQUIRE(store_elems >= 1, "%s: store_elems=%lld", who, store_elems);
-  int top = 0;
-  for (int p = 0; p < n_pages; ++p) {
-    const long long ph = host_h[p], pw = host_w[p];
-    QEA_REQUIRE(ph >= 1 && pw >= 1, "%s: page %d is empty (%lld x %lld)", who, p, ph, pw);
-    QEA_REQUIRE(ph <= QEA_DESKEW_MAX_SIDE && pw <= QEA_DESKEW_MAX_SIDE, "%s: page %d is %lld x %lld, a side over %d", who, p, ph, pw,
-                QEA_DESKEW_MAX_SIDE);
-    QEA_REQUIRE(ph * pw <= QEA_BINARIZE_MAX_PAGE_PIXELS, "%s: page %d has %lld x %lld pixels, more than 2^27", who, p, ph, pw);
-    top = ph > top ? (int)ph : top;
-  }
-  *max_h = top;
-  return QEA_OK;
-}
-
-int check_store(const char* who, const void* store, int store_is_f32) {
-  QEA_REQUIRE(store, "%s: null pointer", who);
-  QEA_REQUIRE(store_is_f32 == 0 || store_is_f32 == 1, "%s: store_is_f32=%d is neither 0 nor 1", who, store_is_f32);
-  QEA_REQUIRE(!store_is_f32 || ((uintptr_t)store & 3) == 0, "%s: an fp32 store must be 4-byte aligned", who);
-  return QEA_OK;
-}
-
 int check_slope_range(const char* who, int A) {
   QEA_REQUIRE(A >= 0 && A <= QEA_DESKEW_MAX_SLOPE, "%s: A=%d outside 0..%d", who, A, QEA_DESKEW_MAX_SLOPE);
   return QEA_OK;
@@ -238,9 +195,11 @@ extern "C" int qea_skew_strip_sums(const void* store, int32_t store_is_f32, int6
                                    const int32_t* w, int32_t n_pages, const int32_t* host_h, const int32_t* host_w, const int32_t* ink_max_dev,
                                    int32_t ink_max, uint8_t* C, void* stream) {
   const char* who = "qea_skew_strip_sums";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
   int max_h = 0;
   if (int rc = check_store(who, store, store_is_f32)) return rc;
-  if (int rc = check_pages(who, store_elems, offset, h, w, n_pages, host_h, host_w, &max_h)) return rc;
+  if (int rc = check_table(who, ps)) return rc;
+  if (int rc = check_page_sizes(who, host_h, host_w, n_pages, QEA_DESKEW_MAX_SIDE, nullptr, nullptr, &max_h)) return rc;
   QEA_REQUIRE(C, "%s: C is NULL", who);
   QEA_REQUIRE(((uintptr_t)ink_max_dev & 3) == 0, "%s: ink_max_dev must be 4-byte aligned", who);
   QEA_REQUIRE(ink_max_dev || (ink_max >= 0 && ink_max <= 254), "%s: ink_max=%d outside 0..254", who, ink_max);
@@ -248,13 +207,9 @@ extern "C" int qea_skew_strip_sums(const void* store, int32_t store_is_f32, int6
               "%s: C overlaps the store", who);
   const long long blocks = (max_h + SUM_ROWS - 1) / SUM_ROWS, grid = blocks * n_pages;
   QEA_REQUIRE(grid <= 0x7fffffffll, "%s: %lld workgroups, more than 2^31 - 1", who, grid);
-  hipStream_t s = (hipStream_t)stream;
-  if (store_is_f32)
-    strip_sums_kernel<float><<<dim3((unsigned)grid), dim3(THREADS), 0, s>>>((const float*)store, (long long)store_elems, offset, h, w, n_pages,
-                                                                           (int)blocks, ink_max_dev, ink_max, C);
-  else
-    strip_sums_kernel<uint8_t><<<dim3((unsigned)grid), dim3(THREADS), 0, s>>>((const uint8_t*)store, (long long)store_elems, offset, h, w, n_pages,
-                                                                             (int)blocks, ink_max_dev, ink_max, C);
+  dispatch_store(store_is_f32, store, [&](auto* typed) {
+    strip_sums_kernel<<<dim3((unsigned)grid), dim3(THREADS), 0, (hipStream_t)stream>>>(typed, ps, (int)blocks, ink_max_dev, ink_max, C);
+  });
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -262,9 +217,11 @@ extern "C" int qea_skew_strip_sums(const void* store, int32_t store_is_f32, int6
 extern "C" int qea_skew_scores(const uint8_t* C, int64_t store_elems, const int64_t* offset, const int32_t* h, const int32_t* w, int32_t n_pages,
                                const int32_t* host_h, const int32_t* host_w, int32_t A, int64_t* scores, void* stream) {
   const char* who = "qea_skew_scores";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
   int max_h = 0;
   QEA_REQUIRE(C, "%s: C is NULL", who);
-  if (int rc = check_pages(who, store_elems, offset, h, w, n_pages, host_h, host_w, &max_h)) return rc;
+  if (int rc = check_table(who, ps)) return rc;
+  if (int rc = check_page_sizes(who, host_h, host_w, n_pages, QEA_DESKEW_MAX_SIDE, nullptr, nullptr, &max_h)) return rc;
   if (int rc = check_slope_range(who, A)) return rc;
   QEA_REQUIRE(scores && ((uintptr_t)scores & 7) == 0, "%s: scores must be an 8-byte aligned table of n_pages x (2 A + 1) values", who);
   const long long blocks = (max_h + SCORE_ROWS - 1) / SCORE_ROWS, grid = blocks * n_pages;
@@ -274,8 +231,8 @@ extern "C" int qea_skew_scores(const uint8_t* C, int64_t store_elems, const int6
     qea_set_error("%s: cannot zero the scores", who);
     return QEA_ERR_LAUNCH;
   }
-  scores_kernel<<<dim3((unsigned)grid, (unsigned)((2 * A + SCORE_CANDIDATES) / SCORE_CANDIDATES)), dim3(THREADS), 0, s>>>(C, (long long)store_elems, offset, h, w, n_pages, (int)blocks, A,
-                                                              (unsigned long long*)scores);
+  scores_kernel<<<dim3((unsigned)grid, (unsigned)((2 * A + SCORE_CANDIDATES) / SCORE_CANDIDATES)), dim3(THREADS), 0, s>>>(
+      C, ps, (int)blocks, A, (unsigned long long*)scores);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -297,31 +254,26 @@ extern "C" int qea_deskew_rotate(const void* store, int32_t store_is_f32, int64_
                                  const int32_t* slopes, const int32_t* table, int32_t A, int32_t nearest, int32_t fill, const float* norm,
                                  float* out_f32, uint8_t* out_u8, void* stream) {
   const char* who = "qea_deskew_rotate";
-  int max_h = 0;
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
+  long long tiles = 0;
   if (int rc = check_store(who, store, store_is_f32)) return rc;
-  if (int rc = check_pages(who, store_elems, offset, h, w, n_pages, host_h, host_w, &max_h)) return rc;
+  if (int rc = check_table(who, ps)) return rc;
+  if (int rc = check_page_sizes(who, host_h, host_w, n_pages, QEA_DESKEW_MAX_SIDE, &tiles, nullptr, nullptr)) return rc;
   if (int rc = check_slope_range(who, A)) return rc;
   QEA_REQUIRE(tile_first, "%s: null pointer", who);
   QEA_REQUIRE(slopes && ((uintptr_t)slopes & 3) == 0, "%s: slopes must be a 4-byte aligned array of n_pages values", who);
   QEA_REQUIRE(table && ((uintptr_t)table & 3) == 0, "%s: table must be a 4-byte aligned array of (2 A + 1) x 2 values", who);
   QEA_REQUIRE(nearest == 0 || nearest == 1, "%s: nearest=%d is neither 0 nor 1", who, nearest);
   QEA_REQUIRE(fill >= 0 && fill <= 255, "%s: fill=%d outside 0..255", who, fill);
-  QEA_REQUIRE(out_f32 || out_u8, "%s: neither an fp32 nor an 8-bit output", who);
-  QEA_REQUIRE(((uintptr_t)out_f32 & 3) == 0, "%s: out_f32 must be 4-byte aligned", who);
+  if (int rc = check_outputs(who, out_f32, out_u8)) return rc;
   QEA_REQUIRE(!out_f32 || (norm && ((uintptr_t)norm & 3) == 0), "%s: out_f32 needs the 4-byte aligned table norm of 256 values", who);
   const unsigned long long bytes = (unsigned long long)store_elems * (store_is_f32 ? 4 : 1);
   QEA_REQUIRE(!overlap(store, bytes, out_u8, (unsigned long long)store_elems) && !overlap(store, bytes, out_f32, 4ull * store_elems),
               "%s: an output overlaps the store (the rotation reads pixels that other workgroups write)", who);
-  long long tiles = 0;
-  for (int p = 0; p < n_pages; ++p) tiles += (long long)((host_h[p] + TH - 1) / TH) * ((host_w[p] + TW - 1) / TW);
-  QEA_REQUIRE(tiles <= 0x7fffffffll, "%s: %lld workgroups, more than 2^31 - 1", who, tiles);
-  hipStream_t s = (hipStream_t)stream;
-  if (store_is_f32)
-    rotate_kernel<float><<<dim3((unsigned)tiles), dim3(THREADS), 0, s>>>((const float*)store, (long long)store_elems, offset, h, w, n_pages,
-                                                                        tile_first, slopes, table, A, nearest, fill, norm, out_f32, out_u8);
-  else
-    rotate_kernel<uint8_t><<<dim3((unsigned)tiles), dim3(THREADS), 0, s>>>((const uint8_t*)store, (long long)store_elems, offset, h, w, n_pages,
-                                                                          tile_first, slopes, table, A, nearest, fill, norm, out_f32, out_u8);
+  dispatch_store(store_is_f32, store, [&](auto* typed) {
+    rotate_kernel<<<dim3((unsigned)tiles), dim3(THREADS), 0, (hipStream_t)stream>>>(typed, ps, tile_first, slopes, table, A, nearest, fill, norm,
+                                                                                    out_f32, out_u8);
+  });
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

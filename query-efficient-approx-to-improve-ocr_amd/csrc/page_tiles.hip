@@ -2,8 +2,7 @@
 // cleaned tiles pasted into the packed outputs in one launch (include/qea_hip.h: qea_page_tiles_gather / qea_page_tiles_scatter;
 // qea/pages.py: clean_pages, whose tiles_gather_spec / tiles_scatter_spec are the specification of the two kernels).
 //
-// The page store keeps pages of any sizes back to back, row-major without padding: page p is h[p] rows of w[p] elements at element
-// offset[p] of the store (8-bit grey, so pages start at any byte, or fp32).  The outputs are packed the same way with the same offsets.
+// The pages lie in the packed page store of csrc/page_store.h; the outputs are packed the same way with the same offsets.
 //
 // page_tiles_gather_kernel: out[N][TH][TW] fp32.  Tile t = (page, oy, ox) reads page pixel (oy + y, ox + x); what lies outside the page's
 // h x w is white (1.0): the padding to the next multiple of 16 costs nothing.  A window gather (csrc/window_gather.h: lanes, reads, the
@@ -24,13 +23,11 @@
 namespace {
 
 template <typename T>
-__global__ __launch_bounds__(WG_THREADS) void page_tiles_gather_kernel(const T* __restrict__ store, long long store_elems,
-                                                                       const int64_t* __restrict__ offset, const int32_t* __restrict__ h,
-                                                                       const int32_t* __restrict__ w, int n_pages,
+__global__ __launch_bounds__(WG_THREADS) void page_tiles_gather_kernel(const T* __restrict__ store, const PageStore ps,
                                                                        const int32_t* __restrict__ tile, int N, int TH, int TW,
                                                                        const float* __restrict__ table, float* __restrict__ out) {
   window_gather(store, table, out, N, TH, TW, [=](int t) {
-    const Page g = page_of(tile[3 * t], offset, h, w, n_pages, store_elems);
+    const Page g = page_of(ps, tile[3 * t]);
     const int oy = tile[3 * t + 1], ox = tile[3 * t + 2];
     // Tile pixel (x, y) is page pixel (ox + x, oy + y): rows -oy .. h-oy-1 and columns -ox .. w-ox-1 of the tile, cut to it.  Origins are
     // ANY int32, so a - o may not be formed as an int: cut = min(max(a - o, 0), hi) for a >= 0 < hi, where o < a gives 0 < a - o < 2^32
@@ -40,15 +37,13 @@ __global__ __launch_bounds__(WG_THREADS) void page_tiles_gather_kernel(const T* 
 }
 
 __global__ __launch_bounds__(WG_THREADS) void page_tiles_scatter_kernel(const float* __restrict__ tiles, int N, int TH, int TW,
-                                                                        const int32_t* __restrict__ tile, const int64_t* __restrict__ offset,
-                                                                        const int32_t* __restrict__ h, const int32_t* __restrict__ w,
-                                                                        int n_pages, long long store_elems, float* __restrict__ out_f32,
-                                                                        uint8_t* __restrict__ out_u8) {
+                                                                        const int32_t* __restrict__ tile, const PageStore ps,
+                                                                        float* __restrict__ out_f32, uint8_t* __restrict__ out_u8) {
   int q, ty, tx0;
   if (!quad_of(TH, TW, q, ty, tx0)) return;
   for (int t = blockIdx.y; t < N; t += gridDim.y) {    // uniform over the workgroup
     const int32_t* r = tile + 7 * t;
-    const Page g = page_of(r[0], offset, h, w, n_pages, store_elems);
+    const Page g = page_of(ps, r[0]);
     const long long py = (long long)r[1] + ty, px0 = (long long)r[2] + tx0;
     // rows and columns this tile owns: its core, inside the page (the tile itself bounds ty and tx0 + k)
     const long long y0 = max(r[3], 0), y1 = min(r[4], g.h), x0 = max(r[5], 0), x1 = min(r[6], g.w);
@@ -66,11 +61,9 @@ __global__ __launch_bounds__(WG_THREADS) void page_tiles_scatter_kernel(const fl
   }
 }
 
-int check_common(const char* who, const void* offset, const void* h, const void* w, const void* tile, int n_pages, long long store_elems, int N,
-                 int TH, int TW) {
-  QEA_REQUIRE(offset && h && w && tile, "%s: null pointer", who);
-  QEA_REQUIRE(n_pages >= 1 && n_pages <= (1 << 24), "%s: n_pages=%d outside 1..2^24", who, n_pages);
-  QEA_REQUIRE(store_elems >= 1, "%s: store_elems=%lld", who, store_elems);
+int check_common(const char* who, const PageStore& ps, const void* tile, int N, int TH, int TW) {
+  if (int rc = check_table(who, ps)) return rc;
+  QEA_REQUIRE(tile, "%s: null pointer", who);
   QEA_REQUIRE(N >= 1 && N <= (1 << 24), "%s: N=%d outside 1..2^24", who, N);
   QEA_REQUIRE(TH >= 1 && TH <= 8192, "%s: TH=%d outside 1..8192", who, TH);
   QEA_REQUIRE(TW >= 4 && TW <= 8192 && TW % 4 == 0, "%s: TW=%d must be a multiple of 4 in 4..8192", who, TW);
@@ -82,18 +75,16 @@ int check_common(const char* who, const void* offset, const void* h, const void*
 extern "C" int qea_page_tiles_gather(const void* store, int32_t store_is_f32, int64_t store_elems, const int64_t* offset, const int32_t* h,
                                      const int32_t* w, int32_t n_pages, const int32_t* tile, int32_t N, int32_t TH, int32_t TW,
                                      const float* table, float* out, void* stream) {
-  QEA_REQUIRE(store && out, "qea_page_tiles_gather: null pointer");
-  QEA_REQUIRE(store_is_f32 == 0 || store_is_f32 == 1, "qea_page_tiles_gather: store_is_f32=%d is neither 0 nor 1", store_is_f32);
-  if (int rc = check_common("qea_page_tiles_gather", offset, h, w, tile, n_pages, store_elems, N, TH, TW)) return rc;
-  QEA_REQUIRE(store_is_f32 || table, "qea_page_tiles_gather: an 8-bit store needs the 256-entry table");
-  QEA_REQUIRE(!store_is_f32 || ((uintptr_t)store & 3) == 0, "qea_page_tiles_gather: an fp32 store must be 4-byte aligned");
-  QEA_REQUIRE(((uintptr_t)out & 15) == 0, "qea_page_tiles_gather: out must be 16-byte aligned");
-  if (store_is_f32)
-    launch_over_quads(page_tiles_gather_kernel<float>, N, TH, TW, stream, (const float*)store, (long long)store_elems, offset, h, w, n_pages,
-                      tile, N, TH, TW, table, out);
-  else
-    launch_over_quads(page_tiles_gather_kernel<uint8_t>, N, TH, TW, stream, (const uint8_t*)store, (long long)store_elems, offset, h, w, n_pages,
-                      tile, N, TH, TW, table, out);
+  const char* who = "qea_page_tiles_gather";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
+  if (int rc = check_store(who, store, store_is_f32)) return rc;
+  QEA_REQUIRE(out, "%s: null pointer", who);
+  if (int rc = check_common(who, ps, tile, N, TH, TW)) return rc;
+  QEA_REQUIRE(store_is_f32 || table, "%s: an 8-bit store needs the 256-entry table", who);
+  QEA_REQUIRE(((uintptr_t)out & 15) == 0, "%s: out must be 16-byte aligned", who);
+  dispatch_store(store_is_f32, store, [&](auto* typed) {
+    launch_over_quads(page_tiles_gather_kernel<StoreElem<decltype(typed)>>, N, TH, TW, stream, typed, ps, tile, N, TH, TW, table, out);
+  });
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }
@@ -101,13 +92,13 @@ extern "C" int qea_page_tiles_gather(const void* store, int32_t store_is_f32, in
 extern "C" int qea_page_tiles_scatter(const float* tiles, int32_t N, int32_t TH, int32_t TW, const int32_t* tile, const int64_t* offset,
                                       const int32_t* h, const int32_t* w, int32_t n_pages, int64_t store_elems, float* out_f32, uint8_t* out_u8,
                                       void* stream) {
-  QEA_REQUIRE(tiles, "qea_page_tiles_scatter: null pointer");
-  QEA_REQUIRE(out_f32 || out_u8, "qea_page_tiles_scatter: neither an fp32 nor an 8-bit output");
-  if (int rc = check_common("qea_page_tiles_scatter", offset, h, w, tile, n_pages, store_elems, N, TH, TW)) return rc;
-  QEA_REQUIRE(((uintptr_t)tiles & 15) == 0, "qea_page_tiles_scatter: tiles must be 16-byte aligned");
-  QEA_REQUIRE(((uintptr_t)out_f32 & 3) == 0, "qea_page_tiles_scatter: out_f32 must be 4-byte aligned");
-  launch_over_quads(page_tiles_scatter_kernel, N, TH, TW, stream, tiles, N, TH, TW, tile, offset, h, w, n_pages, (long long)store_elems, out_f32,
-                    out_u8);
+  const char* who = "qea_page_tiles_scatter";
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
+  QEA_REQUIRE(tiles, "%s: null pointer", who);
+  if (int rc = check_outputs(who, out_f32, out_u8)) return rc;
+  if (int rc = check_common(who, ps, tile, N, TH, TW)) return rc;
+  QEA_REQUIRE(((uintptr_t)tiles & 15) == 0, "%s: tiles must be 16-byte aligned", who);
+  launch_over_quads(page_tiles_scatter_kernel, N, TH, TW, stream, tiles, N, TH, TW, tile, ps, out_f32, out_u8);
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

@@ -24,19 +24,15 @@ namespace {
 constexpr int OH = QEA_WORD_STRIP_H;
 static_assert(OH == 32, "the statement's unit is 1 / 32 source pixel: the shifts by 5 below");
 
-__device__ __forceinline__ int value_of(uint8_t v) { return v; }
-__device__ __forceinline__ int value_of(float v) { return to_u8(v); }
-
 template <typename T>
-__global__ __launch_bounds__(WG_THREADS) void word_strips_kernel(const T* __restrict__ store, long long store_elems,
-                                                                 const int64_t* __restrict__ offset, const int32_t* __restrict__ h,
-                                                                 const int32_t* __restrict__ w, int n_pages, const int32_t* __restrict__ boxes,
-                                                                 int n, int OW, const float* __restrict__ norm, float* __restrict__ out) {
+__global__ __launch_bounds__(WG_THREADS) void word_strips_kernel(const T* __restrict__ store, const PageStore ps,
+                                                                 const int32_t* __restrict__ boxes, int n, int OW,
+                                                                 const float* __restrict__ norm, float* __restrict__ out) {
   int q, oy, ox;
   if (!quad_of(OH, OW, q, oy, ox)) return;
   for (int i = blockIdx.y; i < n; i += gridDim.y) {    // uniform over the workgroup: everything up to the pixel loops is scalar
     const int32_t* b = boxes + 5 * (size_t)i;
-    Page g = page_of(b[0], offset, h, w, n_pages, store_elems);
+    Page g = page_of(ps, b[0]);
     if (g.h > QEA_WORD_STRIP_MAX_SIDE || g.w > QEA_WORD_STRIP_MAX_SIDE) g.h = g.w = 0;
     const int x0 = max(b[1], 0), y0 = max(b[2], 0), x1 = min(b[3], g.w), y1 = min(b[4], g.h);
     f32x4 v = {1.f, 1.f, 1.f, 1.f};
@@ -88,11 +84,10 @@ extern "C" int qea_word_strips(const void* store, int32_t store_is_f32, int64_t 
                                const int32_t* w, int32_t n_pages, const int32_t* boxes, int32_t n, int32_t OW, const float* norm, float* out,
                                void* stream) {
   const char* who = "qea_word_strips";
-  QEA_REQUIRE(store && offset && h && w && boxes && norm && out, "%s: null pointer", who);
-  QEA_REQUIRE(store_is_f32 == 0 || store_is_f32 == 1, "%s: store_is_f32=%d is neither 0 nor 1", who, store_is_f32);
-  QEA_REQUIRE(!store_is_f32 || ((uintptr_t)store & 3) == 0, "%s: an fp32 store must be 4-byte aligned", who);
-  QEA_REQUIRE(n_pages >= 1 && n_pages <= (1 << 24), "%s: n_pages=%d outside 1..2^24", who, n_pages);
-  QEA_REQUIRE(store_elems >= 1, "%s: store_elems=%lld", who, (long long)store_elems);
+  const PageStore ps = {(long long)store_elems, n_pages, offset, h, w};
+  if (int rc = check_store(who, store, store_is_f32)) return rc;
+  if (int rc = check_table(who, ps)) return rc;
+  QEA_REQUIRE(boxes && norm && out, "%s: null pointer", who);
   QEA_REQUIRE(n >= 0 && n <= QEA_WORD_STRIP_MAX_BOXES, "%s: n=%d outside 0..2^20", who, n);
   QEA_REQUIRE(OW >= QEA_WORD_STRIP_MIN_W && OW <= QEA_WORD_STRIP_MAX_W && OW % 16 == 0, "%s: OW=%d must be a multiple of 16 in %d..%d", who, OW,
               QEA_WORD_STRIP_MIN_W, QEA_WORD_STRIP_MAX_W);
@@ -100,12 +95,9 @@ extern "C" int qea_word_strips(const void* store, int32_t store_is_f32, int64_t 
               "%s: offset must be 8-byte aligned, h / w / boxes / norm 4-byte aligned", who);
   QEA_REQUIRE(((uintptr_t)out & 15) == 0, "%s: out must be 16-byte aligned", who);
   if (n == 0) return QEA_OK;                           // nothing to write
-  if (store_is_f32)
-    launch_over_quads(word_strips_kernel<float>, n, OH, OW, stream, (const float*)store, (long long)store_elems, offset, h, w, n_pages, boxes, n,
-                      OW, norm, out);
-  else
-    launch_over_quads(word_strips_kernel<uint8_t>, n, OH, OW, stream, (const uint8_t*)store, (long long)store_elems, offset, h, w, n_pages, boxes,
-                      n, OW, norm, out);
+  dispatch_store(store_is_f32, store, [&](auto* typed) {
+    launch_over_quads(word_strips_kernel<StoreElem<decltype(typed)>>, n, OH, OW, stream, typed, ps, boxes, n, OW, norm, out);
+  });
   QEA_CHECK_LAUNCH();
   return QEA_OK;
 }

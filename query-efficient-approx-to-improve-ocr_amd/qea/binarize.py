@@ -22,8 +22,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import QeaError
-from .pages import _check_out, pack_pages, quantise_u8, unpack_pages
+from .pages import _check_out, host_pages, open_store, pack_ink_host, packed_result, unpack_pages
 
 METHODS = ("otsu", "sauvola")
 MAX_WINDOW, MAX_PAGE_PIXELS = 127, 1 << 27
@@ -40,14 +39,6 @@ def check_params(method, window=25, k=0.2, R=128.0):
             raise ValueError(f"k={k!r}: strictly between 0 and 1")
         if not (isinstance(R, (int, float)) and 0.0 < R < math.inf):
             raise ValueError(f"R={R!r}: positive and finite")
-
-
-def _check_sizes(pages):
-    """before anything is packed or copied"""
-    for i, p in enumerate(pages):
-        shape = tuple(getattr(p, "shape", ()))
-        if len(shape) >= 2 and int(shape[-2]) * int(shape[-1]) > MAX_PAGE_PIXELS:
-            raise QeaError(f"page {i}: {shape[-2]} x {shape[-1]} has more than 2^27 pixels (the bound that keeps Otsu's integers below 2^63)")
 
 
 def otsu_threshold_of_hist(hist):
@@ -95,27 +86,19 @@ def _sauvola_host(v, window, k, R):
 
 def _host(pk, method, window, k, R, out):
     """The host path over a packed store -> (packed result, thresholds or None)"""
-    res = torch.empty(pk.store.numel(), dtype=torch.uint8 if out == "u8" else torch.float32)
-    thresholds = []
-    for o, h, w in zip(pk.offset, pk.h, pk.w):
-        page = pk.store[int(o):int(o) + int(h) * int(w)].view(int(h), int(w))
-        v = (page if page.dtype == torch.uint8 else quantise_u8(page)).numpy()
+    thresholds, inks = [], []
+    for v in host_pages(pk):
         if method == "otsu":
             thresholds.append(otsu_threshold_of_hist(np.bincount(v.reshape(-1), minlength=256)))
-            fg = v.astype(np.int64) <= thresholds[-1]
+            inks.append(v.astype(np.int64) <= thresholds[-1])
         else:
-            fg = _sauvola_host(v, window, k, R)
-        hi = 255 if out == "u8" else 1.0
-        res[int(o):int(o) + int(h) * int(w)] = torch.from_numpy(np.where(fg, 0, hi).astype(np.uint8 if out == "u8" else np.float32)).reshape(-1)
-    return res, (torch.tensor(thresholds, dtype=torch.int32) if method == "otsu" else None)
+            inks.append(_sauvola_host(v, window, k, R))
+    return pack_ink_host(pk, inks, out), (torch.tensor(thresholds, dtype=torch.int32) if method == "otsu" else None)
 
 
-def _device(pk, dev, method, window, k, R, out):
+def _device(store, table, method, window, k, R, out):
     from . import ops
-    store = pk.store.to(dev) if pk.store.dtype == torch.uint8 else pk.store.to(dev, torch.float32)
-    table = ops.binarize_page_table(pk.offset, pk.h, pk.w, dev)
-    res = torch.empty(store.numel(), dtype=torch.uint8 if out == "u8" else torch.float32, device=dev)
-    outs = {"out_u8" if out == "u8" else "out_f32": res}
+    res, outs = packed_result(store.numel(), out, store.device)
     if method == "sauvola":
         ops.binarize_sauvola(store, table, window, k, R, **outs)
         return res, None
@@ -128,16 +111,12 @@ def _run(pages, method, window, k, R, out, device, despeckle=0, despeckle_connec
     if despeckle:
         from . import components
         components.check_params(despeckle_connectivity, min_area=despeckle)
-    _check_sizes(pages)
-    pk = pack_pages(pages)
-    dev = torch.device(device) if device is not None else pk.store.device
+    pk, dev, store, table = open_store(pages, device, max_pixels=MAX_PAGE_PIXELS)   # the bound that keeps Otsu's integers below 2^63
     if dev.type == "cuda":
-        res, thr = _device(pk, dev, method, int(window), float(k), float(R), out)
+        res, thr = _device(store, table, method, int(window), float(k), float(R), out)
         if despeckle:                                          # the packed result is the next store: nothing is unpacked or copied
-            from . import ops
-            res = components.despeckle_store(res, ops.binarize_page_table(pk.offset, pk.h, pk.w, dev), despeckle, despeckle_connectivity, out=out)
+            res = components.despeckle_store(res, table, despeckle, despeckle_connectivity, out=out)
     else:
-        pk = pk._replace(store=pk.store.cpu())
         res, thr = _host(pk, method, int(window), float(k), float(R), out)
         if despeckle:
             res = components.despeckle_store_host(pk._replace(store=res), despeckle, despeckle_connectivity, out=out)

@@ -22,25 +22,21 @@ neighbouring rows, and pointer jumping over the runs, all in numpy.
 import numpy as np
 import torch
 
-from .pages import _check_out, pack_pages, quantise_u8, unpack_pages
+from .pages import _check_out, host_pages, is_int, open_store, pack_host, pack_ink_host, packed_result, unpack_pages
 
-MAX_GAP = 127
-
-
-def _is_int(v):
-    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+MAX_GAP, MAX_PAGE_PIXELS = 127, 1 << 27
 
 
 def check_params(connectivity=8, ink_max=127, min_area=1, gap_x=0, gap_y=0):
     """ValueError for parameters outside the statement's ranges, before any work"""
-    if not _is_int(connectivity) or connectivity not in (4, 8):
+    if not is_int(connectivity) or connectivity not in (4, 8):
         raise ValueError(f"connectivity={connectivity!r}: 4 or 8")
-    if not _is_int(ink_max) or not 0 <= ink_max <= 254:
+    if not is_int(ink_max) or not 0 <= ink_max <= 254:
         raise ValueError(f"ink_max={ink_max!r}: an integer in 0..254")
-    if not _is_int(min_area) or min_area < 1 or min_area >= 2 ** 31:
+    if not is_int(min_area) or min_area < 1 or min_area >= 2 ** 31:
         raise ValueError(f"min_area={min_area!r}: an integer >= 1")
     for name, g in (("gap_x", gap_x), ("gap_y", gap_y)):
-        if not _is_int(g) or not 0 <= g <= MAX_GAP:
+        if not is_int(g) or not 0 <= g <= MAX_GAP:
             raise ValueError(f"{name}={g!r}: an integer in 0..{MAX_GAP}")
 
 
@@ -136,25 +132,10 @@ def _boxes_host(ink, gap_x, gap_y, min_area):
 
 
 def _host_inks(pk, ink_max):
-    for o, h, w in zip(pk.offset, pk.h, pk.w):
-        page = pk.store[int(o):int(o) + int(h) * int(w)].view(int(h), int(w))
-        yield (page if page.dtype == torch.uint8 else quantise_u8(page)).numpy() <= ink_max
-
-
-def _packed_host(pk, pages, dtype):
-    res = torch.empty(pk.store.numel(), dtype=dtype)
-    for o, page in zip(pk.offset, pages):
-        res[int(o):int(o) + page.size] = torch.from_numpy(page).reshape(-1)
-    return res
+    return (v <= ink_max for v in host_pages(pk))
 
 
 # ---------------------------------------------------------------------------------------------------------------- the device path
-def _device_store(pk, dev):
-    from . import ops
-    store = pk.store.to(dev) if pk.store.dtype == torch.uint8 else pk.store.to(dev, torch.float32)
-    return store, ops.binarize_page_table(pk.offset, pk.h, pk.w, dev)
-
-
 def despeckle_store(store, table, min_area, connectivity=8, ink_max=127, out="float"):
     """The device sequence over a packed store that is already on the device (binarize_pages hands its result over without unpacking):
     label (3 launches), stats, apply -> the packed result.  Nothing synchronises."""
@@ -162,16 +143,14 @@ def despeckle_store(store, table, min_area, connectivity=8, ink_max=127, out="fl
     area = torch.empty(store.numel(), dtype=torch.int32, device=store.device)
     labels = ops.cc_label(store, table, connectivity, ink_max, area=area)
     ops.cc_stats(store, table, labels, area)
-    res = torch.empty(store.numel(), dtype=torch.uint8 if out == "u8" else torch.float32, device=store.device)
-    ops.cc_despeckle(store, table, labels, area, min_area, **{"out_u8" if out == "u8" else "out_f32": res})
+    res, outs = packed_result(store.numel(), out, store.device)
+    ops.cc_despeckle(store, table, labels, area, min_area, **outs)
     return res
 
 
 def despeckle_store_host(pk, min_area, connectivity=8, ink_max=127, out="float"):
     """the same over a packed store on the host"""
-    hi, dt = (255, np.uint8) if out == "u8" else (1.0, np.float32)
-    return _packed_host(pk, [np.where(_despeckle_host(ink, min_area, connectivity), 0, hi).astype(dt) for ink in _host_inks(pk, ink_max)],
-                        torch.uint8 if out == "u8" else torch.float32)
+    return pack_ink_host(pk, (_despeckle_host(ink, min_area, connectivity) for ink in _host_inks(pk, ink_max)), out)
 
 
 def _device_tables(pk, store, table, labels, area, min_area):
@@ -192,14 +171,8 @@ def _device_tables(pk, store, table, labels, area, min_area):
     return [rows[a:b] for a, b in zip(first[:-1], first[1:])]
 
 
-def _prepare(pages, device):
-    from .binarize import _check_sizes
-    _check_sizes(pages)
-    pk = pack_pages(pages)
-    dev = torch.device(device) if device is not None else pk.store.device
-    if dev.type != "cuda":
-        pk = pk._replace(store=pk.store.cpu())
-    return pk, dev
+def _open(pages, device):
+    return open_store(pages, device, max_pixels=MAX_PAGE_PIXELS)      # labels are int32 indices into a page
 
 
 # ---------------------------------------------------------------------------------------------------------------- the interface
@@ -207,23 +180,21 @@ def label_pages(pages, connectivity=8, ink_max=127, device=None):
     """pages as for binarize_pages -> a list of int32 [h, w]: the smallest page-relative index of each ink pixel's component, -1 for
     background; on `device` if given, else where the pages are"""
     check_params(connectivity, ink_max)
-    pk, dev = _prepare(pages, device)
+    pk, dev, store, table = _open(pages, device)
     if dev.type == "cuda":
         from . import ops
-        store, table = _device_store(pk, dev)
         res = ops.cc_label(store, table, connectivity, ink_max)
     else:
-        res = _packed_host(pk, [_labels_host(ink, connectivity) for ink in _host_inks(pk, ink_max)], torch.int32)
+        res = pack_host(pk, [_labels_host(ink, connectivity) for ink in _host_inks(pk, ink_max)], torch.int32)
     return [v.view(v.shape[-2], v.shape[-1]) for v in unpack_pages(res, pk)]
 
 
 def page_components(pages, connectivity=8, ink_max=127, device=None):
     """-> per page int32 [n, 6] = (root, area, x_min, y_min, x_max, y_max), inclusive, rows ascending by root"""
     check_params(connectivity, ink_max)
-    pk, dev = _prepare(pages, device)
+    pk, dev, store, table = _open(pages, device)
     if dev.type == "cuda":
         from . import ops
-        store, table = _device_store(pk, dev)
         area = torch.empty(store.numel(), dtype=torch.int32, device=dev)
         labels = ops.cc_label(store, table, connectivity, ink_max, area=area)
         ops.cc_stats(store, table, labels, area)
@@ -236,9 +207,8 @@ def despeckle_pages(pages, min_area, connectivity=8, ink_max=127, out="float", d
     min_area pixels stays ink, everything else is background.  min_area = 1 only binarises at ink_max."""
     _check_out(out)
     check_params(connectivity, ink_max, min_area)
-    pk, dev = _prepare(pages, device)
+    pk, dev, store, table = _open(pages, device)
     if dev.type == "cuda":
-        store, table = _device_store(pk, dev)
         res = despeckle_store(store, table, min_area, connectivity, ink_max, out)
     else:
         res = despeckle_store_host(pk, min_area, connectivity, ink_max, out)
@@ -249,10 +219,9 @@ def word_boxes(pages, gap_x=8, gap_y=0, min_area=16, ink_max=127, device=None):
     """-> per page int32 [n, 4] = (x_min, y_min, x_max, y_max), inclusive: the bounding boxes of the 8-connected components of the page
     smeared by gap_x along rows and then gap_y along columns, whose smeared area is at least min_area, in ascending root order"""
     check_params(8, ink_max, min_area, gap_x, gap_y)
-    pk, dev = _prepare(pages, device)
+    pk, dev, store, table = _open(pages, device)
     if dev.type == "cuda":
         from . import ops
-        store, table = _device_store(pk, dev)
         mask = None
         if gap_x:
             mask = ops.cc_smear(store, table, gap_x, False, ink_max)

@@ -23,43 +23,30 @@ import math
 import numpy as np
 import torch
 
-from ._lib import QeaError
-from .pages import _check_out, norm_table, pack_pages, quantise_u8, unpack_pages
+from .pages import _check_out, host_pages, is_int, norm_table, open_store, pack_host, packed_result, unpack_pages
 
 MAX_SIDE, MAX_PAGE_PIXELS, MAX_SLOPE, MAX_GAIN = 32767, 1 << 27, 256, 10000
 INTERPS = ("bilinear", "nearest")
 
 
-def _is_int(v):
-    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
-
-
 def check_params(max_slope=90, ink="otsu", min_gain=0, interp="bilinear", fill=255):
     """ValueError for parameters outside the statement's ranges, before any work"""
-    if not _is_int(max_slope) or not 0 <= max_slope <= MAX_SLOPE:
+    if not is_int(max_slope) or not 0 <= max_slope <= MAX_SLOPE:
         raise ValueError(f"max_slope={max_slope!r}: an integer in 0..{MAX_SLOPE} (1024ths)")
-    if ink != "otsu" and (not _is_int(ink) or not 0 <= ink <= 254):
+    if ink != "otsu" and (not is_int(ink) or not 0 <= ink <= 254):
         raise ValueError(f"ink={ink!r}: 'otsu' or an integer in 0..254")
-    if not _is_int(min_gain) or not 0 <= min_gain <= MAX_GAIN:
+    if not is_int(min_gain) or not 0 <= min_gain <= MAX_GAIN:
         raise ValueError(f"min_gain={min_gain!r}: an integer in 0..{MAX_GAIN} (per cent)")
     if interp not in INTERPS:
         raise ValueError(f"interp={interp!r}: one of {INTERPS}")
-    if not _is_int(fill) or not 0 <= fill <= 255:
+    if not is_int(fill) or not 0 <= fill <= 255:
         raise ValueError(f"fill={fill!r}: an integer in 0..255")
-
-
-def _check_sizes(pages):
-    """before anything is packed or copied"""
-    for i, p in enumerate(pages):
-        shape = tuple(getattr(p, "shape", ()))
-        if len(shape) >= 2 and (max(shape[-2:]) > MAX_SIDE or int(shape[-2]) * int(shape[-1]) > MAX_PAGE_PIXELS):
-            raise QeaError(f"page {i}: {shape[-2]} x {shape[-1]} has a side over {MAX_SIDE} or more than 2^27 pixels")
 
 
 def rotation_table(A):
     """-> int32 numpy [2 A + 1, 2]: row a + A = (C16, S16) = (round(65536 / n), round(65536 t / n)), t = a / 1024, n = sqrt(1 + t t) in
     fp64.  The kernel and the host path read it as data."""
-    if not _is_int(A) or not 0 <= A <= MAX_SLOPE:
+    if not is_int(A) or not 0 <= A <= MAX_SLOPE:
         raise ValueError(f"A={A!r}: an integer in 0..{MAX_SLOPE}")
     rows = []
     for a in range(-A, A + 1):
@@ -139,16 +126,10 @@ def _rotate_host(v, a, table, interp, fill, rows=256):
     return out
 
 
-def _host_pages(pk):
-    for o, h, w in zip(pk.offset, pk.h, pk.w):
-        page = pk.store[int(o):int(o) + int(h) * int(w)].view(int(h), int(w))
-        yield (page if page.dtype == torch.uint8 else quantise_u8(page)).numpy()
-
-
 def _estimate_host(pk, A, ink, g):
     from .binarize import otsu_threshold_of_hist
     scores = np.zeros((len(pk.h), 2 * A + 1), np.int64)
-    for i, v in enumerate(_host_pages(pk)):
+    for i, v in enumerate(host_pages(pk)):
         ink_max = otsu_threshold_of_hist(np.bincount(v.reshape(-1), minlength=256)) if ink == "otsu" else ink
         scores[i] = _scores_host(_strip_sums_host(v, ink_max), v.shape[1], A)
     return pick_slopes(scores, g), scores
@@ -156,19 +137,11 @@ def _estimate_host(pk, A, ink, g):
 
 def _rotate_pages_host(pk, slopes, A, interp, fill, out):
     table = rotation_table(A)
-    res = torch.empty(pk.store.numel(), dtype=torch.uint8)
-    for o, a, v in zip(pk.offset, slopes, _host_pages(pk)):
-        res[int(o):int(o) + v.size] = torch.from_numpy(_rotate_host(v, int(a), table, interp, fill)).reshape(-1)
+    res = pack_host(pk, (_rotate_host(v, int(a), table, interp, fill) for a, v in zip(slopes, host_pages(pk))), torch.uint8)
     return res if out == "u8" else norm_table()[res.long()]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the device path
-def _device_store(pk, dev):
-    from . import ops
-    store = pk.store.to(dev) if pk.store.dtype == torch.uint8 else pk.store.to(dev, torch.float32)
-    return store, ops.binarize_page_table(pk.offset, pk.h, pk.w, dev)
-
-
 def _estimate_device(store, table, A, ink, g):
     """three launches of csrc/deskew.hip (after Otsu's two for ink="otsu") -> (slopes, scores) on the device; nothing is read back"""
     from . import ops
@@ -181,12 +154,9 @@ def _estimate_device(store, table, A, ink, g):
 
 def _rotate_device(store, table, slopes, A, interp, fill, out):
     from . import ops
-    res = torch.empty(store.numel(), dtype=torch.uint8 if out == "u8" else torch.float32, device=store.device)
+    res, outs = packed_result(store.numel(), out, store.device)
     rot = torch.from_numpy(rotation_table(A)).to(store.device)
-    if out == "u8":
-        ops.deskew_rotate(store, table, slopes, rot, interp, fill, out_u8=res)
-    else:
-        ops.deskew_rotate(store, table, slopes, rot, interp, fill, norm=norm_table().to(store.device), out_f32=res)
+    ops.deskew_rotate(store, table, slopes, rot, interp, fill, norm=None if out == "u8" else norm_table().to(store.device), **outs)
     return res
 
 
@@ -197,11 +167,8 @@ def _given_slopes(slopes, n, A):
     return s.astype(np.int32)
 
 
-def _pack(pages, device):
-    _check_sizes(pages)
-    pk = pack_pages(pages)
-    dev = torch.device(device) if device is not None else pk.store.device
-    return (pk if dev.type == "cuda" else pk._replace(store=pk.store.cpu())), dev
+def _open(pages, device):
+    return open_store(pages, device, MAX_SIDE, MAX_PAGE_PIXELS)
 
 
 def estimate_skew(pages, max_slope=90, ink="otsu", min_gain=0, device=None):
@@ -211,9 +178,9 @@ def estimate_skew(pages, max_slope=90, ink="otsu", min_gain=0, device=None):
     the path of qea/binarize.py (on the device its two launches run first and t* is read by the strip-sum kernel there; the binarised
     image that path also writes is discarded).  A page of a single grey level has no ink and gets slope 0."""
     check_params(max_slope, ink, min_gain)
-    pk, dev = _pack(pages, device)
+    pk, dev, store, table = _open(pages, device)
     if dev.type == "cuda":
-        return _estimate_device(*_device_store(pk, dev), int(max_slope), ink, int(min_gain))
+        return _estimate_device(store, table, int(max_slope), ink, int(min_gain))
     slopes, scores = _estimate_host(pk, int(max_slope), ink, int(min_gain))
     return torch.from_numpy(slopes), torch.from_numpy(scores)
 
@@ -226,11 +193,10 @@ def deskew_pages(pages, max_slope=90, ink="otsu", min_gain=0, interp="bilinear",
     _check_out(out)
     check_params(max_slope, ink, min_gain, interp, fill)
     A = int(max_slope)
-    pk, dev = _pack(pages, device)
+    pk, dev, store, table = _open(pages, device)
     if slopes is not None:
         slopes = torch.from_numpy(_given_slopes(slopes, len(pk.h), A))
     if dev.type == "cuda":
-        store, table = _device_store(pk, dev)
         slopes = _estimate_device(store, table, A, ink, int(min_gain))[0] if slopes is None else slopes.to(dev)
         res = _rotate_device(store, table, slopes, A, interp, int(fill), out)
     else:

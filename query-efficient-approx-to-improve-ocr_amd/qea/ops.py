@@ -1135,8 +1135,7 @@ def page_tiles_gather(store, offset, h, w, rows, out, table=None):
     """include/qea_hip.h: qea_page_tiles_gather — the packed pages `store` (uint8 with the 256-entry fp32 `table`, or fp32), their element
     offset (int64 [n]) and h / w (int32 [n]), the tile rows (int32 [N][3] = page, oy, ox) -> out [N,1,TH,TW] fp32, white outside a page,
     written whole by ONE launch on the current stream."""
-    if store.dtype not in (torch.uint8, torch.float32) or store.dim() != 1:
-        raise _lib.QeaError("page_tiles_gather needs a one-dimensional uint8 or float32 store")
+    _page_store("page_tiles_gather", store)
     if store.dtype == torch.uint8 and table is None:
         raise _lib.QeaError("page_tiles_gather: a uint8 store needs the 256-entry fp32 table")
     (offset, h, w, rows, out, store_p, *table_p), n, tile = _page_tables(
@@ -1210,9 +1209,9 @@ BINARIZE_LAUNCHES = {"sauvola": 0, "histogram": 0, "otsu": 0}    # launches of c
 PageTable = namedtuple("PageTable", "n host_h host_w offset h w tile_first chunk_first words")
 
 
-def binarize_page_table(offset, h, w, device):
+def page_table(offset, h, w, device):
     """The page table of a packed store (HOST arrays: element offset int64 [n], h / w int32 [n]) plus the two block-to-page prefix tables
-    of csrc/binarize.hip, in ONE upload: -> PageTable (device pointers into one int32 tensor, which it keeps alive, and the host copies
+    of csrc/page_store.h (32 x 64 tiles, chunks of 32768 elements), in ONE upload: -> PageTable (device pointers into one int32 tensor, which it keeps alive, and the host copies
     of h / w the entry points validate).  Page sizes are checked by the entry points, not here."""
     if torch.device(device).type != "cuda":
         raise _lib.QeaError(f"the binarisation kernels need a CUDA device (qea/binarize.py has the host path), not {device}")
@@ -1231,22 +1230,34 @@ def binarize_page_table(offset, h, w, device):
     return PageTable(n, h, w, *(int(a) for a in at), words)
 
 
-def _binarize_args(who, store, table, *outs):
-    """-> the leading arguments the three entry points of csrc/binarize.hip share; outs: (name, tensor or None, dtype), as large as the store"""
+def _page_store(who, store, table=None):
+    """the packed store of every page entry point: one-dimensional, uint8 or float32, on a CUDA device, and on its page table's if one is given"""
     if not torch.is_tensor(store) or store.dtype not in (torch.uint8, torch.float32) or store.dim() != 1 or not store.is_cuda:
         raise _lib.QeaError(f"{who} needs a one-dimensional uint8 or float32 CUDA store")
-    if table.words.device != store.device:
+    if table is not None and table.words.device != store.device:
         raise _lib.QeaError(f"{who}: the page table is on {table.words.device}, the store on {store.device}")
-    _tensors(who, store.device, ("store", store, store.dtype), *((name, t, dt, store.numel()) for name, t, dt in outs if t is not None))
-    return (store.data_ptr(), int(store.dtype == torch.float32), store.numel(), table.offset, table.h, table.w, table.n,
-            table.host_h.ctypes.data, table.host_w.ctypes.data)
+
+
+def _page_ptrs(who, store, table, *specs):
+    """ONE _tensors pass over the checked store (it adds: contiguous) and the caller's `specs` -> (the seven arguments that lead every entry
+    point over a store: store, store_is_f32, store_elems, offset, h, w, n_pages; the pointers of specs)"""
+    ptrs = _tensors(who, store.device, ("store", store, store.dtype), *specs)
+    return (ptrs[0], int(store.dtype == torch.float32), store.numel(), table.offset, table.h, table.w, table.n), ptrs[1:]
+
+
+def _page_args(who, store, table, *outs):
+    """-> the nine leading arguments of the entry points that also take the host's copy of h / w; outs: (name, tensor or None, dtype), as
+    large as the store"""
+    _page_store(who, store, table)
+    lead, _ = _page_ptrs(who, store, table, *((name, t, dt, store.numel()) for name, t, dt in outs if t is not None))
+    return lead + (table.host_h.ctypes.data, table.host_w.ctypes.data)
 
 
 def binarize_sauvola(store, table, window=25, k=0.2, R=128.0, out_f32=None, out_u8=None):
-    """include/qea_hip.h: qea_binarize_sauvola — every page of the packed `store` (uint8 or fp32; `table`: binarize_page_table) through
+    """include/qea_hip.h: qea_binarize_sauvola — every page of the packed `store` (uint8 or fp32; `table`: page_table) through
     Sauvola's rule in ONE launch on the current stream: 0 / 0.0 for ink, 255 / 1.0 for background into out_u8 and / or out_f32, packed
     like the store."""
-    args = _binarize_args("binarize_sauvola", store, table, ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
+    args = _page_args("binarize_sauvola", store, table, ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
     _lib.check(_lib.lib().qea_binarize_sauvola(*args, table.tile_first, int(window), float(k), float(R), _ptr(out_f32), _ptr(out_u8), _stream()),
                "qea_binarize_sauvola")
     BINARIZE_LAUNCHES["sauvola"] += 1
@@ -1255,7 +1266,7 @@ def binarize_sauvola(store, table, window=25, k=0.2, R=128.0, out_f32=None, out_
 def otsu_histogram(store, table):
     """include/qea_hip.h: qea_otsu_histogram — launch 1 of Otsu -> the pages' grey-level counts, int32 [n][256] on the device (the entry
     point zeroes the table itself)."""
-    args = _binarize_args("otsu_histogram", store, table)
+    args = _page_args("otsu_histogram", store, table)
     hist = torch.empty(table.n, 256, dtype=torch.int32, device=store.device)
     _lib.check(_lib.lib().qea_otsu_histogram(*args, table.chunk_first, hist.data_ptr(), _stream()), "qea_otsu_histogram")
     BINARIZE_LAUNCHES["histogram"] += 1
@@ -1265,7 +1276,7 @@ def otsu_histogram(store, table):
 def binarize_otsu(store, table, hist, out_f32=None, out_u8=None):
     """include/qea_hip.h: qea_binarize_otsu — launch 2 of Otsu: every workgroup derives its page's threshold from `hist` (otsu_histogram)
     and writes ink as 0 / 0.0, background as 255 / 1.0 -> the thresholds, int32 [n] on the device (-1: a page of one grey level)."""
-    args = _binarize_args("binarize_otsu", store, table, ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
+    args = _page_args("binarize_otsu", store, table, ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
     (hist_p,) = _tensors("binarize_otsu", store.device, ("hist", hist, torch.int32, table.n * 256))
     thresholds = torch.empty(table.n, dtype=torch.int32, device=store.device)
     _lib.check(_lib.lib().qea_binarize_otsu(*args, table.chunk_first, hist_p, _ptr(out_f32), _ptr(out_u8), thresholds.data_ptr(), _stream()),
@@ -1291,7 +1302,7 @@ def cc_label(store, table, connectivity=8, ink_max=127, ink_mask=None, labels=No
     """include/qea_hip.h: qea_cc_label — three launches (tile, border, flatten) on the current stream -> labels, int32 packed like the
     store: an ink pixel's label is the smallest page-relative index of its component, background is -1.  `ink_mask` (uint8, packed like
     the store) replaces the ink_max threshold; `area` (int32, packed like the store) is cleared inside the pages for cc_stats."""
-    args = _binarize_args("cc_label", store, table)
+    args = _page_args("cc_label", store, table)
     labels = _cc_buffer("cc_label", store, "labels", labels)
     if ink_mask is not None:
         _tensors("cc_label", store.device, ("ink_mask", ink_mask, torch.uint8, store.numel()))
@@ -1307,7 +1318,7 @@ def cc_label(store, table, connectivity=8, ink_max=127, ink_mask=None, labels=No
 def cc_stats(store, table, labels, area):
     """include/qea_hip.h: qea_cc_stats — one launch: adds every component's pixel count to area[its root]; `area` is the buffer cc_label
     cleared -> area"""
-    args = _binarize_args("cc_stats", store, table, ("labels", labels, torch.int32), ("area", area, torch.int32))
+    args = _page_args("cc_stats", store, table, ("labels", labels, torch.int32), ("area", area, torch.int32))
     _lib.check(_lib.lib().qea_cc_stats(*args, table.tile_first, labels.data_ptr(), area.data_ptr(), _stream()), "qea_cc_stats")
     COMPONENT_LAUNCHES["stats"] += 1
     return area
@@ -1316,7 +1327,7 @@ def cc_stats(store, table, labels, area):
 def cc_despeckle(store, table, labels, area, min_area, out_f32=None, out_u8=None):
     """include/qea_hip.h: qea_cc_despeckle — one launch: ink of components of at least min_area pixels as 0 / 0.0, everything else as
     255 / 1.0 into out_u8 and / or out_f32, packed like the store."""
-    args = _binarize_args("cc_despeckle", store, table, ("labels", labels, torch.int32), ("area", area, torch.int32),
+    args = _page_args("cc_despeckle", store, table, ("labels", labels, torch.int32), ("area", area, torch.int32),
                           ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
     _lib.check(_lib.lib().qea_cc_despeckle(*args, table.tile_first, labels.data_ptr(), area.data_ptr(), int(min_area), _ptr(out_f32),
                                            _ptr(out_u8), _stream()), "qea_cc_despeckle")
@@ -1326,7 +1337,7 @@ def cc_despeckle(store, table, labels, area, min_area, out_f32=None, out_u8=None
 def cc_smear(store, table, gap, vertical=False, ink_max=127, in_mask=None, out_mask=None):
     """include/qea_hip.h: qea_cc_smear — one launch, one direction of run-length smoothing over the ink of the store (or of `in_mask`)
     -> out_mask, uint8 1 / 0 packed like the store"""
-    args = _binarize_args("cc_smear", store, table)
+    args = _page_args("cc_smear", store, table)
     if in_mask is not None:
         _tensors("cc_smear", store.device, ("in_mask", in_mask, torch.uint8, store.numel()))
     out_mask = _cc_buffer("cc_smear", store, "out_mask", out_mask, torch.uint8)
@@ -1340,7 +1351,7 @@ def cc_boxes(store, table, labels, roots, root_first):
     """include/qea_hip.h: qea_cc_boxes — one launch.  roots: the ascending page-relative roots of all pages, int32 [n] on the device, page
     p's being roots[root_first[p]:root_first[p + 1]] (root_first: int32 [pages + 1] on the device) -> int32 [n][4] = (x_min, y_min,
     x_max, y_max) of the listed components, inclusive"""
-    args = _binarize_args("cc_boxes", store, table, ("labels", labels, torch.int32))
+    args = _page_args("cc_boxes", store, table, ("labels", labels, torch.int32))
     n = roots.numel()
     _tensors("cc_boxes", store.device, ("roots", roots, torch.int32), ("root_first", root_first, torch.int32, table.n + 1))
     boxes = torch.empty(max(n, 1), 4, dtype=torch.int32, device=store.device)      # one spare row: an empty list still has an address
@@ -1362,7 +1373,7 @@ def skew_strip_sums(store, table, ink_max=127, C=None):
     """include/qea_hip.h: qea_skew_strip_sums — one launch -> C, uint8 packed like the store: page p's C[j][y], the ink pixels of row y in
     the 32-column strip j, at offset[p] + j * h[p] + y.  ink_max: an integer 0..254, or an int32 [n] tensor on the device (-1..254 per
     page, e.g. the thresholds binarize_otsu returns), which is read by the kernel, not by the host."""
-    args = _binarize_args("skew_strip_sums", store, table)
+    args = _page_args("skew_strip_sums", store, table)
     C = _cc_buffer("skew_strip_sums", store, "C", C, torch.uint8)
     per_page = None
     if torch.is_tensor(ink_max):
@@ -1408,7 +1419,7 @@ def deskew_rotate(store, table, slopes, rot_table, interp="bilinear", fill=255, 
     [2 A + 1][2] on the device (qea/deskew.py: rotation_table); norm: the 256 fp32 values an fp32 output is read through."""
     if interp not in ("bilinear", "nearest"):
         raise _lib.QeaError(f"deskew_rotate: interp={interp!r} is neither 'bilinear' nor 'nearest'")
-    args = _binarize_args("deskew_rotate", store, table, ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
+    args = _page_args("deskew_rotate", store, table, ("out_f32", out_f32, torch.float32), ("out_u8", out_u8, torch.uint8))
     if not torch.is_tensor(rot_table) or rot_table.dim() != 2 or rot_table.shape[1] != 2 or rot_table.shape[0] % 2 != 1:
         raise _lib.QeaError("deskew_rotate: rot_table must be an int32 [2 A + 1][2] tensor")
     _tensors("deskew_rotate", store.device, ("slopes", slopes, torch.int32, table.n), ("rot_table", rot_table, torch.int32))
@@ -1426,14 +1437,11 @@ WORD_STRIP_LAUNCHES = {"strips": 0}          # launches of csrc/word_strips.hip 
 
 
 def word_strips(store, table, boxes, OW, norm, out=None):
-    """include/qea_hip.h: qea_word_strips — the packed `store` (uint8 or fp32; `table`: binarize_page_table), boxes int32 [n][5] =
+    """include/qea_hip.h: qea_word_strips — the packed `store` (uint8 or fp32; `table`: page_table), boxes int32 [n][5] =
     (page, x0, y0, x1, y1) on the device with x1 / y1 exclusive, and norm, the 256 fp32 values a grey level is written as -> out
     [n, 1, 32, OW] fp32, written whole by ONE launch on the current stream: every box clipped to its page, copied 1:1 where it has at
     most 32 rows, shrunk to 32 rows by the exact area average where it has more, centred in OW on a white ground."""
-    if not torch.is_tensor(store) or store.dtype not in (torch.uint8, torch.float32) or store.dim() != 1 or not store.is_cuda:
-        raise _lib.QeaError("word_strips needs a one-dimensional uint8 or float32 CUDA store")
-    if table.words.device != store.device:
-        raise _lib.QeaError(f"word_strips: the page table is on {table.words.device}, the store on {store.device}")
+    _page_store("word_strips", store, table)
     if not torch.is_tensor(boxes) or boxes.dim() != 2 or boxes.shape[1] != 5:
         raise _lib.QeaError("word_strips: boxes must be an int32 [n][5] tensor = (page, x0, y0, x1, y1)")
     n, OW = boxes.shape[0], int(OW)
@@ -1443,11 +1451,10 @@ def word_strips(store, table, boxes, OW, norm, out=None):
         out = torch.empty(n, 1, WORD_STRIP_H, OW, dtype=torch.float32, device=store.device)
     if out.dim() != 4 or tuple(out.shape[:3]) != (n, 1, WORD_STRIP_H) or out.shape[3] != OW:
         raise _lib.QeaError(f"word_strips: out {tuple(out.shape)} for {n} boxes at width {OW}")
-    store_p, boxes_p, norm_p, out_p = _tensors("word_strips", store.device, ("store", store, store.dtype), ("boxes", boxes, torch.int32),
-                                               ("norm", norm, torch.float32, 256), ("out", out, torch.float32))
+    args, (boxes_p, norm_p, out_p) = _page_ptrs("word_strips", store, table, ("boxes", boxes, torch.int32), ("norm", norm, torch.float32, 256),
+                                                ("out", out, torch.float32))
     if n == 0:                                                 # nothing to write, and an empty tensor has no pointer to hand over
         return out
-    _lib.check(_lib.lib().qea_word_strips(store_p, int(store.dtype == torch.float32), store.numel(), table.offset, table.h, table.w, table.n,
-                                          boxes_p, n, OW, norm_p, out_p, _stream()), "qea_word_strips")
+    _lib.check(_lib.lib().qea_word_strips(*args, boxes_p, n, OW, norm_p, out_p, _stream()), "qea_word_strips")
     WORD_STRIP_LAUNCHES["strips"] += 1
     return out

@@ -38,6 +38,8 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from ._lib import QeaError
+
 HALO = 96
 
 # Default pixels per UNet pass.  What the engine's eval-mode no-grad forward (qea/unet_engine.py) keeps alive per INPUT pixel at f = 32,
@@ -115,6 +117,83 @@ def unpack_pages(store, pk):
         v = store[int(o):int(o) + int(h) * int(w)].view(int(h), int(w))
         out.append(v[None] if d == 3 else v)
     return out
+
+
+# ---- the Python side of a packed store, shared by qea/binarize.py, components.py, deskew.py and reading.py (csrc/page_store.h is the
+# device and library side)
+def is_int(v):
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+def check_page_sizes(pages, max_side=None, max_pixels=None):
+    """QeaError for a page with a side over max_side or more than max_pixels (a power of two) pixels; None: no such bound.  Runs before
+    anything is packed or copied and looks at nothing but .shape."""
+    for i, p in enumerate(pages):
+        shape = tuple(getattr(p, "shape", ()))
+        if len(shape) < 2:
+            continue
+        h, w = int(shape[-2]), int(shape[-1])
+        over = ([f"a side over {max_side}"] if max_side and max(h, w) > max_side else []) + \
+               ([f"more than 2^{int(max_pixels).bit_length() - 1} pixels"] if max_pixels and h * w > max_pixels else [])
+        if over:
+            raise QeaError(f"page {i}: {h} x {w} has " + " and ".join(over))
+
+
+def _device_store(pk, dev):
+    """the store as the kernels read it: 8-bit as it is, anything floating as fp32"""
+    return pk.store.to(dev) if pk.store.dtype == torch.uint8 else pk.store.to(dev, torch.float32)
+
+
+def open_store(pages, device=None, max_side=None, max_pixels=None):
+    """check_page_sizes and pack_pages, then the store where the work runs -> (pk, dev, store, table).  dev is `device` if given, else
+    where the pages are.  On a CUDA dev, store is the device store and table its ops.page_table; on the host, pk.store is moved to the
+    CPU, store is pk.store and table is None."""
+    check_page_sizes(pages, max_side, max_pixels)
+    pk = pack_pages(pages)
+    dev = torch.device(device) if device is not None else pk.store.device
+    if dev.type != "cuda":
+        pk = pk._replace(store=pk.store.cpu())
+        return pk, dev, pk.store, None
+    from . import ops
+    return pk, dev, _device_store(pk, dev), ops.page_table(pk.offset, pk.h, pk.w, dev)
+
+
+def host_page(pk, p):
+    """page p of a packed host store as the statements read it: uint8 numpy [h, w] (a view of an 8-bit store, quantise_u8 of a floating one)"""
+    o, h, w = int(pk.offset[p]), int(pk.h[p]), int(pk.w[p])
+    page = pk.store[o:o + h * w].view(h, w)
+    return (page if page.dtype == torch.uint8 else quantise_u8(page)).numpy()
+
+
+def host_pages(pk):
+    """all of them, one after the other"""
+    return (host_page(pk, p) for p in range(len(pk.h)))
+
+
+def pack_host(pk, arrays, dtype):
+    """one numpy array per page, of the page's size -> a host tensor of `dtype` packed like pk.store"""
+    res = torch.empty(pk.store.numel(), dtype=dtype)
+    for o, a in zip(pk.offset, arrays):
+        res[int(o):int(o) + a.size] = torch.from_numpy(np.ascontiguousarray(a)).reshape(-1)
+    return res
+
+
+def pack_ink_host(pk, inks, out):
+    """one bool array per page -> the packed binarised result: 0 where it is set (ink), 255 for out="u8" / 1.0 for "float" elsewhere"""
+    hi, dtype = (np.uint8(255), torch.uint8) if out == "u8" else (np.float32(1.0), torch.float32)
+    return pack_host(pk, (np.where(ink, hi.dtype.type(0), hi) for ink in inks), dtype)      # in the result's type: no 8-byte detour
+
+
+def packed_result(n, out, device):
+    """-> (res, kw): the packed result of n elements for out="u8" / "float" on `device`, and the out_u8= / out_f32= keyword that hands it
+    to a wrapper of qea/ops.py"""
+    res = torch.empty(n, dtype=torch.uint8 if out == "u8" else torch.float32, device=device)
+    return res, {"out_u8" if out == "u8" else "out_f32": res}
+
+
+def require_eval(model, who):
+    if getattr(model, "training", False) or any(m.training for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)):
+        raise ValueError(f"{who} needs the model in eval mode: with batch statistics a result depends on what shares its pass")
 
 
 def plan_groups(hs, ws, tile, halo=HALO):
@@ -198,11 +277,6 @@ def clean_pages_spec(forward, pages, tile, halo=HALO, out="float", max_tile_pixe
     return unpack_pages(res, pk)
 
 
-def _require_eval(model):
-    if getattr(model, "training", False) or any(m.training for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)):
-        raise ValueError("clean_pages needs the model in eval mode: batch statistics make tiles and whole pages differ by design")
-
-
 def clean_pages(model, pages, tile=(1024, 1024), max_tile_pixels=None, out="float"):
     """pages: a list of [h, w] uint8 tensors (8-bit grey, read as p / 255) or of [h, w] / [1, h, w] float tensors, of any sizes ->
     a list of the same sizes on the model's device: for every page the model's eval-mode pass over the page padded with white to the
@@ -214,20 +288,20 @@ def clean_pages(model, pages, tile=(1024, 1024), max_tile_pixels=None, out="floa
     _check_out(out)
     for T in tile:
         _check_tile(int(T), HALO)
-    _require_eval(model)
+    require_eval(model, "clean_pages")
     budget = int(max_tile_pixels) if max_tile_pixels else MAX_TILE_PIXELS
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         with torch.no_grad():
             return clean_pages_spec(lambda x: model(x.to(dev)), pages, tile, out=out, max_tile_pixels=budget)
     pk = pack_pages(pages)
-    store = pk.store.to(dev) if pk.store.dtype == torch.uint8 else pk.store.to(dev, torch.float32)
+    store = _device_store(pk, dev)
     table = norm_table().to(dev) if store.dtype == torch.uint8 else None
     offset, h, w = (torch.from_numpy(a).to(dev) for a in (pk.offset, pk.h, pk.w))
     groups = plan_groups(pk.h, pk.w, tile)
     rows7 = torch.from_numpy(np.concatenate(list(groups.values()))).to(dev)          # every table of the call in one upload
     rows3 = rows7[:, :3].contiguous()
-    res = torch.empty(store.numel(), dtype=torch.uint8 if out == "u8" else torch.float32, device=dev)
+    res, outs = packed_result(store.numel(), out, dev)
     first = 0
     with torch.no_grad():
         for (TH, TW), rows in groups.items():
@@ -237,6 +311,6 @@ def clean_pages(model, pages, tile=(1024, 1024), max_tile_pixels=None, out="floa
                 x = torch.empty(n, 1, TH, TW, device=dev)
                 ops.page_tiles_gather(store, offset, h, w, rows3[i:i + n], x, table)
                 y = model(x).contiguous()
-                ops.page_tiles_scatter(y, rows7[i:i + n], offset, h, w, **{"out_u8" if out == "u8" else "out_f32": res})
+                ops.page_tiles_scatter(y, rows7[i:i + n], offset, h, w, **outs)
             first += len(rows)
     return unpack_pages(res, pk)

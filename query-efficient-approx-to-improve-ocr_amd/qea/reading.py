@@ -23,8 +23,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from ._lib import QeaError
-from .pages import norm_table, pack_pages, quantise_u8
+from .pages import host_page, is_int, norm_table, open_store, require_eval
 
 OH, MIN_W, MAX_W = 32, 64, 512                    # QEA_WORD_STRIP_H / _MIN_W / _MAX_W of include/qea_hip.h
 MAX_SIDE, MAX_BOXES = 32767, 1 << 20              # QEA_WORD_STRIP_MAX_SIDE / _MAX_BOXES
@@ -34,17 +33,13 @@ MAX_BEAM = 32                                     # the beam kernels' limit (uti
 Plan = namedtuple("Plan", "sw bucket cut passes")  # int32 [n], int32 [n], bool [n], [(OW, int64 box indices)]
 
 
-def _is_int(v):
-    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
-
-
 def default_buckets():
     from datasets.bucketing import BUCKETS
     return BUCKETS
 
 
 def _check_width(width):
-    if not _is_int(width) or width % 16 or not MIN_W <= width <= MAX_W:
+    if not is_int(width) or width % 16 or not MIN_W <= width <= MAX_W:
         raise ValueError(f"width={width!r}: a multiple of 16 in {MIN_W}..{MAX_W}")
 
 
@@ -57,11 +52,11 @@ def check_params(buckets=None, strip_pixels=STRIP_PIXELS, beam=0, nbest=1):
         _check_width(b)
     if any(a >= b for a, b in zip(buckets[:-1], buckets[1:])):
         raise ValueError(f"buckets={buckets!r}: strictly ascending")
-    if not _is_int(strip_pixels) or strip_pixels < 1:
+    if not is_int(strip_pixels) or strip_pixels < 1:
         raise ValueError(f"strip_pixels={strip_pixels!r}: an integer >= 1")
-    if not _is_int(beam) or not 0 <= beam <= MAX_BEAM:
+    if not is_int(beam) or not 0 <= beam <= MAX_BEAM:
         raise ValueError(f"beam={beam!r}: an integer in 0..{MAX_BEAM} (0 = greedy)")
-    if not _is_int(nbest) or not 1 <= nbest <= max(beam, 1):
+    if not is_int(nbest) or not 1 <= nbest <= max(beam, 1):
         raise ValueError(f"nbest={nbest!r}: an integer in 1..beam (1 with the greedy decode)")
     return tuple(int(b) for b in buckets)
 
@@ -147,10 +142,8 @@ def _strips_host(pk, boxes, OW):
     pages = {}
     for i in np.flatnonzero(ch > 0):
         p = int(boxes[i, 0])
-        if p not in pages:
-            o, h, w = int(pk.offset[p]), int(pk.h[p]), int(pk.w[p])
-            page = pk.store[o:o + h * w].view(h, w)
-            pages[p] = (page if page.dtype == torch.uint8 else quantise_u8(page)).numpy()
+        if p not in pages:                                     # only the pages that have a box are read
+            pages[p] = host_page(pk, p)
         crop = pages[p][y0[i]:y0[i] + ch[i], x0[i]:x0[i] + cw[i]]
         levels = crop if ch[i] <= OH else _shrink_host(crop)
         rows, cols = levels.shape
@@ -161,29 +154,13 @@ def _strips_host(pk, boxes, OW):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the interface
-def _check_sizes(pages):
-    """before anything is packed or copied"""
-    for i, p in enumerate(pages):
-        shape = tuple(getattr(p, "shape", ()))
-        if len(shape) >= 2 and max(shape[-2:]) > MAX_SIDE:
-            raise QeaError(f"page {i}: {shape[-2]} x {shape[-1]} has a side over {MAX_SIDE}")
-
-
 class _Cutter:
     """The pages of a call packed once, on the device or on the host; strips(boxes, OW) cuts any subset of boxes at any width."""
 
     def __init__(self, pages, device):
-        _check_sizes(pages)
-        self.pk = pack_pages(pages)
-        self.dev = torch.device(device) if device is not None else self.pk.store.device
+        self.pk, self.dev, self.store, self.table = open_store(pages, device, max_side=MAX_SIDE)
         if self.dev.type == "cuda":
-            from . import ops
-            st = self.pk.store
-            self.store = st.to(self.dev) if st.dtype == torch.uint8 else st.to(self.dev, torch.float32)
-            self.table = ops.binarize_page_table(self.pk.offset, self.pk.h, self.pk.w, self.dev)
             self.norm = norm_table().to(self.dev)
-        else:
-            self.pk = self.pk._replace(store=self.pk.store.cpu())
 
     def strips(self, boxes, OW):
         if self.dev.type == "cuda":
@@ -200,11 +177,6 @@ def word_strips(pages, boxes, width, device=None):
     return _Cutter(pages, device).strips(_box_table(boxes), int(width))
 
 
-def _require_eval(model):
-    if getattr(model, "training", False) or any(m.training for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)):
-        raise ValueError("read_pages needs the model in eval mode: with batch statistics a word would read differently from pass to pass")
-
-
 def read_pages(model, pages, boxes_per_page, index_to_char, buckets=None, strip_pixels=STRIP_PIXELS, beam=0, nbest=1, lm=None,
                lm_weight=1.0, lm_bonus=0.0, lexicon=None, forward=None):
     """pages as for word_strips; boxes_per_page: per page an integer table [n_p, 4] = (x_min, y_min, x_max, y_max), INCLUSIVE, as
@@ -217,7 +189,7 @@ def read_pages(model, pages, boxes_per_page, index_to_char, buckets=None, strip_
     from utils import _check_beam_arguments, pred_to_string
     buckets = check_params(buckets, strip_pixels, beam, nbest)
     _check_beam_arguments("read_pages", beam, lm, lexicon)
-    _require_eval(model)
+    require_eval(model, "read_pages")
     if len(boxes_per_page) != len(pages):
         raise ValueError(f"{len(boxes_per_page)} box tables for {len(pages)} pages")
     table = box_table(boxes_per_page)

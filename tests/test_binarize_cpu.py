@@ -196,7 +196,7 @@ def test_ops_need_a_device():
     from qea import _lib, ops
     assert set(ops.BINARIZE_LAUNCHES) == {"sauvola", "histogram", "otsu"}
     with pytest.raises(_lib.QeaError):
-        ops.binarize_page_table(np.zeros(1, np.int64), np.ones(1, np.int32), np.ones(1, np.int32), torch.device("cpu"))
+        ops.page_table(np.zeros(1, np.int64), np.ones(1, np.int32), np.ones(1, np.int32), torch.device("cpu"))
 
 
 def test_flags_of_the_two_front_ends():

@@ -79,7 +79,7 @@ def test_sauvola_is_the_statement_bit_for_bit(reference, dtype, out):
     from qea import ops
     ref = reference(dtype)
     store = ref["store"].cuda()
-    table = ops.binarize_page_table(ref["offset"], ref["h"], ref["w"], store.device)
+    table = ops.page_table(ref["offset"], ref["h"], ref["w"], store.device)
     inside = _inside(ref)
     for win in WINDOWS:
         for k in KS:
@@ -90,7 +90,7 @@ def test_sauvola_is_the_statement_bit_for_bit(reference, dtype, out):
             ops.binarize_sauvola(store, table, win, k, 128.0, **{key: res})
             assert sum(ops.BINARIZE_LAUNCHES.values()) == sum(before.values()) + 1 and ops.BINARIZE_LAUNCHES["sauvola"] == before["sauvola"] + 1
             _check(res, ref, want, out, inside)
-    one = ops.binarize_page_table(ref["offset"][2:3], ref["h"][2:3], ref["w"][2:3], store.device)      # one page: one launch as well
+    one = ops.page_table(ref["offset"][2:3], ref["h"][2:3], ref["w"][2:3], store.device)      # one page: one launch as well
     before = sum(ops.BINARIZE_LAUNCHES.values())
     res, key = _outputs(store.numel(), out)
     ops.binarize_sauvola(store, one, 25, 0.2, 128.0, **{key: res})
@@ -107,7 +107,7 @@ def test_otsu_is_the_statement_bit_for_bit(reference, dtype, out):
     from qea import ops
     ref = reference(dtype)
     store = ref["store"].cuda()
-    table = ops.binarize_page_table(ref["offset"], ref["h"], ref["w"], store.device)
+    table = ops.page_table(ref["offset"], ref["h"], ref["w"], store.device)
     res, key = _outputs(store.numel(), out)
     before = dict(ops.BINARIZE_LAUNCHES)
     hist = ops.otsu_histogram(store, table)
@@ -193,7 +193,7 @@ def test_library_refusals_launch_nothing():
     from qea import _lib, ops
     L = _lib.lib()
     store = torch.randint(0, 256, (64,), dtype=torch.uint8, device="cuda")
-    table = ops.binarize_page_table(np.zeros(1, np.int64), np.asarray([8], np.int32), np.asarray([8], np.int32), store.device)
+    table = ops.page_table(np.zeros(1, np.int64), np.asarray([8], np.int32), np.asarray([8], np.int32), store.device)
     out = torch.full((64,), 0x5A, dtype=torch.uint8, device="cuda")
     outf = torch.full((65,), -7.0, device="cuda")
     hist = torch.full((256,), 3, dtype=torch.int32, device="cuda")

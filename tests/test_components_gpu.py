@@ -56,7 +56,7 @@ def test_labels_areas_and_despeckle_are_the_statement_bit_for_bit(dtype, connect
         assert np.array_equal(spec.ink_of(store[int(o):int(o) + ink.size].view(ink.shape).numpy()), ink)
     n = store.numel()
     store = store.cuda()
-    table = ops.binarize_page_table(offset, h, w, store.device)
+    table = ops.page_table(offset, h, w, store.device)
     labels = torch.full((n,), LABEL_SENTINEL, dtype=torch.int32, device="cuda")
     area = torch.full((n,), AREA_SENTINEL, dtype=torch.int32, device="cuda")
     before = dict(ops.COMPONENT_LAUNCHES)
@@ -222,7 +222,7 @@ def test_library_refusals_launch_nothing():
     g = torch.Generator().manual_seed(3)
     page = torch.randint(0, 256, (8, 8), generator=g, dtype=torch.uint8)
     store = page.reshape(-1).cuda()
-    table = ops.binarize_page_table(np.zeros(1, np.int64), np.asarray([8], np.int32), np.asarray([8], np.int32), store.device)
+    table = ops.page_table(np.zeros(1, np.int64), np.asarray([8], np.int32), np.asarray([8], np.int32), store.device)
     labels = torch.full((64,), LABEL_SENTINEL, dtype=torch.int32, device="cuda")
     area = torch.full((64,), AREA_SENTINEL, dtype=torch.int32, device="cuda")
     out = torch.full((64,), 0x5A, dtype=torch.uint8, device="cuda")

@@ -58,7 +58,7 @@ def test_sums_scores_slopes_and_pages_are_the_statement_bit_for_bit(kind, A):
     n = host.numel()
     store = _on_device(host)
     assert store.data_ptr() % 16 != 0 and store.is_contiguous()
-    table = ops.binarize_page_table(offset, h, w, store.device)
+    table = ops.page_table(offset, h, w, store.device)
     Cs = torch.full((n,), C_SENTINEL, dtype=torch.uint8, device="cuda")
     scores = torch.full((len(NAMES), 2 * A + 1), SCORE_SENTINEL, dtype=torch.int64, device="cuda")
     slopes = torch.full((len(NAMES),), SLOPE_SENTINEL, dtype=torch.int32, device="cuda")
@@ -103,7 +103,7 @@ def test_where_32_bits_overflow():
     names = sorted(large_pages())
     pk = pack_pages([torch.from_numpy(large_pages()[n]) for n in names])
     store = pk.store.cuda()
-    table = ops.binarize_page_table(pk.offset, pk.h, pk.w, store.device)
+    table = ops.page_table(pk.offset, pk.h, pk.w, store.device)
     scores = ops.skew_scores(ops.skew_strip_sums(store, table, 127), table, LARGE_A)
     slopes = ops.skew_pick(scores)
     rot = torch.from_numpy(rotation_table(LARGE_A)).cuda()
@@ -146,7 +146,7 @@ def test_per_page_ink_comes_from_the_device_otsu_thresholds():
         host, offset, h, w = _store(kind)
         pages = u8_pages() if kind == "u8" else float_pages()
         store = _on_device(host)
-        table = ops.binarize_page_table(offset, h, w, store.device)
+        table = ops.page_table(offset, h, w, store.device)
         scratch = torch.empty(host.numel(), dtype=torch.uint8, device="cuda")
         thresholds = ops.binarize_otsu(store, table, ops.otsu_histogram(store, table), out_u8=scratch)
         assert thresholds.is_cuda
@@ -214,7 +214,7 @@ def test_library_refusals_launch_nothing():
     page = spec.sheared_text_page(61, 2, 40, 45)
     store = torch.from_numpy(page.reshape(-1)).cuda()
     n = store.numel()
-    table = ops.binarize_page_table(np.zeros(1, np.int64), np.asarray([40], np.int32), np.asarray([45], np.int32), store.device)
+    table = ops.page_table(np.zeros(1, np.int64), np.asarray([40], np.int32), np.asarray([45], np.int32), store.device)
     Cs = torch.full((n,), C_SENTINEL, dtype=torch.uint8, device="cuda")
     scores = torch.full((1, 181), SCORE_SENTINEL, dtype=torch.int64, device="cuda")
     slopes = torch.full((1,), SLOPE_SENTINEL, dtype=torch.int32, device="cuda")

@@ -229,3 +229,66 @@ def test_clean_cli_and_eval_prep_flags():
     assert v.parse_args([]).tile is None and v.parse_args(["--tile", "320", "320"]).tile == [320, 320]
     for tag in "pacer":
         assert not hasattr(build_parser(tag, "").parse_args([] if tag != "r" else ["--cers_tess_path", "x"]), "tile")
+
+
+def test_packed_store_helpers():
+    """the Python side of a packed store (qea/pages.py): the size bounds each caller asks for, seen through .shape alone; open_store on the
+    host; host_pages and pack_host as a round trip"""
+    from types import SimpleNamespace
+    from qea._lib import QeaError
+    from qea.pages import (check_page_sizes, host_page, host_pages, is_int, open_store, pack_host, pack_ink_host, pack_pages, packed_result,
+                           quantise_u8, require_eval)
+    stub = lambda *shape: SimpleNamespace(shape=shape)          # nothing behind it: only .shape may be looked at
+    ok, wide, huge, both = stub(400, 512), stub(2, 32768), stub(1 << 14, (1 << 13) + 1), stub(1, 40000, 4000)
+    for bounds in (dict(), dict(max_pixels=1 << 27), dict(max_side=32767, max_pixels=1 << 27), dict(max_side=32767)):
+        check_page_sizes([ok, stub(1, 1), stub(1, 32767, 4096), stub(7), object()], **bounds)
+    check_page_sizes([wide], max_pixels=1 << 27)                # binarize and components: pixels only
+    check_page_sizes([huge], max_side=32767)                    # reading: sides only
+    check_page_sizes([wide, huge, both])                        # no bound at all
+    for pages, bounds, words in (([ok, huge], dict(max_pixels=1 << 27), ["page 1", "16384 x 8193", "2^27"]),
+                                 ([huge], dict(max_side=32767, max_pixels=1 << 27), ["page 0", "2^27"]),
+                                 ([ok, ok, wide], dict(max_side=32767, max_pixels=1 << 27), ["page 2", "2 x 32768", "32767"]),
+                                 ([wide], dict(max_side=32767), ["32767"]),
+                                 ([both], dict(max_side=32767, max_pixels=1 << 27), ["40000 x 4000", "32767", "2^27"])):
+        with pytest.raises(QeaError) as e:
+            check_page_sizes(pages, **bounds)
+        assert all(word in str(e.value) for word in words), (str(e.value), words)
+    with pytest.raises(QeaError, match="32767"):
+        check_page_sizes([wide], 32767, 1 << 27)                # the positional order deskew uses
+    assert is_int(3) and is_int(np.int32(3)) and not is_int(True) and not is_int(3.0) and not is_int("3")
+
+    g = torch.Generator().manual_seed(8)
+    grey = [torch.randint(0, 256, s, generator=g, dtype=torch.uint8) for s in ((3, 5), (1, 1), (4, 2))]
+    real = [torch.rand(1, 3, 5, generator=g, dtype=torch.float64) * 1.5 - 0.25, torch.rand(2, 2, generator=g, dtype=torch.float64)]
+    for pages in (grey, real):
+        pk, dev, store, table = open_store(pages, None, 32767, 1 << 27)
+        assert dev.type == "cpu" and store is pk.store and table is None and store.dtype == pages[0].dtype
+        assert pk.offset.tolist() == np.concatenate([[0], np.cumsum([p.shape[-2] * p.shape[-1] for p in pages])[:-1]]).tolist()
+        views = list(host_pages(pk))
+        for p, (page, v) in enumerate(zip(pages, views)):
+            assert v.dtype == np.uint8 and v.shape == tuple(page.shape[-2:]) and np.array_equal(v, host_page(pk, p))
+            assert np.array_equal(v, (page if page.dtype == torch.uint8 else quantise_u8(page)).reshape(v.shape).numpy())
+        back = pack_host(pk, views, torch.uint8)                # the round trip: the packed 8-bit form of the store
+        assert back.dtype == torch.uint8 and torch.equal(back, store if store.dtype == torch.uint8 else quantise_u8(store))
+        assert all(np.array_equal(a, b) for a, b in zip(host_pages(pk._replace(store=back)), views))
+        labels = pack_host(pk, [np.arange(v.size, dtype=np.int64).reshape(v.shape).T.copy().T for v in views], torch.int32)   # strided arrays too
+        assert labels.dtype == torch.int32 and labels.tolist() == [i for v in views for i in range(v.size)]
+        for out, hi in (("u8", 255), ("float", 1.0)):
+            ink = pack_ink_host(pk, [v <= 127 for v in views], out)
+            assert ink.dtype == (torch.uint8 if out == "u8" else torch.float32)
+            assert torch.equal(ink, torch.where(back <= 127, 0, hi).to(ink.dtype))
+    assert open_store(grey, "cpu")[1] == torch.device("cpu")
+    with pytest.raises(QeaError, match="2\\^27"):
+        open_store([torch.zeros(1, dtype=torch.uint8).expand(1 << 14, (1 << 13) + 1)], None, max_pixels=1 << 27)     # refused before it is packed
+    with pytest.raises(ValueError):
+        open_store([])
+
+    for out, dtype, key in (("u8", torch.uint8, "out_u8"), ("float", torch.float32, "out_f32")):
+        res, kw = packed_result(6, out, torch.device("cpu"))
+        assert res.dtype == dtype and res.shape == (6,) and list(kw) == [key] and kw[key] is res
+    bn = torch.nn.Sequential(torch.nn.Conv2d(1, 1, 1), torch.nn.BatchNorm2d(1))
+    require_eval(bn.eval(), "clean_pages")
+    bn[1].train()
+    for who in ("clean_pages", "read_pages"):
+        with pytest.raises(ValueError, match=f"{who}.*eval"):
+            require_eval(bn, who)

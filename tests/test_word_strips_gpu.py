@@ -47,7 +47,7 @@ def test_the_kernel_is_the_statement_bit_for_bit(kind, OW):
     from qea import ops
     store, offset, h, w = _store(kind)
     assert store.data_ptr() % 16 != 0 and store.is_contiguous()
-    table = ops.binarize_page_table(offset, h, w, store.device)
+    table = ops.page_table(offset, h, w, store.device)
     boxes = torch.from_numpy(boxes_for(OW)).cuda()
     out = torch.full((len(boxes), 1, 32, OW), SENTINEL, device="cuda")
     before = dict(ops.WORD_STRIP_LAUNCHES)
@@ -182,7 +182,7 @@ def test_library_refusals_launch_nothing():
     L = _lib.lib()
     page = u8_pages()[1]
     store = torch.from_numpy(page.reshape(-1).copy()).cuda()
-    table = ops.binarize_page_table(np.zeros(1, np.int64), np.asarray([45], np.int32), np.asarray([67], np.int32), store.device)
+    table = ops.page_table(np.zeros(1, np.int64), np.asarray([45], np.int32), np.asarray([67], np.int32), store.device)
     host_boxes = np.asarray([(0, 0, 0, 67, 45), (0, 5, 7, 60, 39)], np.int32)
     boxes = torch.from_numpy(host_boxes).cuda()
     norm = torch.from_numpy(spec.norm()).cuda()

@@ -62,7 +62,7 @@ def step(name):
         pages.append(page)
     pk = pack_pages(pages)
     store = pk.store.to(dev)
-    table = ops.binarize_page_table(pk.offset, pk.h, pk.w, dev)
+    table = ops.page_table(pk.offset, pk.h, pk.w, dev)
     out, copy = torch.empty_like(store), torch.empty_like(store)
     res = dict(workload=name, pages=len(pages), page_size=list(WORKLOADS[name][0]), pixels=int(store.numel()))
     res["copy_ms"] = _timed(torch, lambda: copy.copy_(store))

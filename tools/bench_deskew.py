@@ -76,7 +76,7 @@ def step(name):
     pages, ks = _pages(torch, name)
     pk = pack_pages(pages)
     store = pk.store.to(dev)
-    table = ops.binarize_page_table(pk.offset, pk.h, pk.w, dev)
+    table = ops.page_table(pk.offset, pk.h, pk.w, dev)
     dev_pages = unpack_pages(store, pk)
     copy = torch.empty_like(store)
     res = dict(workload=name, pages=len(pages), page_size=list(WORKLOADS[name][0]), pixels=int(store.numel()), max_slope=A, sheared_by=ks)

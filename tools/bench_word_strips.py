@@ -100,7 +100,7 @@ def step(name):
     table = reading.box_table(per_page)
     host_pages = [p.cpu() for p in pages]
     pk = pack_pages(pages)
-    store, ptable, norm = pk.store, ops.binarize_page_table(pk.offset, pk.h, pk.w, dev), norm_table().to(dev)
+    store, ptable, norm = pk.store, ops.page_table(pk.offset, pk.h, pk.w, dev), norm_table().to(dev)
     plan = reading.strip_plan(table, pk.h, pk.w)
     heights = np.minimum(table[:, 4], pk.h[table[:, 0]]) - np.maximum(table[:, 2], 0)
     res = dict(workload=name, pages=len(pages), page_size=list(WORKLOADS[name]["sizes"][0]), boxes=len(table), cut=int(plan.cut.sum()),
