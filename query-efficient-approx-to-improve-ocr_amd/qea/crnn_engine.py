@@ -10,7 +10,7 @@ their autograd, including the NaN scrub of CRNN.backward_hook (:30-32).
 """
 import torch
 
-from . import batchnorm, ops
+from . import batchnorm, conv, ops
 from .params import ensure_flat
 
 FUSE_POOL = True      # tests flip this: conv1 + ReLU + pool and BatchNorm2 apply + ReLU + pool as one pass each (same bits)
@@ -67,9 +67,10 @@ class CRNNEngine:
             ops.conv_c1_fwd(x, P[c + "conv1.weight"], P[c + "conv1.bias"], a1, 64, B, H, W, 64, relu=True)
             ops.maxpool_fwd(a1, 64, p1, 64, B, H, W, 64, 2, 2, amax=amx["p1"])
         acts = {"a1": a1, "p1": p1}                       # a1 None: not kept (the backward rebuilds it from x; tests: ctx["conv1_params"])
-        cur, ccur, cur_name = p1, 64, "p1"
-        dims = {"conv1": (H, W)}
+        cur, cur_name = p1, "p1"
+        convs = {}                                        # conv2 .. conv7: each layer's geometry, stated here and reused by the backward
         for name, cin, cout, relu, pool in CONVS:
+            cv = convs[name] = conv.Conv(B, h, w, cin, cout, 3, 3, pad=(1, 1))
             a = torch.empty(B * h * w, cout, device=dev)
             amx["a" + name[-1]] = slot()
             fused_pool = None
@@ -78,14 +79,12 @@ class CRNNEngine:
                 pt = torch.empty(B * ph * pw, cout, device=dev)
                 amx["p" + name[-1]] = slot()
                 # the pool behind relu(conv) leaves with the conv's epilogue where the kernel has the instance (same bits)
-                if FUSE_POOL and pool[0] == 2 and h % 2 == 0 and ops.conv_can_pool(B=B, H=h, W=w, Cin=cin, N=cout, kw=pool[1], ldx=cin, ldy=cout):
+                if FUSE_POOL and pool[0] == 2 and h % 2 == 0 and cv.can_pool(pool[1], cin, cout):
                     fused_pool = (pt, cout, pool[1], amx["p" + name[-1]])
-            ops.conv_igemm(cur, P[c + name + ".weight"], a, B=B, H=h, W=w, Cin=cin, OH=h, OW=w, N=cout, KH=3, KW=3, pad=(1, 1),
-                           ldx=cin, ldy=cout, bias=P[c + name + ".bias"], relu=relu, w_src=("fwd", P[c + name + ".weight"]),
-                           x_amax=amx[cur_name], y_amax=amx["a" + name[-1]], pool=fused_pool)
+            cv.fwd(cur, cin, P[c + name + ".weight"], a, cout, bias=P[c + name + ".bias"], relu=relu, x_amax=amx[cur_name],
+                   y_amax=amx["a" + name[-1]], pool=fused_pool)
             acts["a" + name[-1]] = a
-            dims[name] = (h, w)
-            cur, ccur, cur_name = a, cout, "a" + name[-1]
+            cur, cur_name = a, "a" + name[-1]
             if pool:
                 if fused_pool is None:
                     ops.maxpool_fwd(a, cout, pt, cout, B, h, w, cout, pool[0], pool[1], amax=amx["p" + name[-1]])
@@ -96,8 +95,8 @@ class CRNNEngine:
         for name, bn, cin in (("conv5", "batchnorm1", 256), ("conv6", "batchnorm2", 512)):
             M = B * h * w
             y = torch.empty(M, 512, device=dev)
-            ops.conv_igemm(cur, P[c + name + ".weight"], y, B=B, H=h, W=w, Cin=cin, OH=h, OW=w, N=512, KH=3, KW=3, pad=(1, 1),
-                           ldx=cin, ldy=512, bias=P[c + name + ".bias"], w_src=("fwd", P[c + name + ".weight"]), x_amax=amx[cur_name])
+            convs[name] = conv.Conv(B, h, w, cin, 512, 3, 3, pad=(1, 1))
+            convs[name].fwd(cur, cin, P[c + name + ".weight"], y, 512, bias=P[c + name + ".bias"], x_amax=amx[cur_name])
             amx["a" + name[-1]] = slot()
             a = torch.empty(M, 512, device=dev)
             pool = None
@@ -110,7 +109,6 @@ class CRNNEngine:
                                                          Bf[c + bn + ".running_mean"], Bf[c + bn + ".running_var"], bn_training, parts,
                                                          need_grad, amax=amx["a" + name[-1]], pool=pool)
             acts["a" + name[-1]], acts["y" + name[-1]] = a, y     # (y: the conv output under the name the trace tools tap)
-            dims[name] = (h, w)
             cur, cur_name = a, "a" + name[-1]
         if bn_training:
             fs.ibuf.add_(len(parts))                                # num_batches_tracked: one per group, as sequential calls
@@ -120,19 +118,18 @@ class CRNNEngine:
             amx["p6"] = slot()
             ops.maxpool_fwd(cur, 512, p6, 512, B, h, w, 512, 2, 1, amax=amx["p6"])
         acts["p6"] = p6
-        h6, w6 = h // 2, w
-        T = w6 - 1
-        if h6 != 2:
+        if h // 2 != 2:
             raise ValueError("CRNN backbone must reduce the height to 2 before conv7")
         # conv7 2x2 pad 0 -> [B,1,T,512], written as [T][B][512]
+        c7 = convs["conv7"] = conv.Conv(B, h // 2, w, 512, 512, 2, 2)
+        T = c7.OW
         seq = torch.empty(T, B, 512, device=dev)
-        ops.conv_igemm(p6, P[c + "conv7.weight"], seq, B=B, H=h6, W=w6, Cin=512, OH=1, OW=T, N=512, KH=2, KW=2, ldx=512, ldy=512,
-                       bias=P[c + "conv7.bias"], out_mode=ops.OUT_TBC, w_src=("fwd", P[c + "conv7.weight"]), x_amax=amx["p6"], y_amax=amx["seq"])
-        dims["conv7"] = (h6, w6)
+        c7.fwd(p6, 512, P[c + "conv7.weight"], seq, 512, bias=P[c + "conv7.bias"], out_mode=ops.OUT_TBC, x_amax=amx["p6"], y_amax=amx["seq"])
 
         # BiLSTM x2
         xin = seq
         lstm = []
+        proj = conv.gemm(T * B, 512, 4 * HID)             # one direction's input projection: all steps of the layer in one GEMM
         for layer in (0, 1):
             # the layer input's abs-max for its two projection GEMMs: conv7 carried it for layer 0; the BiLSTM output of layer 0
             # gets one pass of its own (shared by both directions)
@@ -144,9 +141,7 @@ class CRNNEngine:
             for d, suf in enumerate(("", "_reverse")):
                 b_ih, b_hh = P[f"lstm.bias_ih_l{layer}{suf}"], P[f"lstm.bias_hh_l{layer}{suf}"]
                 bias = ops.weight_cached("lstm_bias_sum", b_ih, lambda b_ih=b_ih, b_hh=b_hh: (b_ih + b_hh).detach(), also=(b_hh,))
-                ops.conv_igemm(xin, P[f"lstm.weight_ih_l{layer}{suf}"], gates[:, :, d * 4 * HID:], B=1, H=1, W=T * B, Cin=512, OH=1,
-                               OW=T * B, N=4 * HID, KH=1, KW=1, ldx=512, ldy=2 * 4 * HID, bias=bias,
-                               w_src=("fwd", P[f"lstm.weight_ih_l{layer}{suf}"]), x_amax=xin_amax)
+                proj.fwd(xin, 512, P[f"lstm.weight_ih_l{layer}{suf}"], gates[:, :, d * 4 * HID:], 2 * 4 * HID, bias=bias, x_amax=xin_amax)
             cst = torch.empty(T, B, 2 * HID, device=dev)
             y = torch.empty(T, B, 2 * HID, device=dev)
             # the layer output's abs-max: the next layer's projections / the Linear GEMM and, in the backward, the weight gradients
@@ -159,13 +154,14 @@ class CRNNEngine:
         # Linear + log_softmax (vocab padded to a multiple of 32 columns; pad columns stay 0)
         vp = self.vpad
         logits = torch.zeros(T * B, vp, device=dev)
-        ops.conv_igemm(xin, P["linear.weight"], logits, B=1, H=1, W=T * B, Cin=512, OH=1, OW=T * B, N=self.vocab, KH=1, KW=1, ldx=512,
-                       ldy=vp, bias=P["linear.bias"], w_src=("fwd", P["linear.weight"]), x_amax=lstm[1]["y_amax"])
+        conv.gemm(T * B, 512, self.vocab).fwd(xin, 512, P["linear.weight"], logits, vp, bias=P["linear.bias"], x_amax=lstm[1]["y_amax"])
         lp = torch.zeros(T * B, vp, device=dev)
         ops.log_softmax_fwd(logits, vp, lp, vp, T * B, self.vocab)
         out = lp.view(T, B, vp)[:, :, :self.vocab]
         if need_grad:
-            ctx.update(acts=acts, dims=dims, lstm=lstm, lp=lp, T=T, h6=h6, w6=w6, amx=amx, conv1_params=(P[c + "conv1.weight"], P[c + "conv1.bias"]))
+            # (dims: each layer's input plane under the key tests/decisions.py reads; the backward reads the records)
+            dims = {"conv1": (H, W), **{name: (cv.H, cv.W) for name, cv in convs.items()}}
+            ctx.update(acts=acts, convs=convs, dims=dims, lstm=lstm, lp=lp, T=T, amx=amx, conv1_params=(P[c + "conv1.weight"], P[c + "conv1.bias"]))
         return out, ctx
 
     # ------------------------------------------------------------------ backward
@@ -183,7 +179,7 @@ class CRNNEngine:
             full = (ctx["B"], ctx["x"])
             ctx, dlp = self._group_slice(ctx, dlp)
         B, H, W, T = ctx["B"], ctx["H"], ctx["W"], ctx["T"]
-        acts, dims = ctx["acts"], ctx["dims"]
+        acts, convs = ctx["acts"], ctx["convs"]
         vp, V = self.vpad, self.vocab
         c = self.cp
         TB = T * B
@@ -201,8 +197,7 @@ class CRNNEngine:
         if param_grads:
             def linear_grads():
                 dwl = torch.empty(vp, 512, device=dev)
-                ops.conv_wgrad(dlogits, y1, dwl, B=1, PH=1, PW=TB, QH=1, QW=TB, R=vp, Cc=512, KH=1, KW=1, ldp=vp, ldq=512,
-                               p_amax=dl_amax, q_amax=ctx["lstm"][1].get("y_amax"))
+                conv.gemm(TB, 512, vp).wgrad(dlogits, vp, y1, 512, dwl, p_amax=dl_amax, q_amax=ctx["lstm"][1].get("y_amax"))
                 G["linear.weight"].add_(dwl[:V])
                 dbl = torch.empty(vp, device=dev)
                 ops.colsum(dlogits, vp, TB, vp, dbl)
@@ -218,11 +213,11 @@ class CRNNEngine:
             return out
         wlT = ops.weight_cached(("padT", vp), wlin, padded_T)
         dy = torch.empty(T, B, 512, device=dev)
-        ops.conv_igemm(dlogits, wlT, dy, B=1, H=1, W=TB, Cin=vp, OH=1, OW=TB, N=512, KH=1, KW=1, ldx=vp, ldy=512, w_src=(("padT", vp), wlin),
-                       x_amax=dl_amax)
+        conv.gemm(TB, vp, 512).fwd(dlogits, vp, wlT, dy, 512, w_src=(("padT", vp), wlin), x_amax=dl_amax)
 
         # BiLSTM layers, top first
         dseq_bt = None
+        proj = conv.gemm(TB, 512, 4 * HID)                 # one direction's input projection (its weight gradient)
         for layer in (1, 0):
             s = ctx["lstm"][layer]
             gates, cst, yl, xin = s["gates"], s["c"], s["y"], s["x"]
@@ -236,8 +231,7 @@ class CRNNEngine:
                 def lstm_grads(layer=layer, gates=gates, xin=xin, yl=yl, g_amax=g_amax, x_amax=s.get("x_amax"), y_amax=s.get("y_amax")):
                     for d, suf in enumerate(("", "_reverse")):
                         dg = gates[:, :, d * 4 * HID:]
-                        ops.conv_wgrad(dg, xin, G[f"lstm.weight_ih_l{layer}{suf}"], B=1, PH=1, PW=TB, QH=1, QW=TB, R=4 * HID, Cc=512,
-                                       KH=1, KW=1, ldp=8 * HID, ldq=512, accumulate=True, p_amax=g_amax, q_amax=x_amax)
+                        proj.wgrad(dg, 8 * HID, xin, 512, G[f"lstm.weight_ih_l{layer}{suf}"], accumulate=True, p_amax=g_amax, q_amax=x_amax)
                         db = torch.empty(4 * HID, device=dev)                  # b_ih and b_hh enter the gates as a sum: one column
                         ops.colsum(dg, 8 * HID, TB, 4 * HID, db)               # sum (a full pass over the gate gradients) serves both
                         G[f"lstm.bias_ih_l{layer}{suf}"].add_(db)
@@ -248,8 +242,8 @@ class CRNNEngine:
                                 pg, qh = gates[1:, :, :4 * HID], yl[:T - 1, :, :HID]
                             else:
                                 pg, qh = gates[:T - 1, :, 4 * HID:], yl[1:, :, HID:]
-                            ops.conv_wgrad(pg, qh, G[f"lstm.weight_hh_l{layer}{suf}"], B=1, PH=1, PW=n, QH=1, QW=n, R=4 * HID, Cc=HID,
-                                           KH=1, KW=1, ldp=8 * HID, ldq=2 * HID, accumulate=True, p_amax=g_amax, q_amax=y_amax)
+                            conv.gemm(n, HID, 4 * HID).wgrad(pg, 8 * HID, qh, 2 * HID, G[f"lstm.weight_hh_l{layer}{suf}"], accumulate=True,
+                                                             p_amax=g_amax, q_amax=y_amax)
                 side.run(lstm_grads)
             wf, wr = P[f"lstm.weight_ih_l{layer}"], P[f"lstm.weight_ih_l{layer}_reverse"]
 
@@ -261,38 +255,35 @@ class CRNNEngine:
             wT = ops.weight_cached("catT", wf, cat_T, also=(wr,))
             if layer == 1:
                 dxl = torch.empty(T, B, 512, device=dev)
-                ops.conv_igemm(gates, wT, dxl, B=1, H=1, W=TB, Cin=8 * HID, OH=1, OW=TB, N=512, KH=1, KW=1, ldx=8 * HID, ldy=512,
-                               x_amax=g_amax, w_src=("catT", wf, (wr,)))      # (planes of the concatenated filter: cached with BOTH directions' weights)
+                # (planes of the concatenated filter: cached with BOTH directions' weights)
+                conv.gemm(TB, 8 * HID, 512).fwd(gates, 8 * HID, wT, dxl, 512, w_src=("catT", wf, (wr,)), x_amax=g_amax)
                 dy = dxl
             else:
                 # rows (t,b) -> output row b*T + t : the gradient of conv7's output in its own [B,1,T,512] order
                 dseq_bt = torch.empty(B, T, 512, device=dev)
                 dseq_amax = slot()
-                ops.conv_igemm(gates, wT, dseq_bt, B=T, H=1, W=B, Cin=8 * HID, OH=1, OW=B, N=512, KH=1, KW=1, ldx=8 * HID, ldy=512,
-                               out_mode=ops.OUT_TBC, x_amax=g_amax, y_amax=dseq_amax, w_src=("catT", wf, (wr,)))
+                conv.Conv(T, 1, B, 8 * HID, 512, 1, 1).fwd(gates, 8 * HID, wT, dseq_bt, 512, w_src=("catT", wf, (wr,)), out_mode=ops.OUT_TBC,
+                                                           x_amax=g_amax, y_amax=dseq_amax)
 
         # conv7 (2x2, pad 0) backward
-        h6, w6 = ctx["h6"], ctx["w6"]
-        p6 = acts["p6"]
+        c7, p6 = convs["conv7"], acts["p6"]
         if param_grads:
             def conv7_grads():
                 ops.colsum(dseq_bt, 512, B * T, 512, G[c + "conv7.bias"], accumulate=True)
-                ops.conv_wgrad(dseq_bt, p6, G[c + "conv7.weight"], B=B, PH=1, PW=T, QH=h6, QW=w6, R=512, Cc=512, KH=2, KW=2, ldp=512,
-                               ldq=512, accumulate=True, p_amax=dseq_amax, q_amax=ctx.get("amx", {}).get("p6"))
+                c7.wgrad(dseq_bt, 512, p6, 512, G[c + "conv7.weight"], accumulate=True, p_amax=dseq_amax, q_amax=ctx.get("amx", {}).get("p6"))
             side.run(conv7_grads, dseq_bt)
-        w7t = ops.flip_transposed(P[c + "conv7.weight"], 512, 512, 2, 2)
-        dp6 = torch.empty(B * h6 * w6, 512, device=dev)
-        ops.conv_igemm(dseq_bt, w7t, dp6, B=B, H=1, W=T, Cin=512, OH=h6, OW=w6, N=512, KH=2, KW=2, pad=(1, 1), ldx=512, ldy=512,
-                       w_src=("flipT", P[c + "conv7.weight"]), x_amax=dseq_amax)
+        dp6 = torch.empty(B * c7.H * c7.W, 512, device=dev)
+        c7.dgrad(dseq_bt, 512, P[c + "conv7.weight"], dp6, 512, x_amax=dseq_amax)
         # pool (2,1) backward -> grad of a6 (ReLU handled by bn_bwd's mask)
-        h, w = dims["conv6"]
+        h, w = convs["conv6"].H, convs["conv6"].W            # (conv5 works on the same plane)
         da = None
         if not FUSE_POOL_BWD:
             da = torch.empty(B * h * w, 512, device=dev)
             ops.maxpool_bwd(acts["a6"], 512, dp6, 512, da, 512, B, h, w, 512, 2, 1, relu_mask=False)
         amx = ctx.get("amx", {})                                  # forward tensors' abs-max (a replica-group slice keeps its tensor's bound)
-        for name, bn, cin, src in (("conv6", "batchnorm2", 512, "a5"), ("conv5", "batchnorm1", 256, "p4")):
-            M = B * h * w
+        for name, bn, src in (("conv6", "batchnorm2", "a5"), ("conv5", "batchnorm1", "p4")):
+            cv = convs[name]
+            M, cin = B * h * w, cv.Cin
             dy_ = torch.empty(M, 512, device=dev)
             dy_amax = slot()
             # da None: conv6's output went through the (2,1) pool only, whose backward rides in the two passes of BatchNorm2's (qea_bn_bwd_pool)
@@ -300,21 +291,19 @@ class CRNNEngine:
                                G[c + bn + ".weight"] if param_grads else None, G[c + bn + ".bias"] if param_grads else None, amax=dy_amax,
                                pool=(dp6, 512, 1) if da is None else None)
             if param_grads:
-                def bn_conv_grads(dy_=dy_, name=name, src=src, cin=cin, M=M, dy_amax=dy_amax):
+                def bn_conv_grads(dy_=dy_, name=name, src=src, cv=cv, dy_amax=dy_amax):
                     # (the bias gradient = column sums of dy rides with the weight gradient's staging waves where the kernel has it)
-                    ops.conv_wgrad(dy_, acts[src], G[c + name + ".weight"], B=B, PH=h, PW=w, QH=h, QW=w, R=512, Cc=cin, KH=3, KW=3,
-                                   pad=(1, 1), ldp=512, ldq=cin, accumulate=True, p_amax=dy_amax, q_amax=amx.get(src),
-                                   dbias=G[c + name + ".bias"])
+                    cv.wgrad(dy_, 512, acts[src], cv.Cin, G[c + name + ".weight"], accumulate=True, p_amax=dy_amax, q_amax=amx.get(src),
+                             dbias=G[c + name + ".bias"])
                 side.run(bn_conv_grads, dy_)
-            wt = ops.flip_transposed(P[c + name + ".weight"], 512, cin, 3, 3)
             da = torch.empty(M, cin, device=dev)
-            ops.conv_igemm(dy_, wt, da, B=B, H=h, W=w, Cin=512, OH=h, OW=w, N=cin, KH=3, KW=3, pad=(1, 1), ldx=512, ldy=cin,
-                           w_src=("flipT", P[c + name + ".weight"]), x_amax=dy_amax)
+            cv.dgrad(dy_, 512, P[c + name + ".weight"], da, cin, x_amax=dy_amax)
         # da = grad of p4 [B,4,W/4,256]
         # conv4 (+ReLU, pool (2,1)), conv3 (+ReLU), conv2 (+ReLU, pool (2,2))
         dcur, dcur_amax = da, None
         for name, cin, cout, relu, pool in reversed(CONVS):
-            h, w = dims[name]
+            cv = convs[name]
+            h, w = cv.H, cv.W
             M = B * h * w
             a = acts["a" + name[-1]]
             if pool:
@@ -325,19 +314,16 @@ class CRNNEngine:
                 dyc, dyc_amax = dcur, dcur_amax             # already masked by the producer's epilogue (which also left its abs-max)
             src = {"conv4": "a3", "conv3": "p2", "conv2": "p1"}[name]
             if param_grads:
-                def conv_grads(dyc=dyc, name=name, src=src, cin=cin, cout=cout, M=M, h=h, w=w, dyc_amax=dyc_amax):
-                    ops.conv_wgrad(dyc, acts[src], G[c + name + ".weight"], B=B, PH=h, PW=w, QH=h, QW=w, R=cout, Cc=cin, KH=3, KW=3,
-                                   pad=(1, 1), ldp=cout, ldq=cin, accumulate=True, p_amax=dyc_amax, q_amax=amx.get(src),
-                                   dbias=G[c + name + ".bias"])
+                def conv_grads(dyc=dyc, name=name, src=src, cv=cv, dyc_amax=dyc_amax):
+                    cv.wgrad(dyc, cv.N, acts[src], cv.Cin, G[c + name + ".weight"], accumulate=True, p_amax=dyc_amax, q_amax=amx.get(src),
+                             dbias=G[c + name + ".bias"])
                 side.run(conv_grads, dyc)
-            wt = ops.flip_transposed(P[c + name + ".weight"], cout, cin, 3, 3)
             dnext = torch.empty(M, cin, device=dev)
             # conv4's input a3 is a bare ReLU output (no pool in between): fuse its mask here
             mask = acts["a3"] if name == "conv4" else None
             dnext_amax = slot() if name == "conv4" else None   # conv4's input gradient IS conv3's output gradient (no pool in between)
-            ops.conv_igemm(dyc, wt, dnext, B=B, H=h, W=w, Cin=cout, OH=h, OW=w, N=cin, KH=3, KW=3, pad=(1, 1), ldx=cout, ldy=cin,
-                           mask=mask, ldmask=cin if mask is not None else 0, w_src=("flipT", P[c + name + ".weight"]),
-                           x_amax=dyc_amax, y_amax=dnext_amax)
+            cv.dgrad(dyc, cout, P[c + name + ".weight"], dnext, cin, mask=mask, ldmask=cin if mask is not None else 0, x_amax=dyc_amax,
+                     y_amax=dnext_amax)
             dcur, dcur_amax = dnext, dnext_amax
         # dcur = grad of p1 [B,16,W/2,64]; conv1
         dx = None
@@ -386,6 +372,7 @@ class CRNNEngine:
                 rows = t.shape[0] // B                                   # pixels per sample at this layer
                 acts[name] = t[b0 * rows:(b0 + k) * rows]
         sub["acts"] = acts
+        sub["convs"] = {name: cv.with_batch(k) for name, cv in ctx["convs"].items()}
         sub["lstm"] = [{key: (v[:, b0:b0 + k].contiguous() if torch.is_tensor(v) and v.dim() == 3 and v.shape[:2] == (T, B) else v)
                         for key, v in s.items()} for s in ctx["lstm"]]
         lp = ctx["lp"]

@@ -253,6 +253,14 @@ def transposed(w, R, Cc):
     return weight_cached(("T", R, Cc), w, build)
 
 
+def _src_cached(kind, dims, w_src, build, batch=None):
+    """build() -> a form of conv_igemm's filter `w`: cached under (kind, w_src's kind, *dims) with the weight(s) w_src names until one of
+    them changes; built afresh for a filter nobody named the source of (w_src None)."""
+    if w_src is None:
+        return build()
+    return weight_cached((kind, w_src[0]) + dims, w_src[1], build, also=tuple(w_src[2]) if len(w_src) > 2 else (), batch=batch)
+
+
 def _frag_planes_f16(d, kind, x, w, w_src, x_amax):
     """conv_igemm on a tile that reads the filter from fp16 fragment planes (kind 1: 3x3 LDS-halo kernel, kind 2: 1x1 LDS tile):
     points `d` at the cached planes of `w` and at the input's abs-max; returns both tensors (the caller holds them over the launch).
@@ -268,15 +276,22 @@ def _frag_planes_f16(d, kind, x, w, w_src, x_amax):
         elif kind == 1 and w_src[0] == "flipT" and d.KH == 3 and d.KW == 3:
             srck, amax = "flipT", (9 * N, Cin, 9 * N)
     job = FormJob("pack", kind, (N, Cin, 0, 0), srck, (L.qea_pack_frag_planes_f16_bytes if kind == 1 else L.qea_pack_frag_planes_f16_1x1_bytes)(N, Cin), amax)
-    if w_src is None:
-        frag = job.build(None, w)
-    else:
-        frag = weight_cached(("fragf16" if kind == 1 else "frag1x1", w_src[0], N, Cin), w_src[1], lambda: job.build(w_src[1], w),
-                             also=tuple(w_src[2]) if len(w_src) > 2 else (), batch=job if srck else None)
+    frag = _src_cached("fragf16" if kind == 1 else "frag1x1", (N, Cin), w_src, lambda: job.build(w_src[1] if w_src is not None else None, w),
+                       batch=job if srck else None)
     # the input's abs-max: carried by the tensor's producer (x_amax), else one pass over the input here
     xmax = x_amax if x_amax is not None else absmax(x, d.ldx, d.B * d.H * d.W, Cin)
     d.w_frag_planes, d.x_absmax = frag.data_ptr(), xmax.data_ptr()
     return frag, xmax
+
+
+def _conv_desc(x, w, y, *, B, H, W, Cin, OH, OW, N, KH, KW, pad, stride, ldx, ldy, scale=None, bias=None, mask=None, ldmask=0, relu=False,
+               accumulate=False, out_mode=OUT_NHWC, tile=0):
+    """the qea_conv_desc of a launch, before the routing below fills in planes, abs-max slots and epilogue outputs"""
+    return _lib.ConvDesc(x=_ptr(x), w=_ptr(w), y=_ptr(y), scale=_ptr(scale), bias=_ptr(bias), mask=_ptr(mask),
+                         B=B, H=H, W=W, Cin=Cin, OH=OH, OW=OW, N=N, KH=KH, KW=KW, pad_h=pad[0], pad_w=pad[1],
+                         stride_h=stride[0], stride_w=stride[1], ldx=ldx, ldy=ldy, ldmask=ldmask,
+                         relu=int(relu), accumulate=int(accumulate), out_mode=out_mode, tile=tile, x_planes=None, w_planes=None, stats=None,
+                         w_frag_planes=None)
 
 
 def conv_igemm(x, w, y, *, B, H, W, Cin, OH, OW, N, KH, KW, pad=(0, 0), stride=(1, 1), ldx, ldy,
@@ -296,11 +311,8 @@ def conv_igemm(x, w, y, *, B, H, W, Cin, OH, OW, N, KH, KW, pad=(0, 0), stride=(
     whose input was y_ref: the epilogue also leaves the two reductions of that BatchNorm's backward; returns (partials, blocks) for
     bn_bwd(partials=...), or None when this launch has no such epilogue (the caller's bn_bwd then makes its own pass)."""
     L = _lib.lib()
-    d = _lib.ConvDesc(x=_ptr(x), w=_ptr(w), y=_ptr(y), scale=_ptr(scale), bias=_ptr(bias), mask=_ptr(mask),
-                      B=B, H=H, W=W, Cin=Cin, OH=OH, OW=OW, N=N, KH=KH, KW=KW, pad_h=pad[0], pad_w=pad[1],
-                      stride_h=stride[0], stride_w=stride[1], ldx=ldx, ldy=ldy, ldmask=ldmask,
-                      relu=int(relu), accumulate=int(accumulate), out_mode=out_mode, tile=tile, x_planes=None, w_planes=None, stats=None,
-                      w_frag_planes=None)
+    d = _conv_desc(x, w, y, B=B, H=H, W=W, Cin=Cin, OH=OH, OW=OW, N=N, KH=KH, KW=KW, pad=pad, stride=stride, ldx=ldx, ldy=ldy, scale=scale,
+                   bias=bias, mask=mask, ldmask=ldmask, relu=relu, accumulate=accumulate, out_mode=out_mode, tile=tile)
     frag = xmax = None
     wants = L.qea_conv_igemm_wants_frag_planes(C.byref(d)) if PRESPLIT["on"] else 0
     if wants == 2 and SPLIT_F16["on"] and x_planes is None and w_planes is None:
@@ -314,7 +326,7 @@ def conv_igemm(x, w, y, *, B, H, W, Cin, OH, OW, N, KH, KW, pad=(0, 0), stride=(
             out = torch.empty(L.qea_pack_frag_planes_bytes(N, Cin), dtype=torch.uint8, device=x.device)
             _lib.check(L.qea_pack_frag_planes(_ptr(w), N, Cin, out.data_ptr(), _stream()), "qea_pack_frag_planes")
             return out
-        frag = weight_cached(("frag", w_src[0], N, Cin), w_src[1], build, also=tuple(w_src[2]) if len(w_src) > 2 else ()) if w_src is not None else build()
+        frag = _src_cached("frag", (N, Cin), w_src, build)
         d.w_frag_planes = frag.data_ptr()
     elif PRESPLIT["on"] and Cin % 16 == 0 and L.qea_conv_igemm_uses_split_bf16(C.byref(d)):
         K = KH * KW * Cin
@@ -326,7 +338,7 @@ def conv_igemm(x, w, y, *, B, H, W, Cin, OH, OW, N, KH, KW, pad=(0, 0), stride=(
             f16 = SPLIT_F16["on"] and x_planes is None and w_planes is None and N * K * 4 < (1 << 31) - 256
             if w_planes is None:
                 build = (lambda: split_planes_f16(w, K, N, K, w_src)) if f16 else (lambda: split_planes(w, K, N, K))
-                w_planes = weight_cached(("planesf16" if f16 else "planes", w_src[0], N, K), w_src[1], build, also=tuple(w_src[2]) if len(w_src) > 2 else ()) if w_src is not None else build()
+                w_planes = _src_cached("planesf16" if f16 else "planes", (N, K), w_src, build)
             d.x_planes = x_planes.data_ptr() if x_planes is not None else None
             d.w_planes = w_planes.data_ptr()
             if f16:                                       # hybrid tile on the two-way fp16 split: the activations' abs-max
@@ -359,9 +371,7 @@ def conv_can_pool(*, B, H, W, Cin, N, kw, ldx, ldy, mask=None):
     the two-way fp16 split is on and the LDS-halo kernel has the instance."""
     if not (PRESPLIT["on"] and SPLIT_F16["on"] and mfma_mode() == "split_f16") or mask is not None:
         return False
-    d = _lib.ConvDesc(x=None, w=None, y=None, scale=None, bias=None, mask=None, B=B, H=H, W=W, Cin=Cin, OH=H, OW=W, N=N, KH=3, KW=3, pad_h=1, pad_w=1,
-                      stride_h=1, stride_w=1, ldx=ldx, ldy=ldy, ldmask=0, relu=0, accumulate=0, out_mode=OUT_NHWC, tile=0, x_planes=None,
-                      w_planes=None, stats=None, w_frag_planes=None)
+    d = _conv_desc(None, None, None, B=B, H=H, W=W, Cin=Cin, OH=H, OW=W, N=N, KH=3, KW=3, pad=(1, 1), stride=(1, 1), ldx=ldx, ldy=ldy)
     return bool(_lib.lib().qea_conv_igemm_can_pool(C.byref(d), kw))
 
 

@@ -14,7 +14,7 @@ the [B,1,H,W] input and the [B,1,H,W] sigmoid output stays NHWC in HBM:
 """
 import torch
 
-from . import batchnorm, ops
+from . import batchnorm, conv, ops
 from .params import ensure_flat
 
 FUSE_EVAL_BN = True   # tests flip this to compare the fused inference epilogue with the two-pass form
@@ -46,12 +46,13 @@ class UNetEngine:
         self.dec = {l: _Block(f"decoder{l}", f"dec{l}", 2 * c, c) for l, c in ((4, 8 * f), (3, 4 * f), (2, 2 * f), (1, f))}
 
     # ------------------------------------------------------------------ helpers
-    def _conv_bn_relu(self, P, Bf, blk, i, x, ldx, cin, B, H, W, out, ldo, training, keep, parts, x_amax=None, out_amax=None, pool=None):
-        """x [B,H,W,cin] (pixel stride ldx) -> conv -> BN -> ReLU -> out (pixel stride ldo).  training, parts, keep: see batchnorm.forward.
+    def _conv_bn_relu(self, P, Bf, blk, i, x, ldx, cv, out, ldo, training, keep, parts, x_amax=None, out_amax=None, pool=None):
+        """x [B,H,W,cin] (pixel stride ldx) -> the 3x3 layer cv -> BN -> ReLU -> out (pixel stride ldo).  training, parts, keep: see
+        batchnorm.forward.
         pool = (pooled [B*(H/2)*(W/2)][cout], its abs-max slot): the 2x2 max-pool of the block output (model_unet.py:52-59) leaves with
         the BatchNorm apply in ONE pass (FUSE_BN_POOL) where there is such a pass.
         -> (the batchnorm.Stage, or None where the BatchNorm rode in the conv; True when the pool left here, else the caller pools)."""
-        cout = blk.cout
+        B, H, W, cin, cout = cv.B, cv.H, cv.W, cv.Cin, cv.N
         w = P[blk.key(i, "w")]
         bn = (P[blk.key(i, "gamma")], P[blk.key(i, "beta")], Bf[blk.key(i, "rm")], Bf[blk.key(i, "rv")])
         if not training and not keep and cin != 1 and FUSE_EVAL_BN:
@@ -59,10 +60,9 @@ class UNetEngine:
             # same fused multiply-add bn_apply evaluates, so the result is bit-identical to the two-pass form
             scale, shift = batchnorm.eval_scale_shift(cout, *bn)
             fused_pool = None
-            if pool is not None and ops.conv_can_pool(B=B, H=H, W=W, Cin=cin, N=cout, kw=2, ldx=ldx, ldy=ldo):
+            if pool is not None and cv.can_pool(2, ldx, ldo):
                 fused_pool = (pool[0], cout, 2, pool[1])         # ... and so does the 2x2 max-pool behind the block
-            ops.conv_igemm(x, w, out, B=B, H=H, W=W, Cin=cin, OH=H, OW=W, N=cout, KH=3, KW=3, pad=(1, 1), ldx=ldx, ldy=ldo,
-                           scale=scale, bias=shift, relu=True, w_src=("fwd", w), x_amax=x_amax, y_amax=out_amax, pool=fused_pool)
+            cv.fwd(x, ldx, w, out, ldo, scale=scale, bias=shift, relu=True, x_amax=x_amax, y_amax=out_amax, pool=fused_pool)
             return None, fused_pool is not None
         y = torch.empty(B * H * W, cout, device=x.device)
         fused = None
@@ -71,8 +71,7 @@ class UNetEngine:
         else:
             # train-mode BatchNorm: the conv's epilogue also leaves per-block fp64 column sums of y (no second pass over y)
             # (per-group statistics take the separate pass: a statistics block of the generic tile may straddle two images)
-            fused = ops.conv_igemm(x, w, y, B=B, H=H, W=W, Cin=cin, OH=H, OW=W, N=cout, KH=3, KW=3, pad=(1, 1), ldx=ldx, ldy=cout,
-                                   w_src=("fwd", w), want_stats=training and len(parts) == 1, x_amax=x_amax)
+            fused = cv.fwd(x, ldx, w, y, cout, want_stats=training and len(parts) == 1, x_amax=x_amax)
         return batchnorm.forward(y, out, ldo, H, W, cout, *bn, training, parts, keep, amax=out_amax, partials=fused,
                                  pool=(pool[0], cout, 2, 2, pool[1]) if pool is not None else None)
 
@@ -95,11 +94,12 @@ class UNetEngine:
         def run_block(blk, xin, ldx, cin, h, w, out, ldo, xin_amax, out_amax, pool=None):
             a1 = torch.empty(B * h * w, blk.cout, device=dev)
             a1_amax = slot()
-            bn1, _ = self._conv_bn_relu(P, Bf, blk, 1, xin, ldx, cin, B, h, w, a1, blk.cout, training, need_grad, parts, xin_amax, a1_amax)
-            bn2, pooled_here = self._conv_bn_relu(P, Bf, blk, 2, a1, blk.cout, blk.cout, B, h, w, out, ldo, training, need_grad, parts, a1_amax,
-                                                  out_amax, pool)
+            c1, c2 = (conv.Conv(B, h, w, ci, blk.cout, 3, 3, pad=(1, 1)) for ci in (cin, blk.cout))      # the block's two 3x3 layers
+            bn1, _ = self._conv_bn_relu(P, Bf, blk, 1, xin, ldx, c1, a1, blk.cout, training, need_grad, parts, xin_amax, a1_amax)
+            bn2, pooled_here = self._conv_bn_relu(P, Bf, blk, 2, a1, blk.cout, c2, out, ldo, training, need_grad, parts, a1_amax, out_amax, pool)
             if need_grad:
-                ctx["blocks"][blk.mod] = {"xin": xin, "ldx": ldx, "cin": cin, "h": h, "w": w, "a1": a1, "out": out, "ldo": ldo,
+                # (h, w: the block's plane under the keys tests/decisions.py reads; the backward reads the records)
+                ctx["blocks"][blk.mod] = {"xin": xin, "ldx": ldx, "c1": c1, "c2": c2, "h": h, "w": w, "a1": a1, "out": out, "ldo": ldo,
                                           "bn1": bn1, "bn2": bn2, "xin_amax": xin_amax, "a1_amax": a1_amax,
                                           "y1": bn1.y, "y2": bn2.y}        # the conv outputs under the names the trace tools tap
             return pooled_here
@@ -127,11 +127,10 @@ class UNetEngine:
         ups = {}
         for l in (4, 3, 2, 1):
             cat, hh, ww, c = cats[l]
-            wup = P[f"upconv{l}.weight"]                       # [2c][2][2][c] physical (IOHW channels_last)
-            wT = ops.transposed(wup, dcin, 4 * c)
-            ops.conv_igemm(d, wT, cat, B=B, H=h, W=w, Cin=dcin, OH=h, OW=w, N=4 * c, KH=1, KW=1, ldx=dcin, ldy=2 * c,
-                           bias=P[f"upconv{l}.bias"], out_mode=ops.OUT_CONVT, w_src=("T", wup), x_amax=d_amax, y_amax=cat_amax[l])
-            ups[l] = (d, dcin, h, w, d_amax)
+            # upconv_l is the adjoint of the stride-2 2x2 layer (hh, ww, c) -> (h, w, dcin), whose filter its weight [2c][2][2][c] is as it lies
+            up = conv.Conv(B, hh, ww, c, dcin, 2, 2, stride=(2, 2))
+            up.scatter_adjoint(d, dcin, P[f"upconv{l}.weight"], cat, 2 * c, bias=P[f"upconv{l}.bias"], x_amax=d_amax, y_amax=cat_amax[l])
+            ups[l] = (d, up, d_amax)
             h, w = hh, ww
             dnew = torch.empty(B * h * w, c, device=dev)
             d_amax = slot()
@@ -168,36 +167,30 @@ class UNetEngine:
             pool = (dpool, ld, 2): the gradient of the block's 2x2-pooled output still has to be routed to the winners and added to da2 —
             done inside the two passes of BatchNorm2's backward (qea_bn_bwd_pool)."""
             s = ctx["blocks"][blk.mod]
-            h, w, cin, cout = s["h"], s["w"], s["cin"], blk.cout
+            c1, c2 = s["c1"], s["c2"]
+            h, w, cin, cout = c1.H, c1.W, c1.Cin, c1.N
             M = B * h * w
             dy2 = torch.empty(M, cout, device=dev)
             dy2_amax, dy1_amax = slot(), slot()
             batchnorm.backward(s["bn2"], da2, ldda, dy2, P[blk.key(2, "gamma")], G[blk.key(2, "gamma")], G[blk.key(2, "beta")], amax=dy2_amax,
                                pool=pool)
-            w2 = P[blk.key(2, "w")]
-            side.run(lambda: ops.conv_wgrad(dy2, s["a1"], G[blk.key(2, "w")], B=B, PH=h, PW=w, QH=h, QW=w, R=cout, Cc=cout, KH=3, KW=3,
-                                            pad=(1, 1), ldp=cout, ldq=cout, accumulate=True, p_amax=dy2_amax, q_amax=s.get("a1_amax")), dy2)
-            w2t = ops.flip_transposed(w2, cout, cout, 3, 3)
+            side.run(lambda: c2.wgrad(dy2, cout, s["a1"], cout, G[blk.key(2, "w")], accumulate=True, p_amax=dy2_amax, q_amax=s.get("a1_amax")), dy2)
             da1 = torch.empty(M, cout, device=dev)
             # the two reductions of BatchNorm1's backward come with da1 from the dgrad's epilogue (FUSE_BN_BWD_SUMS; train mode, one
             # statistics group, fp16 form) instead of a pass of their own over da1 and y1
             bst = s["bn1"].producer_sums() if FUSE_BN_BWD_SUMS else None
-            part = ops.conv_igemm(dy2, w2t, da1, B=B, H=h, W=w, Cin=cout, OH=h, OW=w, N=cout, KH=3, KW=3, pad=(1, 1), ldx=cout, ldy=cout,
-                                  w_src=("flipT", w2), x_amax=dy2_amax, bwd_stats=bst)
+            part = c2.dgrad(dy2, cout, P[blk.key(2, "w")], da1, cout, x_amax=dy2_amax, bwd_stats=bst)
             dy1 = torch.empty(M, cout, device=dev)       # (dy2 may still be read by its wgrad on the side stream)
             batchnorm.backward(s["bn1"], da1, cout, dy1, P[blk.key(1, "gamma")], G[blk.key(1, "gamma")], G[blk.key(1, "beta")], amax=dy1_amax,
                                partials=part if bst is not None else None)
             if cin == 1:
                 side.run(lambda: ops.conv_c1_wgrad(s["xin"], dy1, cout, G[blk.key(1, "w")], None, B, h, w, cout, accumulate=True), dy1)
                 return None
-            side.run(lambda: ops.conv_wgrad(dy1, s["xin"], G[blk.key(1, "w")], B=B, PH=h, PW=w, QH=h, QW=w, R=cout, Cc=cin, KH=3, KW=3,
-                                            pad=(1, 1), ldp=cout, ldq=s["ldx"], accumulate=True, p_amax=dy1_amax, q_amax=s.get("xin_amax")), dy1)
-            w1 = P[blk.key(1, "w")]
-            w1t = ops.flip_transposed(w1, cout, cin, 3, 3)
+            side.run(lambda: c1.wgrad(dy1, cout, s["xin"], s["ldx"], G[blk.key(1, "w")], accumulate=True, p_amax=dy1_amax,
+                                      q_amax=s.get("xin_amax")), dy1)
             dxin = torch.empty(M, cin, device=dev)
             last_amax[0] = slot()                               # a decoder block's input gradient feeds the transposed conv's dgrad GEMM
-            ops.conv_igemm(dy1, w1t, dxin, B=B, H=h, W=w, Cin=cout, OH=h, OW=w, N=cin, KH=3, KW=3, pad=(1, 1), ldx=cout, ldy=cin,
-                           w_src=("flipT", w1), x_amax=dy1_amax, y_amax=last_amax[0])
+            c1.dgrad(dy1, cout, P[blk.key(1, "w")], dxin, cin, x_amax=dy1_amax, y_amax=last_amax[0])
             return dxin
 
         # head
@@ -212,16 +205,15 @@ class UNetEngine:
             dcat = block_bwd(self.dec[l], dd, self.dec[l].cout)
             cat, hh, ww, c = ctx["cats"][l]
             dcats[l] = dcat
-            dprev, dcin, h, w, dprev_amax = ctx["ups"][l]  # input of upconv_l: [B*h*w][dcin]
-            def up_grads(dcat=dcat, dprev=dprev, l=l, c=c, hh=hh, ww=ww, h=h, w=w, dcin=dcin, pa=dprev_amax, qa=last_amax[0]):
+            dprev, up, dprev_amax = ctx["ups"][l]          # input of upconv_l: [B*h*w][dcin]; the layer upconv_l is the adjoint of
+            dcin = up.N
+            def up_grads(dcat=dcat, dprev=dprev, l=l, c=c, hh=hh, ww=ww, up=up, pa=dprev_amax, qa=last_amax[0]):
                 ops.colsum(dcat, 2 * c, B * hh * ww, c, G[f"upconv{l}.bias"], accumulate=True)
-                ops.conv_wgrad(dprev, dcat, G[f"upconv{l}.weight"], B=B, PH=h, PW=w, QH=hh, QW=ww, R=dcin, Cc=c, KH=2, KW=2,
-                               stride=(2, 2), ldp=dcin, ldq=2 * c, accumulate=True, p_amax=pa, q_amax=qa)
+                up.wgrad(dprev, up.N, dcat, 2 * c, G[f"upconv{l}.weight"], accumulate=True, p_amax=pa, q_amax=qa)
             side.run(up_grads, dcat)
-            dd = torch.empty(B * h * w, dcin, device=dev)
+            dd = torch.empty(B * up.OH * up.OW, dcin, device=dev)
             # (the GEMM reads the up half of dcat, whose abs-max the slot of the whole tensor bounds)
-            ops.conv_igemm(dcat, P[f"upconv{l}.weight"], dd, B=B, H=hh, W=ww, Cin=c, OH=h, OW=w, N=dcin, KH=2, KW=2, stride=(2, 2),
-                           ldx=2 * c, ldy=dcin, w_src=("fwd", P[f"upconv{l}.weight"]), x_amax=last_amax[0])
+            up.fwd(dcat, 2 * c, P[f"upconv{l}.weight"], dd, dcin, x_amax=last_amax[0])
         # bottleneck, then encoder 4..1: skip grad (dcat[:, c:]) + pool backward of the deeper level
         dpool = block_bwd(self.bott, dd, self.bott.cout)
         for l in (4, 3, 2, 1):
