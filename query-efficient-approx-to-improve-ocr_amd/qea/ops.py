@@ -430,17 +430,21 @@ def mfma_mode():
 
 
 class AmaxPool:
-    """Zero-filled 4-byte slots for producer-carried abs-max values: one allocation + one memset per forward / backward pass."""
+    """Zero-filled 4-byte slots for producer-carried abs-max values: one allocation + one memset per forward / backward pass.
+    A pool lives for one pass and keeps every buffer it has handed slots out of for that long: a weight gradient pending on the side
+    stream reads its slots without listing them in SideStream.run's `reads`, and every pass ends in join()."""
 
     def __init__(self, device, n=192, on=True):
         self.on = on
         self.buf = torch.zeros(n, device=device) if on else None
+        self.full = []                                            # the buffers whose slots ran out
         self.used = 0
 
     def __call__(self):
         if not self.on:
             return None
         if self.used == self.buf.numel():
+            self.full.append(self.buf)
             self.buf = torch.zeros(self.buf.numel(), device=self.buf.device)
             self.used = 0
         self.used += 1
