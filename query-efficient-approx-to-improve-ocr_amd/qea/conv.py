@@ -6,7 +6,8 @@ launches of a layer read it, so they cannot disagree:
   wgrad  = dw[n][kh][kw][c] = sum dy[b,oh,ow][n] * x[b, oh*s+kh-pad, ow*s+kw-pad][c]: p = dy on (OH, OW), q = x on (H, W);
   a transposed convolution (stride = kernel, pad 0) is the adjoint of a Conv and holds that Conv's filter as it lies: its forward is
   scatter_adjoint, its input gradient the Conv's fwd, its weight gradient the Conv's wgrad(dy = the adjoint's input, x = its output gradient).
-Operands are [pixels][channels] rows with a pixel stride (ld) given per call: a layer reads and writes channel slices of wider rows.
+Operands are records (qea/act.py: tensor, channels, pixel stride, abs-max slot); every method refuses, before any launch, one whose
+channels or rows are not the layer's, and unpacks the strides and slots at the ops boundary.
 Calls go through the attributes of `ops` (tools/engine_schedule.py records by replacing them)."""
 from . import ops
 
@@ -29,41 +30,56 @@ class Conv:
         """the same layer on B samples (the backward of one replica group)"""
         return Conv(B, self.H, self.W, self.Cin, self.N, self.KH, self.KW, self.pad, self.stride)
 
-    def fwd(self, x, ldx, w, y, ldy, w_src=None, **epilogue):
-        """x [B*H*W][Cin] -> y [B*OH*OW][N] (rows as out_mode says) with the filter w [N][KH][KW][Cin].  w_src: only where w is a form the
-        caller derived from model weights itself (ops.conv_igemm's w_src); a model weight is its own source.  epilogue: conv_igemm's."""
-        return ops.conv_igemm(x, w, y, B=self.B, H=self.H, W=self.W, Cin=self.Cin, OH=self.OH, OW=self.OW, N=self.N, KH=self.KH, KW=self.KW,
-                              pad=self.pad, stride=self.stride, ldx=ldx, ldy=ldy, w_src=("fwd", w) if w_src is None else w_src, **epilogue)
+    def _check(self, on_input, on_output, pooled=None, kw=1):
+        """refuse a record that is not [B*H*W][Cin] on the layer's input plane, [B*OH*OW][N] on its output plane ([../(2*kw)][N]: pooled)"""
+        for a, C, pixels in ((on_input, self.Cin, self.H * self.W), (on_output, self.N, self.OH * self.OW), (pooled, self.N, (self.OH // 2) * (self.OW // kw))):
+            if a is not None and (a.C != C or a.nrows != self.B * pixels):
+                raise ValueError(f"an operand of [{a.nrows}][{a.C}] where this layer has [{self.B * pixels}][{C}]")
 
-    def dgrad(self, dy, lddy, w, dx, lddx, **epilogue):
-        """dy [B*OH*OW][N] -> dx [B*H*W][Cin] with the layer's own filter w (its flip-transposed form is derived and cached here)."""
+    def fwd(self, x, w, y, w_src=None, pool=None, **epilogue):
+        """x [B*H*W][Cin] -> y [B*OH*OW][N] (rows as out_mode says) with the filter w [N][KH][KW][Cin].  w_src: only where w is a form the
+        caller derived from model weights itself (ops.conv_igemm's w_src); a model weight is its own source.  pool = (pooled Act, kw): the
+        2 x kw max-pool of y leaves with the epilogue (see can_pool).  epilogue: conv_igemm's."""
+        self._check(x, y, *(pool or ()))
+        return ops.conv_igemm(x.t, w, y.t, B=self.B, H=self.H, W=self.W, Cin=self.Cin, OH=self.OH, OW=self.OW, N=self.N, KH=self.KH, KW=self.KW,
+                              pad=self.pad, stride=self.stride, ldx=x.ld, ldy=y.ld, x_amax=x.amax, y_amax=y.amax,
+                              w_src=("fwd", w) if w_src is None else w_src,
+                              pool=(pool[0].t, pool[0].ld, pool[1], pool[0].amax) if pool is not None else None, **epilogue)
+
+    def dgrad(self, dy, w, dx, mask=None, **epilogue):
+        """dy [B*OH*OW][N] -> dx [B*H*W][Cin] with the layer's own filter w (its flip-transposed form is derived and cached here).
+        mask: the Act on the input plane whose sign masks dx (a ReLU behind it)."""
         if self.stride != (1, 1):
             raise ValueError(f"dgrad is the stride-1 form; this layer has stride {self.stride}")
+        self._check(dx, dy)
+        self._check(mask, None)                                # (the mask lies on dx's plane)
         wt = ops.flip_transposed(w, self.N, self.Cin, self.KH, self.KW)
-        return ops.conv_igemm(dy, wt, dx, B=self.B, H=self.OH, W=self.OW, Cin=self.N, OH=self.H, OW=self.W, N=self.Cin, KH=self.KH, KW=self.KW,
-                              pad=(self.KH - 1 - self.pad[0], self.KW - 1 - self.pad[1]), ldx=lddy, ldy=lddx, w_src=("flipT", w), **epilogue)
+        return ops.conv_igemm(dy.t, wt, dx.t, B=self.B, H=self.OH, W=self.OW, Cin=self.N, OH=self.H, OW=self.W, N=self.Cin, KH=self.KH, KW=self.KW,
+                              pad=(self.KH - 1 - self.pad[0], self.KW - 1 - self.pad[1]), ldx=dy.ld, ldy=dx.ld, x_amax=dy.amax, y_amax=dx.amax,
+                              w_src=("flipT", w), mask=mask.t if mask is not None else None, ldmask=mask.ld if mask is not None else 0, **epilogue)
 
-    def wgrad(self, dy, lddy, x, ldx, dw, **kw):
-        """dw [N][KH][KW][Cin] (+)= the layer's weight gradient from dy [B*OH*OW][N] and x [B*H*W][Cin].  kw: accumulate, p_amax (of dy),
-        q_amax (of x), dbias."""
-        ops.conv_wgrad(dy, x, dw, B=self.B, PH=self.OH, PW=self.OW, QH=self.H, QW=self.W, R=self.N, Cc=self.Cin, KH=self.KH, KW=self.KW,
-                       pad=self.pad, stride=self.stride, ldp=lddy, ldq=ldx, **kw)
+    def wgrad(self, dy, x, dw, **kw):
+        """dw [N][KH][KW][Cin] (+)= the layer's weight gradient from dy [B*OH*OW][N] and x [B*H*W][Cin].  kw: accumulate, dbias."""
+        self._check(x, dy)
+        ops.conv_wgrad(dy.t, x.t, dw, B=self.B, PH=self.OH, PW=self.OW, QH=self.H, QW=self.W, R=self.N, Cc=self.Cin, KH=self.KH, KW=self.KW,
+                       pad=self.pad, stride=self.stride, ldp=dy.ld, ldq=x.ld, p_amax=dy.amax, q_amax=x.amax, **kw)
 
-    def scatter_adjoint(self, x, ldx, w, y, ldy, **epilogue):
+    def scatter_adjoint(self, x, w, y, **epilogue):
         """The adjoint map x [B*OH*OW][N] -> y [B*H*W][Cin] with the filter w as it lies: every input pixel writes its own KH x KW output
         pixels, so it is one GEMM on w's transpose [N][KH*KW*Cin] whose epilogue scatters (OUT_CONVT, which knows the 2x2 window)."""
         if self.stride != (self.KH, self.KW) or self.pad != (0, 0) or (self.KH, self.KW) != (2, 2):
             raise ValueError(f"scatter_adjoint needs stride = kernel = (2, 2) and pad 0, got kernel {(self.KH, self.KW)}, stride {self.stride}, "
                              f"pad {self.pad}")
+        self._check(y, x)
         K = self.KH * self.KW * self.Cin
         wT = ops.transposed(w, self.N, K)
-        return ops.conv_igemm(x, wT, y, B=self.B, H=self.OH, W=self.OW, Cin=self.N, OH=self.OH, OW=self.OW, N=K, KH=1, KW=1,
-                              ldx=ldx, ldy=ldy, out_mode=ops.OUT_CONVT, w_src=("T", w), **epilogue)
+        return ops.conv_igemm(x.t, wT, y.t, B=self.B, H=self.OH, W=self.OW, Cin=self.N, OH=self.OH, OW=self.OW, N=K, KH=1, KW=1,
+                              ldx=x.ld, ldy=y.ld, x_amax=x.amax, y_amax=y.amax, out_mode=ops.OUT_CONVT, w_src=("T", w), **epilogue)
 
-    def can_pool(self, kw, ldx, ldy):
-        """can this layer's fwd carry the 2 x kw max-pool behind it in its epilogue (fwd's pool=)?"""
+    def can_pool(self, kw, x, y):
+        """can this layer's fwd(x, ., y) carry the 2 x kw max-pool behind it in its epilogue (fwd's pool=)?"""
         return (self.KH, self.KW, self.pad, self.stride) == (3, 3, (1, 1), (1, 1)) and \
-            ops.conv_can_pool(B=self.B, H=self.H, W=self.W, Cin=self.Cin, N=self.N, kw=kw, ldx=ldx, ldy=ldy)
+            ops.conv_can_pool(B=self.B, H=self.H, W=self.W, Cin=self.Cin, N=self.N, kw=kw, ldx=x.ld, ldy=y.ld)
 
 
 def gemm(M, K, N):

@@ -15,6 +15,7 @@ the [B,1,H,W] input and the [B,1,H,W] sigmoid output stays NHWC in HBM:
 import torch
 
 from . import batchnorm, conv, ops
+from .act import Act
 from .params import ensure_flat
 
 FUSE_EVAL_BN = True   # tests flip this to compare the fused inference epilogue with the two-pass form
@@ -46,11 +47,11 @@ class UNetEngine:
         self.dec = {l: _Block(f"decoder{l}", f"dec{l}", 2 * c, c) for l, c in ((4, 8 * f), (3, 4 * f), (2, 2 * f), (1, f))}
 
     # ------------------------------------------------------------------ helpers
-    def _conv_bn_relu(self, P, Bf, blk, i, x, ldx, cv, out, ldo, training, keep, parts, x_amax=None, out_amax=None, pool=None):
-        """x [B,H,W,cin] (pixel stride ldx) -> the 3x3 layer cv -> BN -> ReLU -> out (pixel stride ldo).  training, parts, keep: see
-        batchnorm.forward.
-        pool = (pooled [B*(H/2)*(W/2)][cout], its abs-max slot): the 2x2 max-pool of the block output (model_unet.py:52-59) leaves with
-        the BatchNorm apply in ONE pass (FUSE_BN_POOL) where there is such a pass.
+    def _conv_bn_relu(self, P, Bf, blk, i, x, cv, out, training, keep, parts, pool=None):
+        """x [B,H,W,cin] -> the 3x3 layer cv -> BN -> ReLU -> out (Acts; x of the one-channel first layer: the image itself).  training,
+        parts, keep: see batchnorm.forward.
+        pool = the Act [B*(H/2)*(W/2)][cout]: the 2x2 max-pool of the block output (model_unet.py:52-59) leaves with the BatchNorm apply
+        in ONE pass (FUSE_BN_POOL) where there is such a pass.
         -> (the batchnorm.Stage, or None where the BatchNorm rode in the conv; True when the pool left here, else the caller pools)."""
         B, H, W, cin, cout = cv.B, cv.H, cv.W, cv.Cin, cv.N
         w = P[blk.key(i, "w")]
@@ -59,21 +60,18 @@ class UNetEngine:
             # inference (Phase A's cleaner pass, validation): eval-mode BatchNorm + ReLU ride in the conv epilogue — the
             # same fused multiply-add bn_apply evaluates, so the result is bit-identical to the two-pass form
             scale, shift = batchnorm.eval_scale_shift(cout, *bn)
-            fused_pool = None
-            if pool is not None and cv.can_pool(2, ldx, ldo):
-                fused_pool = (pool[0], cout, 2, pool[1])         # ... and so does the 2x2 max-pool behind the block
-            cv.fwd(x, ldx, w, out, ldo, scale=scale, bias=shift, relu=True, x_amax=x_amax, y_amax=out_amax, pool=fused_pool)
-            return None, fused_pool is not None
-        y = torch.empty(B * H * W, cout, device=x.device)
+            fuse_pool = pool is not None and cv.can_pool(2, x, out)     # ... and so does the 2x2 max-pool behind the block
+            cv.fwd(x, w, out, scale=scale, bias=shift, relu=True, pool=(pool, 2) if fuse_pool else None)
+            return None, fuse_pool
+        y = Act.empty(B * H * W, cout, out.t.device)
         fused = None
         if cin == 1:
-            ops.conv_c1_fwd(x, w, None, y, cout, B, H, W, cout, relu=False)
+            ops.conv_c1_fwd(x, w, None, y.t, y.ld, B, H, W, cout, relu=False)
         else:
             # train-mode BatchNorm: the conv's epilogue also leaves per-block fp64 column sums of y (no second pass over y)
             # (per-group statistics take the separate pass: a statistics block of the generic tile may straddle two images)
-            fused = cv.fwd(x, ldx, w, y, cout, want_stats=training and len(parts) == 1, x_amax=x_amax)
-        return batchnorm.forward(y, out, ldo, H, W, cout, *bn, training, parts, keep, amax=out_amax, partials=fused,
-                                 pool=(pool[0], cout, 2, 2, pool[1]) if pool is not None else None)
+            fused = cv.fwd(x, w, y, want_stats=training and len(parts) == 1)
+        return batchnorm.forward(y, out, H, W, *bn, training, parts, keep, partials=fused, pool=(pool, 2, 2) if pool is not None else None)
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, training, need_grad, groups=1):
@@ -84,60 +82,48 @@ class UNetEngine:
         if H % 16 or W % 16:
             raise ValueError(f"UNet input {H}x{W} must be a multiple of 16 in both dimensions")
         dev = x.device
-        f = self.f
         parts = batchnorm.partition(int(groups) if training else 1, B)
         ctx = {"x": x, "B": B, "H": H, "W": W, "blocks": {}} if need_grad else None
 
-        # producer-carried abs-max slots of every tensor a split-fp16 conv / wgrad launch will consume (None: that split is off)
+        # every tensor a split-fp16 conv / wgrad launch will consume carries the abs-max slot its producer fills (None: that split is off)
         slot = ops.amax_pool(dev)
 
-        def run_block(blk, xin, ldx, cin, h, w, out, ldo, xin_amax, out_amax, pool=None):
-            a1 = torch.empty(B * h * w, blk.cout, device=dev)
-            a1_amax = slot()
+        def run_block(blk, xin, cin, h, w, out, pool=None):
+            a1 = Act.empty(B * h * w, blk.cout, dev, slot)
             c1, c2 = (conv.Conv(B, h, w, ci, blk.cout, 3, 3, pad=(1, 1)) for ci in (cin, blk.cout))      # the block's two 3x3 layers
-            bn1, _ = self._conv_bn_relu(P, Bf, blk, 1, xin, ldx, c1, a1, blk.cout, training, need_grad, parts, xin_amax, a1_amax)
-            bn2, pooled_here = self._conv_bn_relu(P, Bf, blk, 2, a1, blk.cout, c2, out, ldo, training, need_grad, parts, a1_amax, out_amax, pool)
+            bn1, _ = self._conv_bn_relu(P, Bf, blk, 1, xin, c1, a1, training, need_grad, parts)
+            bn2, pooled_here = self._conv_bn_relu(P, Bf, blk, 2, a1, c2, out, training, need_grad, parts, pool)
             if need_grad:
                 # (h, w: the block's plane under the keys tests/decisions.py reads; the backward reads the records)
-                ctx["blocks"][blk.mod] = {"xin": xin, "ldx": ldx, "c1": c1, "c2": c2, "h": h, "w": w, "a1": a1, "out": out, "ldo": ldo,
-                                          "bn1": bn1, "bn2": bn2, "xin_amax": xin_amax, "a1_amax": a1_amax,
+                ctx["blocks"][blk.mod] = {"xin": xin, "c1": c1, "c2": c2, "h": h, "w": w, "a1": a1, "out": out, "bn1": bn1, "bn2": bn2,
                                           "y1": bn1.y, "y2": bn2.y}        # the conv outputs under the names the trace tools tap
             return pooled_here
 
         # encoder: level l has c = f*2^(l-1) channels at (H,W)/2^(l-1); its output goes to cat_l[:, c:2c]
-        cats, cat_amax = {}, {}
-        xin, ldx, cin, xin_amax = x, 1, 1, None
-        h, w = H, W
+        cats = {}
+        xin, cin, h, w = x, 1, H, W                             # (the one-channel image is no record: conv_c1_* take it as it is)
         for l, blk in enumerate(self.enc, start=1):
             c = blk.cout
-            cat = torch.empty(B * h * w, 2 * c, device=dev)
+            cat = Act.empty(B * h * w, 2 * c, dev, slot)        # one slot for the skip half (BatchNorm apply) and the up half (transposed conv)
             cats[l] = (cat, h, w, c)
-            cat_amax[l] = slot()                               # shared by the skip half (BatchNorm apply) and the up half (transposed conv)
-            skip = cat[:, c:]
-            pooled = torch.empty(B * (h // 2) * (w // 2), c, device=dev)
-            xin_in, xin_amax = xin_amax, slot()
-            if not run_block(blk, xin, ldx, cin, h, w, skip, 2 * c, xin_in, cat_amax[l], pool=(pooled, xin_amax) if FUSE_BN_POOL else None):
-                ops.maxpool_fwd(skip, 2 * c, pooled, c, B, h, w, c, 2, 2, amax=xin_amax)
-            xin, ldx, cin = pooled, c, c
-            h, w = h // 2, w // 2
-        d = torch.empty(B * h * w, self.bott.cout, device=dev)
-        d_amax = slot()                                        # the transposed conv that consumes d is a split GEMM too
-        run_block(self.bott, xin, ldx, cin, h, w, d, self.bott.cout, xin_amax, d_amax)
-        dcin = self.bott.cout
+            skip = cat.cols(c, c)
+            pooled = Act.empty(B * (h // 2) * (w // 2), c, dev, slot)
+            if not run_block(blk, xin, cin, h, w, skip, pool=pooled if FUSE_BN_POOL else None):
+                ops.maxpool_fwd(skip.t, skip.ld, pooled.t, pooled.ld, B, h, w, c, 2, 2, amax=pooled.amax)
+            xin, cin, h, w = pooled, c, h // 2, w // 2
+        d = Act.empty(B * h * w, self.bott.cout, dev, slot)     # (the transposed conv that consumes d is a split GEMM too)
+        run_block(self.bott, xin, cin, h, w, d)
         ups = {}
         for l in (4, 3, 2, 1):
             cat, hh, ww, c = cats[l]
-            # upconv_l is the adjoint of the stride-2 2x2 layer (hh, ww, c) -> (h, w, dcin), whose filter its weight [2c][2][2][c] is as it lies
-            up = conv.Conv(B, hh, ww, c, dcin, 2, 2, stride=(2, 2))
-            up.scatter_adjoint(d, dcin, P[f"upconv{l}.weight"], cat, 2 * c, bias=P[f"upconv{l}.bias"], x_amax=d_amax, y_amax=cat_amax[l])
-            ups[l] = (d, up, d_amax)
-            h, w = hh, ww
-            dnew = torch.empty(B * h * w, c, device=dev)
-            d_amax = slot()
-            run_block(self.dec[l], cat, 2 * c, 2 * c, h, w, dnew, c, cat_amax[l], d_amax)
-            d, dcin = dnew, c
+            # upconv_l is the adjoint of the stride-2 2x2 layer (hh, ww, c) -> (h, w, d.C), whose filter its weight [2c][2][2][c] is as it lies
+            up = conv.Conv(B, hh, ww, c, d.C, 2, 2, stride=(2, 2))
+            up.scatter_adjoint(d, P[f"upconv{l}.weight"], Act(cat.t, c, cat.ld, cat.amax), bias=P[f"upconv{l}.bias"])
+            ups[l] = (d, up)
+            d = Act.empty(B * hh * ww, c, dev, slot)
+            run_block(self.dec[l], cat, 2 * c, hh, ww, d)
         out = torch.empty(B, 1, H, W, device=dev)
-        ops.head_fwd(d, f, P["conv.weight"], P["conv.bias"], out, B * H * W, f)
+        ops.head_fwd(d.t, d.ld, P["conv.weight"], P["conv.bias"], out, B * H * W, d.C)
         if training:
             fs.ibuf.add_(len(parts))                            # all num_batches_tracked counters at once
         if need_grad:
@@ -154,77 +140,67 @@ class UNetEngine:
         G = {n: p.grad for n, p in P.items()}
         B, H, W = ctx["B"], ctx["H"], ctx["W"]
         dev = dout.device
-        f = self.f
         dout = dout.contiguous()
         side = ops.SideStream.of(self, dev)
         slot = ops.amax_pool(dev)
 
-        last_amax = [None]                                        # abs-max slot of the tensor block_bwd returned last
-
-        def block_bwd(blk, da2, ldda, pool=None):
-            """da2: grad w.r.t. the block output (pixel stride ldda).  Returns grad w.r.t. the block input
-            as a fresh [M][cin] tensor, or None for the first encoder block.
-            pool = (dpool, ld, 2): the gradient of the block's 2x2-pooled output still has to be routed to the winners and added to da2 —
+        def block_bwd(blk, da2, pool=None):
+            """da2: grad w.r.t. the block output.  Returns grad w.r.t. the block input as a fresh [M][cin] Act (a decoder block's feeds
+            the transposed conv's dgrad GEMM: it carries its slot), or None for the first encoder block.
+            pool = (dpool, 2): the gradient of the block's 2x2-pooled output still has to be routed to the winners and added to da2 —
             done inside the two passes of BatchNorm2's backward (qea_bn_bwd_pool)."""
             s = ctx["blocks"][blk.mod]
             c1, c2 = s["c1"], s["c2"]
             h, w, cin, cout = c1.H, c1.W, c1.Cin, c1.N
             M = B * h * w
-            dy2 = torch.empty(M, cout, device=dev)
-            dy2_amax, dy1_amax = slot(), slot()
-            batchnorm.backward(s["bn2"], da2, ldda, dy2, P[blk.key(2, "gamma")], G[blk.key(2, "gamma")], G[blk.key(2, "beta")], amax=dy2_amax,
-                               pool=pool)
-            side.run(lambda: c2.wgrad(dy2, cout, s["a1"], cout, G[blk.key(2, "w")], accumulate=True, p_amax=dy2_amax, q_amax=s.get("a1_amax")), dy2)
-            da1 = torch.empty(M, cout, device=dev)
+            dy2 = Act.empty(M, cout, dev, slot)
+            dy1_amax = slot()
+            batchnorm.backward(s["bn2"], da2, dy2, P[blk.key(2, "gamma")], G[blk.key(2, "gamma")], G[blk.key(2, "beta")], pool=pool)
+            side.run(lambda: c2.wgrad(dy2, s["a1"], G[blk.key(2, "w")], accumulate=True), dy2.t)
+            da1 = Act.empty(M, cout, dev)
             # the two reductions of BatchNorm1's backward come with da1 from the dgrad's epilogue (FUSE_BN_BWD_SUMS; train mode, one
             # statistics group, fp16 form) instead of a pass of their own over da1 and y1
             bst = s["bn1"].producer_sums() if FUSE_BN_BWD_SUMS else None
-            part = c2.dgrad(dy2, cout, P[blk.key(2, "w")], da1, cout, x_amax=dy2_amax, bwd_stats=bst)
-            dy1 = torch.empty(M, cout, device=dev)       # (dy2 may still be read by its wgrad on the side stream)
-            batchnorm.backward(s["bn1"], da1, cout, dy1, P[blk.key(1, "gamma")], G[blk.key(1, "gamma")], G[blk.key(1, "beta")], amax=dy1_amax,
+            part = c2.dgrad(dy2, P[blk.key(2, "w")], da1, bwd_stats=bst)
+            dy1 = Act(torch.empty(M, cout, device=dev), amax=dy1_amax)       # (dy2 may still be read by its wgrad on the side stream)
+            batchnorm.backward(s["bn1"], da1, dy1, P[blk.key(1, "gamma")], G[blk.key(1, "gamma")], G[blk.key(1, "beta")],
                                partials=part if bst is not None else None)
             if cin == 1:
-                side.run(lambda: ops.conv_c1_wgrad(s["xin"], dy1, cout, G[blk.key(1, "w")], None, B, h, w, cout, accumulate=True), dy1)
+                side.run(lambda: ops.conv_c1_wgrad(s["xin"], dy1.t, dy1.ld, G[blk.key(1, "w")], None, B, h, w, cout, accumulate=True), dy1.t)
                 return None
-            side.run(lambda: c1.wgrad(dy1, cout, s["xin"], s["ldx"], G[blk.key(1, "w")], accumulate=True, p_amax=dy1_amax,
-                                      q_amax=s.get("xin_amax")), dy1)
-            dxin = torch.empty(M, cin, device=dev)
-            last_amax[0] = slot()                               # a decoder block's input gradient feeds the transposed conv's dgrad GEMM
-            c1.dgrad(dy1, cout, P[blk.key(1, "w")], dxin, cin, x_amax=dy1_amax, y_amax=last_amax[0])
+            side.run(lambda: c1.wgrad(dy1, s["xin"], G[blk.key(1, "w")], accumulate=True), dy1.t)
+            dxin = Act.empty(M, cin, dev, slot)
+            c1.dgrad(dy1, P[blk.key(1, "w")], dxin)
             return dxin
 
         # head
         d1 = ctx["d1"]
-        M0 = B * H * W
-        dd = torch.empty(M0, f, device=dev)
-        ops.head_bwd(d1, f, ctx["out"], dout, P["conv.weight"], dd, f, G["conv.weight"], G["conv.bias"], M0, f, accumulate=True)
+        dd = Act.empty(B * H * W, d1.C, dev)
+        ops.head_bwd(d1.t, d1.ld, ctx["out"], dout, P["conv.weight"], dd.t, dd.ld, G["conv.weight"], G["conv.bias"], B * H * W, d1.C, accumulate=True)
 
         # decoder levels 1..4: block backward gives d(cat_l); split into up-conv grad and skip grad
         dcats = {}
         for l in (1, 2, 3, 4):
-            dcat = block_bwd(self.dec[l], dd, self.dec[l].cout)
-            cat, hh, ww, c = ctx["cats"][l]
-            dcats[l] = dcat
-            dprev, up, dprev_amax = ctx["ups"][l]          # input of upconv_l: [B*h*w][dcin]; the layer upconv_l is the adjoint of
-            dcin = up.N
-            def up_grads(dcat=dcat, dprev=dprev, l=l, c=c, hh=hh, ww=ww, up=up, pa=dprev_amax, qa=last_amax[0]):
-                ops.colsum(dcat, 2 * c, B * hh * ww, c, G[f"upconv{l}.bias"], accumulate=True)
-                up.wgrad(dprev, up.N, dcat, 2 * c, G[f"upconv{l}.weight"], accumulate=True, p_amax=pa, q_amax=qa)
-            side.run(up_grads, dcat)
-            dd = torch.empty(B * up.OH * up.OW, dcin, device=dev)
-            # (the GEMM reads the up half of dcat, whose abs-max the slot of the whole tensor bounds)
-            up.fwd(dcat, 2 * c, P[f"upconv{l}.weight"], dd, dcin, x_amax=last_amax[0])
+            dcats[l] = block_bwd(self.dec[l], dd)
+            dprev, up = ctx["ups"][l]                       # input of upconv_l: [B*h*w][dcin]; the layer upconv_l is the adjoint of
+            dup = Act(dcats[l].t, up.Cin, dcats[l].ld, dcats[l].amax)                    # the up half of dcat (whose abs-max the slot of the whole tensor bounds)
+            def up_grads(dup=dup, dprev=dprev, l=l, up=up):
+                ops.colsum(dup.t, dup.ld, dup.nrows, dup.C, G[f"upconv{l}.bias"], accumulate=True)
+                up.wgrad(dprev, dup, G[f"upconv{l}.weight"], accumulate=True)
+            side.run(up_grads, dup.t)
+            dd = Act.empty(B * up.OH * up.OW, up.N, dev)
+            up.fwd(dup, P[f"upconv{l}.weight"], dd)
         # bottleneck, then encoder 4..1: skip grad (dcat[:, c:]) + pool backward of the deeper level
-        dpool = block_bwd(self.bott, dd, self.bott.cout)
+        dpool = block_bwd(self.bott, dd)
         for l in (4, 3, 2, 1):
             cat, hh, ww, c = ctx["cats"][l]
-            dskip = dcats[l][:, c:]
+            skip, dskip = cat.cols(c, c), dcats[l].cols(c, c)
             if FUSE_POOL_BWD and ctx["blocks"][self.enc[l - 1].mod]["bn2"].single:
                 # the pool backward rides in the two passes of BatchNorm2's backward: dskip is read, never rewritten
                 # (one statistics group only: the grouped backward keeps the pool's own pass)
-                dpool = block_bwd(self.enc[l - 1], dskip, 2 * c, pool=(dpool, c, 2))
+                dpool = block_bwd(self.enc[l - 1], dskip, pool=(dpool, 2))
             else:
-                ops.maxpool_bwd(cat[:, c:], 2 * c, dpool, c, dskip, 2 * c, B, hh, ww, c, 2, 2, relu_mask=False, accumulate=True)
-                dpool = block_bwd(self.enc[l - 1], dskip, 2 * c)
+                ops.maxpool_bwd(skip.t, skip.ld, dpool.t, dpool.ld, dskip.t, dskip.ld, B, hh, ww, c, 2, 2, relu_mask=False, accumulate=True)
+                dpool = block_bwd(self.enc[l - 1], dskip)
         side.join()
         return None
