@@ -882,6 +882,31 @@ int qea_word_strips(const void* store, int32_t store_is_f32, int64_t store_elems
                     const int32_t* w, int32_t n_pages, const int32_t* boxes, int32_t n, int32_t OW, const float* norm, float* out,
                     void* stream);
 
+/* CTC forced alignment (csrc/ctc_align.hip; qea/align.py, qea.ops.ctc_align, utils.char_spans; the statement, which the device, the host
+ * path and tests/align_spec.py reproduce bit for bit, scores included, is DESIGN.md "Forced alignment"): the best single alignment of a
+ * GIVEN label to a sample's log-probs, where the beam searches return labellings, which carry no positions.
+ *   scores element (t,n,c) at t*ld_t + n*ld_n + c, converted to fp64 exactly; NaN and +inf count as -inf.  targets: the labels end to
+ *   end, int32; target_offsets [N+1] int64, label n = targets[target_offsets[n] .. target_offsets[n+1]), L characters, S = 2L+1 extended
+ *   states: ext(s) = blank for even s and l[s>>1] for odd s; skip(s) for odd s >= 3 with l[s>>1] != l[(s>>1)-1].
+ *   v_0(0) = lp[0][blank], v_0(1) = lp[0][l_0], the rest -inf; for t >= 1 the candidates are, IN THIS ORDER, stay v_{t-1}(s), step
+ *   v_{t-1}(s-1) (s >= 1), skip v_{t-1}(s-2) (skip(s)); the largest wins, of equal ones the earliest; v_t(s) = winner + lp[t][ext(s)], one
+ *   fp64 add; the winner's kind 0 / 1 / 2 is the back-pointer.  The path ends in S-1 or S-2 (L >= 1), the larger v_{T-1}, S-1 on equality.
+ *   score [N] fp64: that value; -inf = infeasible (T too short for L plus its adjacent repeats; impossible classes on every path), and so
+ *   is a label longer than L_max or with an entry outside 0..C-1 or equal to blank: such an entry is never used as an address.
+ *   path [N][T] int32: the character index at step t, -1 for blank; -2 throughout an infeasible sample.
+ *   first / last [target_offsets[N]] int32, laid out as targets: the steps character k's state 2k+1 occupies (contiguous); -1 / -1 when
+ *   infeasible.  char_score, likewise, fp64: lp[t][l_k] added up over t = first .. last in ASCENDING t; -inf when infeasible.
+ *   L = 0 is feasible: the all-blank path.  Every sample uses all T steps.
+ * L_max bounds the label lengths as S_max does for qea_ctc_loss.  One workgroup per sample, one thread per extended state, the prev rows
+ * in LDS and a barrier per step, as the loss scans; the back-pointers, 2 bits each, stay in LDS (32 KB at T = 512, L_max = 127).  One
+ * launch, no workspace, no atomics, nothing synchronises; every output element is stored exactly once.
+ * Refused before any launch: T outside 1..512, C outside 2..256, blank outside 0..C-1, L_max outside 0..127, N < 0, negative ld_t / ld_n,
+ * and with N > 0 a NULL pointer.  N = 0 is accepted and launches nothing.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects it by symbol.) */
+int qea_ctc_align(const float* scores, int32_t ld_t, int32_t ld_n, const int32_t* targets, const int64_t* target_offsets, int32_t T,
+                  int32_t N, int32_t C, int32_t blank, int32_t L_max, double* score, int32_t* path, int32_t* first, int32_t* last,
+                  double* char_score, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,10 @@ through the eval-mode CRNN bucket by bucket; greedy, beam, n-gram-fused or lexic
 exclusion rules) and "label" holds what the CRNN reads; with a beam "score" (the log-score the search ranked by) is added.  A line
 "<stem>: N words read, M cut" is printed per page (cut: wider than the last bucket).  Without the flag nothing changes: the same JSON
 bytes.
+[new] --read_chars (with --read): every label is also aligned to the scores it was decoded from (CTC forced alignment, utils.char_spans:
+one more launch per CRNN pass) and each row gains "chars": [{"c", "x_min", "x_max", "conf"}], one entry per character of the label: its
+columns on the page (x_max exclusive; y_min / y_max are the row's own) and the mean of its log-probabilities over the steps it
+occupies.  An empty label has an empty list.  The folder still loads as a PatchDataset, which ignores the key.
 
     python clean_cli.py --deskew --method sauvola --boxes --read out/crnn/model_1_0.00 --in_dir scans --out_dir read
 
@@ -70,6 +74,9 @@ class CleanPages:
         self.read_lm_weight, self.read_lm_bonus = float(getattr(args, "read_lm_weight", 1.0)), float(getattr(args, "read_lm_bonus", 0.0))
         self.read_buckets = tuple(getattr(args, "read_buckets", None) or reading.default_buckets())
         self.read_lm = self.read_lexicon = self.read_model = None
+        self.read_chars = bool(getattr(args, "read_chars", False))
+        if self.read_chars and not self.read_path:
+            raise ValueError("--read_chars needs --read CRNN_CHECKPOINT")
         if self.read_path:
             self.boxes = True
             reading.check_params(self.read_buckets, beam=self.read_beam)
@@ -129,11 +136,13 @@ class CleanPages:
                 cleaned = binarize_pages(pages, self.method, window=self.window, k=self.k, out="u8", device=self.device,
                                          despeckle=self.despeckle)
             boxes = components.word_boxes(cleaned, gap_x=self.boxes_gap, min_area=self.boxes_min_area, device=self.device) if self.boxes else None
-            texts = scores = None
+            texts = scores = chars = None
             if self.read_model is not None:
                 texts, *scores, _ = reading.read_pages(self.read_model, cleaned, boxes, self.index_to_char, buckets=self.read_buckets,
                                                        beam=self.read_beam, lm=self.read_lm, lm_weight=self.read_lm_weight,
-                                                       lm_bonus=self.read_lm_bonus, lexicon=self.read_lexicon)
+                                                       lm_bonus=self.read_lm_bonus, lexicon=self.read_lexicon, chars=self.read_chars)
+                if self.read_chars:
+                    chars = scores.pop()
                 table = reading.box_table(boxes)
                 plan = reading.strip_plan(table, [p.shape[-2] for p in cleaned], [p.shape[-1] for p in cleaned], self.read_buckets)
                 for n, t, m in zip(names, texts, np.bincount(table[plan.cut, 0], minlength=len(names)).tolist()):
@@ -149,6 +158,8 @@ class CleanPages:
                             row["label"] = t
                         for row, s in zip(rows, scores[0][i] if scores else []):
                             row["score"] = s
+                        for row, cs in zip(rows, chars[i] if chars else []):   # y_min / y_max of a character are its row's own
+                            row["chars"] = [dict(c=c, x_min=a, x_max=b, conf=v) for c, a, b, v in cs]
                     with open(os.path.splitext(path)[0] + ".json", "w") as f:
                         json.dump(rows, f)
         print(f"{len(written)} pages cleaned into {self.out_dir}")

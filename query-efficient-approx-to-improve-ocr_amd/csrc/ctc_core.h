@@ -1,6 +1,7 @@
 // The CTC recursion shared by ctc.hip (one problem per sample) and ctc_history.hip (up to W problems per strip): the alpha / beta
 // scan of ONE problem, the two pieces of the gradient's inner loop, the fixed-order fp64 tree sum, and the two host-side lines
-// (S_max check, thread count) that both launchers need.  fp64 on purpose.  An infeasible label gives nll = +inf and
+// (S_max check, thread count) that both launchers need.  ctc_align.hip, the max-product member of the family, shares the states
+// (ctc_state), the thread count and the bound check.  fp64 on purpose.  An infeasible label gives nll = +inf and
 // NaN gradient rows; CRNN's NaN scrub depends on that convention.
 #pragma once
 #include "common.h"
@@ -27,6 +28,24 @@ static inline int ctc_check_s_max(const char* fn, int S_max) {
   return QEA_OK;
 }
 static inline int ctc_scan_threads(int S_max) { return ((S_max + 63) / 64) * 64; }
+// the same check for a caller that bounds the label length instead (ctc_align.hip): S_max = 2 L_max + 1
+constexpr int CTC_MAX_L = (CTC_MAX_S - 1) / 2;
+static inline int ctc_check_l_max(const char* fn, int L_max) {
+  QEA_REQUIRE(L_max >= 0 && L_max <= CTC_MAX_L, "%s: L_max=%d must be in [0,%d] (%d extended states)", fn, L_max, CTC_MAX_L, CTC_MAX_S);
+  return QEA_OK;
+}
+
+// state s of the extended label of tg[0..L), S = 2L + 1: its class l'_s (blank for even s and for s >= S) and whether the recursion may
+// skip into it: from s - 2 going forward, to s + 2 going backward (is_beta)
+__device__ __forceinline__ void ctc_state(const int* __restrict__ tg, int s, int S, int blank, bool is_beta, int& ch, bool& skip) {
+  ch = blank;
+  skip = false;
+  if (s < S && (s & 1)) {
+    ch = tg[s >> 1];
+    if (!is_beta) skip = (s >= 2) && (tg[(s >> 1) - 1] != ch);
+    else skip = (s + 2 < S) && (tg[(s >> 1) + 1] != ch);
+  }
+}
 
 // alpha (is_beta false) or beta recursion of one problem by one workgroup, one thread per extended-label state:
 //   alpha_t(s) = lse(alpha_{t-1}(s), alpha_{t-1}(s-1), [alpha_{t-1}(s-2)]) + lp[t, l'_s]
@@ -37,13 +56,9 @@ __device__ __forceinline__ double ctc_scan(const float* __restrict__ lpn, int ld
                                            int S_max, bool is_beta, double* __restrict__ out, double (*prev)[CTC_MAX_S + 2]) {
   const int s = threadIdx.x;
   const int S = 2 * L + 1;
-  int ch = blank;      // l'_s
-  bool skip = false;   // alpha: may come from s-2 ; beta: may go to s+2
-  if (s < S && (s & 1)) {
-    ch = tg[s >> 1];
-    if (!is_beta) skip = (s >= 2) && (tg[(s >> 1) - 1] != ch);
-    else skip = (s + 2 < S) && (tg[(s >> 1) + 1] != ch);
-  }
+  int ch;      // l'_s
+  bool skip;   // alpha: may come from s-2 ; beta: may go to s+2
+  ctc_state(tg, s, S, blank, is_beta, ch, skip);
   if (Tn <= 0 || S > S_max) return (double)INFINITY;
 
   // prev rows are padded by 2 on the side the recursion reaches into

@@ -218,6 +218,9 @@ FLAGS += [
                                  "together with --read_lm"), "n"),
     ("--read_buckets", dict(type=int, nargs="+", metavar="W", help="[new] --read: the strip widths, ascending multiples of 16 in 64..512 "
                                                                    "(default 128 256 384 512); a word wider than the last loses its sides"), "n"),
+    ("--read_chars", dict(action="store_true", help="[new] --read: align every label to the scores it was decoded from (CTC forced alignment) and "
+                                                    "add 'chars': [{c, x_min, x_max, conf}] to each row: the character's columns on the page "
+                                                    "(x_max exclusive) and the mean of its log-probabilities"), "n"),
 ]
 
 

@@ -955,6 +955,39 @@ def ctc_beam_decode_dfa(scores, K, automaton, blank=0):
     return _beam_search("qea_ctc_beam_decode_dfa", scores, K, blank, mode, torch.int32)
 
 
+def ctc_align(scores, targets, offsets, L_max, blank=0):
+    """CTC forced alignment (include/qea_hip.h: qea_ctc_align) of scores [T,N,C] (CUDA, float32, any T / N strides, unit class stride)
+    to the labels targets (int32, end to end) / offsets (int64 [N+1]), both contiguous on the scores' device; L_max >= every label length
+    -> (score float64 [N], path int32 [N,T], first int32 [sum L], last int32 [sum L], char_score float64 [sum L]) on the device, one
+    launch and no synchronisation (sum L is targets.numel(): nothing is read back).  Raises QeaError for what qea.align.check_limits
+    refuses and for tensors of another device, dtype or layout; N = 0 launches nothing."""
+    from . import align
+    who = "ctc_align"
+    if scores.dim() != 3 or not scores.is_cuda or scores.dtype != torch.float32:
+        raise _lib.QeaError(f"{who} needs a CUDA float32 tensor [T,N,C] (there is no CPU path here: qea.align has one)")
+    if scores.stride(2) != 1:
+        raise _lib.QeaError(f"{who} needs a unit class stride: make the last dimension contiguous")
+    if not (0 <= scores.stride(0) < 2 ** 31 and 0 <= scores.stride(1) < 2 ** 31):
+        raise _lib.QeaError(f"{who}: the T and N strides must fit 32 bits")
+    T, N, C_ = scores.shape
+    blank, L_max = int(blank), int(L_max)
+    align.check_limits(T, C_, blank, L_max, N)
+    for name, t, dtype, numel in (("targets", targets, torch.int32, None), ("offsets", offsets, torch.int64, N + 1)):
+        if not (torch.is_tensor(t) and t.device == scores.device and t.dtype == dtype and t.dim() == 1 and t.is_contiguous()
+                and numel in (None, t.numel())):
+            raise _lib.QeaError(f"{who}: {name} must be a contiguous 1-D {dtype} tensor on the scores' device"
+                                + (f" of {numel} elements" if numel else ""))
+    total, dev = targets.numel(), scores.device
+    score, path = torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, T, dtype=torch.int32, device=dev)
+    # at least one element behind every pointer: a batch of empty labels is a valid call
+    first, last = (torch.empty(max(total, 1), dtype=torch.int32, device=dev) for _ in range(2))
+    char_score = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+    tg = targets if total else torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().qea_ctc_align(_ptr(scores), scores.stride(0), scores.stride(1), _ptr(tg), _ptr(offsets), T, N, C_, blank, L_max,
+                                        _ptr(score), _ptr(path), _ptr(first), _ptr(last), _ptr(char_score), _stream()), "qea_ctc_align")
+    return score, path, first[:total], last[:total], char_score[:total]
+
+
 def prof_read_launches(klass, capacity=4096):
     import numpy as np
     ms = np.zeros(capacity)

@@ -177,16 +177,48 @@ def word_strips(pages, boxes, width, device=None):
     return _Cutter(pages, device).strips(_box_table(boxes), int(width))
 
 
+def char_boxes(first, last, x0, cw, ch, sw, OW):
+    """Pure integer host code: the character spans of ONE box (first / last: per character the CRNN steps it occupies, as utils.char_spans
+    returns them) and that box's geometry (x0: its clipped left edge on the page, cw x ch: its clipped size, sw: its strip width from
+    strip_plan, OW: the width of the pass it was read in) -> per character (x_min, x_max) in page coordinates, x_max EXCLUSIVE as in the
+    written JSON.
+    Step t of the CRNN is column t of conv7.  Along the width the layers are (the CRNN's layer list): conv1 3x3 pad 1, pool 2x2,
+    conv2 3x3 pad 1, pool 2x2, conv3..conv6 3x3 pad 1 with the pools (2, 1) behind conv4 and conv6, which halve the height only, and conv7
+    2x2 without padding.  So a pooled column p covers strip columns [4 p, 4 p + 4), conv7 column t reads pooled columns t and t + 1, T = OW / 4 - 1,
+    and step t is centred on strip columns [4 t, 4 t + 8).  Its cell is the central half [4 t + 2, 4 t + 6): the cells of neighbouring steps
+    touch and tile [2, OW - 2).  A character on steps first..last owns strip columns [4 first + 2, 4 last + 6).
+    The strip holds the box's sw columns from left = (OW - sw) // 2 on (Python floor division as _strips_host centres them; negative for
+    a cut strip), one strip column being m / 32 page columns with m = max(ch, 32):
+        a = clamp(4 first + 2 - left, 0, sw - 1)    b = clamp(4 last + 6 - left, a + 1, sw)
+        x_min = x0 + (a m) // 32                    x_max = x0 + min(cw, (b m + 31) // 32)
+    For ch <= 32 that is the shift by x0 - left.  A character the alignment put into the padding is clamped to the box's nearest column:
+    every box lies inside [x0, x0 + cw], is at least one column wide, and x_min does not decrease along the word."""
+    x0, cw, ch, sw, OW = (int(v) for v in (x0, cw, ch, sw, OW))
+    if cw < 1 or ch < 1 or sw < 1:
+        raise ValueError(f"char_boxes: an empty box (cw={cw}, ch={ch}, sw={sw}) has no characters")
+    left, m = (OW - sw) // 2, max(ch, OH)
+    out = []
+    for f, l in zip(first, last):
+        a = min(max(4 * int(f) + 2 - left, 0), sw - 1)
+        b = min(max(4 * int(l) + 6 - left, a + 1), sw)
+        out.append((x0 + (a * m) // 32, x0 + min(cw, (b * m + 31) // 32)))
+    return out
+
+
 def read_pages(model, pages, boxes_per_page, index_to_char, buckets=None, strip_pixels=STRIP_PIXELS, beam=0, nbest=1, lm=None,
-               lm_weight=1.0, lm_bonus=0.0, lexicon=None, forward=None):
+               lm_weight=1.0, lm_bonus=0.0, lexicon=None, forward=None, chars=False):
     """pages as for word_strips; boxes_per_page: per page an integer table [n_p, 4] = (x_min, y_min, x_max, y_max), INCLUSIVE, as
     components.word_boxes returns them -> (texts, cut) for beam = 0 and (texts, scores, cut) for beam > 0: per page the list of what the
     CRNN reads in that page's box order (strings, or lists of nbest strings), the scores as utils.pred_to_string(return_scores=True)
     gives them in the same nesting, and the number of boxes whose strip is wider than the last bucket and lost its sides.
     The work follows strip_plan: one word_strips call (one launch) per non-empty bucket, one CRNN forward per pass, on the model's device;
     decoding is utils.pred_to_string unchanged (beam, nbest, lm, lm_weight, lm_bonus, lexicon are its arguments).  forward: the callable
-    that maps a pass [b, 1, 32, OW] to its scores [T, b, C]; the default is the model itself."""
-    from utils import _check_beam_arguments, pred_to_string
+    that maps a pass [b, 1, 32, OW] to its scores [T, b, C]; the default is the model itself.
+    chars=True: the best string of every box is also aligned to the scores of the same pass (utils.char_spans: one more launch per pass)
+    and the result gains, in front of cut, per page and box a list of (char, x_min, x_max, mean_logp): the character's columns on the page
+    (char_boxes; x_max exclusive) and the mean of its log-probs over its steps.  An empty string, an empty box and an infeasible alignment
+    give an empty list.  index_to_char must then be one-to-one (ValueError otherwise)."""
+    from utils import _check_beam_arguments, char_spans, pred_to_string
     buckets = check_params(buckets, strip_pixels, beam, nbest)
     _check_beam_arguments("read_pages", beam, lm, lexicon)
     require_eval(model, "read_pages")
@@ -197,7 +229,12 @@ def read_pages(model, pages, boxes_per_page, index_to_char, buckets=None, strip_
     cutter = _Cutter(pages, param.device if param is not None else None)
     plan = strip_plan(table, cutter.pk.h, cutter.pk.w, buckets, strip_pixels)
     forward = model if forward is None else forward
-    texts, scores = [None] * len(table), [None] * len(table)
+    texts, scores, spans = [None] * len(table), [None] * len(table), [None] * len(table)
+    if chars:
+        char_to_index = {c: i for i, c in index_to_char.items()}
+        if len(char_to_index) != len(index_to_char):
+            raise ValueError("read_pages(chars=True): index_to_char maps several classes to one character")
+        x0, _, cw, ch, _ = _geometry(table, cutter.pk.h, cutter.pk.w)
     strips, width, done = None, None, 0
     with torch.no_grad():
         for OW, idx in plan.passes:
@@ -213,7 +250,15 @@ def read_pages(model, pages, boxes_per_page, index_to_char, buckets=None, strip_
                 got, sc = pred_to_string(s, labels, index_to_char), labels
             for i, t, v in zip(idx.tolist(), got, sc):
                 texts[i], scores[i] = t, v
+            if chars:
+                best = [t if isinstance(t, str) else t[0] for t in got]
+                for i, text, (score, lo, hi, cs) in zip(idx.tolist(), best, char_spans(s, best, char_to_index)):
+                    spans[i] = []
+                    if text and score > -np.inf and plan.sw[i] > 0:
+                        cols = char_boxes(lo, hi, x0[i], cw[i], ch[i], plan.sw[i], OW)
+                        spans[i] = [(c, a, b, float(v) / (int(h) - int(l) + 1)) for c, (a, b), v, l, h in zip(text, cols, cs, lo, hi)]
     first = np.searchsorted(table[:, 0], np.arange(len(pages) + 1)).tolist()      # the table is page after page
     per_page = lambda values: [values[a:b] for a, b in zip(first[:-1], first[1:])]
     cut = int(plan.cut.sum())
-    return (per_page(texts), per_page(scores), cut) if beam else (per_page(texts), cut)
+    out = (per_page(texts), per_page(scores)) if beam else (per_page(texts),)
+    return out + ((per_page(spans), cut) if chars else (cut,))

@@ -8,7 +8,8 @@ Python loop with an .item() per (b,t)), crop + pad gather with a scatter-add bac
 beam= / nbest= / return_scores= arguments of pred_to_string and batch_cers add a CTC prefix beam search (csrc/ctc_beam.hip for CUDA
 scores, qea/beam.py on the host), and beam_decode_lm / lm= / lm_weight= / lm_bonus= fuse a character n-gram prior (qea/lm.py) into
 that search; beam_decode_lexicon / lexicon= keep it inside a word list (qea/lexicon.py); the reference has no beam and the defaults
-are its greedy decode.  The optional
+are its greedy decode.  [new] char_spans aligns given strings to the scores (CTC forced alignment: csrc/ctc_align.hip, qea/align.py) and
+returns where each character sits and how confident the CRNN is of it.  The optional
 third-party pieces of the reference file (wandb, optuna, unidecode, Levenshtein, torchvision) are
 imported lazily and only where the corresponding feature is used."""
 import json
@@ -187,6 +188,46 @@ def pred_to_string(scores, labels, index_to_char, show_text=False, beam=0, nbest
         for l, p in zip(labels, preds):
             print(l, " -> ", p)
     return preds
+
+
+def char_spans(scores, texts, char_to_index, blank=0):
+    """[new] CTC forced alignment of scores [T,N,C] to N given readings: texts is N strings (mapped through char_to_index) or N lists of
+    class indices -> per sample (score, first, last, char_score): the log-score of the best single alignment as a Python float, and per
+    character the first and last step it occupies (int32 numpy) and the sum of its log-probs over those steps (float64 numpy; divided by
+    last - first + 1 it is the character's mean log-prob).  An infeasible sample (more characters, counting a blank between repeats, than
+    steps; a class outside the scores; the blank inside the label) gives (-inf, all -1, all -1, all -inf).  CUDA scores: one launch
+    (qea.ops.ctc_align); CPU scores, or QEA_ALIGN=host: the same statement as a host loop (qea/align.py), bit for bit.  ValueError, naming
+    the sample, for a character outside the vocabulary and for a label of more than 127 characters."""
+    from qea import align
+    s = scores.detach()
+    if s.dim() != 3 or len(texts) != s.shape[1]:
+        raise ValueError(f"char_spans: {len(texts)} texts for scores of shape {tuple(s.shape)} ([T, N, C] with N texts wanted)")
+    labels = []
+    for n, text in enumerate(texts):
+        if isinstance(text, str):
+            missing = sorted({c for c in text if c not in char_to_index})
+            if missing:
+                raise ValueError(f"char_spans: sample {n}: {missing} not in the vocabulary")
+            text = [char_to_index[c] for c in text]
+        if len(text) > align.MAX_L:
+            raise ValueError(f"char_spans: sample {n}: a label of {len(text)} characters, more than {align.MAX_L}")
+        labels.append([int(c) for c in text])
+    lengths = [len(l) for l in labels]
+    offsets = np.concatenate(([0], np.cumsum(lengths, dtype=np.int64))).astype(np.int64)
+    flat = np.asarray([c for l in labels for c in l], dtype=np.int64)
+    flat = np.where((flat < -1) | (flat >= 2 ** 31), -1, flat).astype(np.int32)      # any class that is none stays one in 32 bits
+    L_max = max(lengths, default=0)
+    if s.is_cuda and not align.use_host():
+        from qea import ops
+        if s.dtype != torch.float32:
+            s = s.float()
+        if s.stride(2) != 1:
+            s = s.contiguous()
+        out = ops.ctc_align(s, torch.from_numpy(flat).to(s.device), torch.from_numpy(offsets).to(s.device), L_max, blank)
+    else:
+        out = align.ctc_align(s, flat, offsets, L_max, blank)
+    score, _, first, last, char_score = (v.cpu().numpy() for v in out)
+    return [(float(score[n]), first[a:b], last[a:b], char_score[a:b]) for n, (a, b) in enumerate(zip(offsets[:-1].tolist(), offsets[1:].tolist()))]
 
 
 def levenshtein(a, b):
