@@ -584,7 +584,8 @@ extern "C" int qea_bn_train_stats(const float* y, int32_t ldy, int64_t M, int32_
   QEA_REQUIRE(y && mean_out && invstd_out && scale_out && shift_out, "qea_bn_train_stats: null pointer");
   QEA_REQUIRE(((uintptr_t)y & 15) == 0, "qea_bn_train_stats: alignment");
   ColGeom g;
-  if (int rc = check_cols("qea_bn_train_stats", M, C, ldy, workspace, workspace_bytes, 0, &g)) return rc;
+  // (3 constants although only the partial rows are written: ONE workspace size for stats / bwd / colsum, qea_colreduce_workspace_bytes)
+  if (int rc = check_cols("qea_bn_train_stats", M, C, ldy, workspace, workspace_bytes, 3, &g)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)g.rt * C * 2 * sizeof(double);
   hipLaunchKernelGGL(colreduce_kernel<0>, dim3(g.grid), dim3(RED_THREADS), lds, s, y, ldy, nullptr, 0, nullptr, 0, nullptr, nullptr,
@@ -794,7 +795,7 @@ extern "C" int qea_colsum(const float* x, int32_t ldx, int64_t M, int32_t C, flo
                           size_t workspace_bytes, void* stream) {
   QEA_REQUIRE(x && out, "qea_colsum: null pointer");
   ColGeom g;
-  if (int rc = check_cols("qea_colsum", M, C, ldx, workspace, workspace_bytes, 0, &g)) return rc;
+  if (int rc = check_cols("qea_colsum", M, C, ldx, workspace, workspace_bytes, 3, &g)) return rc;   // (as qea_bn_train_stats)
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)g.rt * C * 2 * sizeof(double);
   hipLaunchKernelGGL(colreduce_kernel<2>, dim3(g.grid), dim3(RED_THREADS), lds, s, x, ldx, nullptr, 0, nullptr, 0, nullptr, nullptr,
