@@ -907,6 +907,37 @@ int qea_ctc_align(const float* scores, int32_t ld_t, int32_t ld_n, const int32_t
                   int32_t N, int32_t C, int32_t blank, int32_t L_max, double* score, int32_t* path, int32_t* first, int32_t* last,
                   double* char_score, void* stream);
 
+/* Word boxes grouped into text lines and put into reading order (csrc/lines.hip; qea/lines.py: group_lines, page_text; clean_cli.py
+ * --lines --text; the statement, which the device, the host path and tests/lines_spec.py reproduce bit for bit, is DESIGN.md "Text lines").
+ * qea_line_group — ONE launch, one workgroup per page, whatever the pages hold.  boxes is int32 [n_boxes][4] = (x_min, y_min, x_max, y_max),
+ *   inclusive, any int32 values, on the device, page after page as qea_cc_boxes writes them; box_first is int32 [n_pages + 1] on the
+ *   device, page p's boxes being rows box_first[p] .. box_first[p + 1] - 1.  overlap (1..100, per cent), tall (1..QEA_LINE_MAX_TALL) and gap
+ *   (0..QEA_LINE_MAX_GAP, 0 = no limit) are the statement's parameters.  All arithmetic is 64-bit.  Per page, with i counting within it:
+ *   a box with h_i = y_max - y_min + 1 <= 0 or w_i <= 0 is empty and a line of its own; med = the element of rank (m - 1) div 2 among the
+ *   ascending heights of the m non-empty boxes (0 if m = 0); a non-empty box is linkable iff h_i <= tall med; two linkable boxes are in
+ *   one height band iff 100 ov >= overlap min(h_i, h_j), ov = min(y_max_i, y_max_j) - max(y_min_i, y_min_j) + 1; under the key
+ *   (x_min_i, i), succ(i) / pred(i) is the box of i's band with the smallest key above / the largest key below i's; the link i - succ(i)
+ *   exists iff gap = 0 or x_min_succ - x_max_i - 1 <= gap med, the link i - pred(i) iff gap = 0 or x_min_i - x_max_pred - 1 <= gap med; a
+ *   line is a connected component of the links, its box the union of its members'; lines are numbered ascending by
+ *   (y_min + y_max, x_min, smallest member) of their boxes; a box's position is its rank under (line, x_min, y_min, i).
+ *   line / pos / order [n_boxes] int32, laid out as boxes: the box's line, its position, and the inverse of pos (order[first + pos_i] = i).
+ *   line_box [n_boxes][4] int32: rows box_first[p] .. box_first[p] + L_p - 1 hold the page's line boxes in line order, the rest of the
+ *   page's rows -1.  n_lines [n_pages] int32 = L_p, med [n_pages] int64.
+ * max_boxes (0..QEA_LINE_MAX_BOXES) is a HOST value the caller vouches for, the largest page; it sizes the workgroup's LDS tables (36 B per
+ * box).  A page of more than max_boxes boxes gets -1 in all of its outputs, n_lines and med included; a page whose range runs backwards or
+ * leaves [0, n_boxes] gets n_lines = med = -1 and nothing else.  Neither is read or written out of bounds.
+ * The lines are found by a min-index union-find in LDS: no loop runs "until converged", every walk moves to a strictly smaller index.
+ * No workspace, no global atomics, nothing synchronises.  Refused before any launch: n_pages < 0, n_boxes < 0, boxes without a page,
+ * max_boxes, overlap, tall or gap outside its range, a NULL or misaligned pointer (boxes and line_box: 16 bytes, med: 8).  n_pages = 0
+ * is accepted and does nothing; n_boxes = 0 clears n_lines and med (hipMemsetAsync on the stream) and launches nothing.
+ * (Additive: no struct changed and qea_version() is unchanged; a caller detects it by symbol.) */
+#define QEA_LINE_MAX_BOXES 4096
+#define QEA_LINE_MAX_TALL 64
+#define QEA_LINE_MAX_GAP 1024
+int qea_line_group(const int32_t* boxes, const int32_t* box_first, int32_t n_pages, int32_t n_boxes, int32_t max_boxes, int32_t overlap,
+                   int32_t tall, int32_t gap, int32_t* line, int32_t* pos, int32_t* order, int32_t* line_box, int32_t* n_lines,
+                   int64_t* med, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

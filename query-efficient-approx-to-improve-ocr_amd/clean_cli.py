@@ -34,10 +34,17 @@ bytes.
 one more launch per CRNN pass) and each row gains "chars": [{"c", "x_min", "x_max", "conf"}], one entry per character of the label: its
 columns on the page (x_max exclusive; y_min / y_max are the row's own) and the mean of its log-probabilities over the steps it
 occupies.  An empty label has an empty list.  The folder still loads as a PatchDataset, which ignores the key.
+[new] --lines [--lines_overlap P --lines_tall T --lines_gap G], with any method; implies --boxes: the word boxes of a --batch_pages group
+go through ONE call of qea/lines.py: group_lines (one launch: neighbours along x that overlap vertically form a line), after the reading,
+which keeps the order read_pages was given.  The rows of <stem>.json are then written in READING order, lines top to bottom and each line
+left to right, and each gains "line"; a line "<stem>: L lines" is printed per page.  The grouping is local and meant for level or
+--deskew'ed pages.  Without the flag nothing changes: the same JSON bytes.
+[new] --text (needs --read, implies --lines): <stem>.txt holds what the CRNN read, the words of a line joined by a space and the lines by
+a newline (lines.page_text; an empty label is skipped).
 
     python clean_cli.py --deskew --method sauvola --boxes --read out/crnn/model_1_0.00 --in_dir scans --out_dir read
 
-is a complete OCR run, and the written folder loads as a labelled PatchDataset.
+is a complete OCR run, and the written folder loads as a labelled PatchDataset; with --text it also writes the pages' text.
 """
 import json
 import os
@@ -45,7 +52,7 @@ import os
 import numpy as np
 import torch
 
-from qea import components, deskew, reading
+from qea import components, deskew, lines, reading
 from qea.binarize import binarize_pages, check_params
 from qea.pages import clean_pages
 from qea.trainer_core import hip_backend
@@ -86,6 +93,17 @@ class CleanPages:
                 raise ValueError("--read_lexicon needs --read_beam K and cannot be combined with --read_lm")
         elif self.read_beam or self.read_lm_path or self.read_lexicon_path or getattr(args, "read_buckets", None):
             raise ValueError("--read_beam, --read_lm, --read_lexicon and --read_buckets need --read CRNN_CHECKPOINT")
+        self.text = bool(getattr(args, "text", False))
+        if self.text and not self.read_path:
+            raise ValueError("--text needs --read CRNN_CHECKPOINT: it writes what the CRNN read")
+        self.lines = bool(getattr(args, "lines", False)) or self.text
+        given = [getattr(args, name, None) for name in ("lines_overlap", "lines_tall", "lines_gap")]
+        if self.lines:
+            self.boxes = True
+            self.lines_params = tuple(d if v is None else v for v, d in zip(given, (50, 3, 0)))
+            lines.check_params(*self.lines_params)
+        elif any(v is not None for v in given):
+            raise ValueError("--lines_overlap, --lines_tall and --lines_gap need --lines")
         if self.despeckle:
             if self.method == "unet":
                 raise ValueError("--despeckle needs --method otsu or sauvola: the UNet's output is grey, and despeckling would binarise it")
@@ -147,6 +165,12 @@ class CleanPages:
                 plan = reading.strip_plan(table, [p.shape[-2] for p in cleaned], [p.shape[-1] for p in cleaned], self.read_buckets)
                 for n, t, m in zip(names, texts, np.bincount(table[plan.cut, 0], minlength=len(names)).tolist()):
                     print(f"{os.path.splitext(n)[0]}: {len(t)} words read, {m} cut")
+            grouped = None
+            if self.lines:                                     # after the reading, which keeps the order read_pages was given
+                grouped = [(o.cpu().tolist(), l.cpu().tolist(), len(lb))
+                           for o, l, lb in lines.group_lines(boxes, *self.lines_params, device=self.device)]
+                for n, (_, _, L) in zip(names, grouped):
+                    print(f"{os.path.splitext(n)[0]}: {L} lines")
             for i, (n, page) in enumerate(zip(names, cleaned)):
                 path = os.path.join(self.out_dir, os.path.splitext(n)[0] + ".png")
                 Image.fromarray(page.cpu().numpy()).save(path)
@@ -160,6 +184,14 @@ class CleanPages:
                             row["score"] = s
                         for row, cs in zip(rows, chars[i] if chars else []):   # y_min / y_max of a character are its row's own
                             row["chars"] = [dict(c=c, x_min=a, x_max=b, conf=v) for c, a, b, v in cs]
+                    if grouped is not None:
+                        order, line, _ = grouped[i]
+                        for row, l in zip(rows, line):
+                            row["line"] = l
+                        rows = [rows[k] for k in order]
+                        if self.text:
+                            with open(os.path.splitext(path)[0] + ".txt", "w") as f:
+                                f.write(lines.page_text(texts[i], order, line))
                     with open(os.path.splitext(path)[0] + ".json", "w") as f:
                         json.dump(rows, f)
         print(f"{len(written)} pages cleaned into {self.out_dir}")

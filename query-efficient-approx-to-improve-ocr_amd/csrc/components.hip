@@ -15,15 +15,13 @@
 //                   the root is the tile-local minimum.  The kernel also clears the in-page elements of `area` when it is given.
 //   border_kernel   one thread per pixel of a tile's bottom row and right column unites it with its neighbours across the edge (the two
 //                   diagonals as well at connectivity 8, which also covers both diagonals through a tile corner).  Lock-free min-index
-//                   union-find on `labels` (Playne & Hawick 2018; Komura 2015): find both roots, atomicMin the larger root's slot with the
-//                   smaller; when the value the atomic returns shows that the slot was no longer a root, go on from that value.
+//                   union-find on `labels` (csrc/union_find.h): find both roots, atomicMin the larger root's slot with the smaller; when
+//                   the value the atomic returns shows that the slot was no longer a root, go on from that value.
 //   flatten_kernel  every ink pixel's label becomes its root.
-// The invariant: labels[x] <= x, and labels[x] is a pixel of x's component.  A link is only ever replaced by a smaller one, and the thread
-// that replaces the link x -> old by x -> b goes on to unite old with b, so no connection is lost.  The smallest pixel m of a component can
-// only point to itself, so it is a root throughout; when the border kernel has ended every adjacent pair has been united, a component has
-// one root, and that root is m.  A load that returns an older value returns an older parent, which is still a smaller member of the same
-// component: only the value atomicMin returns decides whether a union is complete.  Inside the border kernel every access to `labels` is
-// an agent-scope relaxed atomic (the XCDs' L2s are not coherent for plain loads within a launch); kernel boundaries order the rest.
+// The invariant and why no connection is lost are in csrc/union_find.h: labels[x] <= x is a pixel of x's component, the smallest pixel m of
+// a component is a root throughout, and when the border kernel has ended every adjacent pair has been united, so that a component has one
+// root, m.  Inside the border kernel every access to `labels` is an agent-scope relaxed atomic (the XCDs' L2s are not coherent for plain
+// loads within a launch); kernel boundaries order the rest.
 //
 // Termination: no kernel waits for another workgroup.  Every loop over labels / L moves to a strictly smaller index or exits (find), or
 // strictly lowers the larger of its two indices or exits (unite), so its length is bounded by the chain it walks.  A value that is no
@@ -38,6 +36,7 @@
 // qea_cc_boxes, one launch: the same hash table carries x / y minima and maxima per distinct root; a root's rank among the caller's ascending
 // list of roots is found by binary search, and one atomicMin / atomicMax per bound and distinct root reaches boxes[rank].
 #include "page_store.h"
+#include "union_find.h"
 
 namespace {
 
@@ -46,47 +45,6 @@ constexpr int MAX_GAP = QEA_CC_MAX_GAP;
 static_assert(TW == 64 && TH == 32 && THREADS == 256, "a wave owns eight rows of the tile and a lane one column; 8 pixels per thread");
 static_assert((SLOTS & (SLOTS - 1)) == 0 && SLOTS >= TILE, "the hash table holds every pixel of a tile even if all labels differ");
 constexpr int SMEAR_LDS = (TH + 2 * MAX_GAP) * TW > TH * (TW + 2 * MAX_GAP) ? (TH + 2 * MAX_GAP) * TW : TH * (TW + 2 * MAX_GAP);
-
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-#define RLX_GROUP __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
-
-// ---- the union-find, once for a tile in LDS (workgroup scope) and once for a page in global memory (agent scope)
-struct LdsForest {
-  int* L;
-  __device__ __forceinline__ int load(int x) const { return __hip_atomic_load(L + x, RLX_GROUP); }
-  __device__ __forceinline__ int lower(int x, int v) const { return __hip_atomic_fetch_min(L + x, v, RLX_GROUP); }
-};
-struct PageForest {
-  int* L;       // labels + the page's offset
-  __device__ __forceinline__ int load(int x) const { return __hip_atomic_load(L + x, RLX_AGENT); }
-  __device__ __forceinline__ int lower(int x, int v) const { return __hip_atomic_fetch_min(L + x, v, RLX_AGENT); }
-};
-
-template <class F>
-__device__ __forceinline__ int find_root(const F f, int x) {
-  for (;;) {                    // moves to a strictly smaller index or exits: at most the length of the chain it walks
-    const int p = f.load(x);
-    if (p >= x || p < 0) return x;
-    x = p;
-  }
-}
-
-template <class F>
-__device__ __forceinline__ void unite(const F f, int a, int b) {
-  for (;;) {                    // max(a, b) strictly falls from one round to the next, or the loop exits
-    a = find_root(f, a);
-    b = find_root(f, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = f.lower(a, b);            // a > b
-    if (old == a) return;                     // a was a root and now points to b
-    a = old;                                  // a had a parent old < a already: old and b remain to be united
-  }
-}
 
 template <typename T>
 __global__ __launch_bounds__(THREADS) void cc_tile_kernel(const T* __restrict__ store, const PageStore ps,

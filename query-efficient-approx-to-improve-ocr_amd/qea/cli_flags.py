@@ -223,6 +223,21 @@ FLAGS += [
                                                     "(x_max exclusive) and the mean of its log-probabilities"), "n"),
 ]
 
+# [new] word boxes grouped into text lines and the page's plain text (qea/lines.py): what makes the rows of <stem>.json readable in order
+FLAGS += [
+    ("--lines", dict(action="store_true", help="[new] implies --boxes: group the word boxes of every page into text lines (neighbours along x "
+                                               "that overlap vertically), write the rows of <stem>.json in reading order, each with its "
+                                               "'line', and print '<stem>: L lines' per page.  Meant for level or --deskew'ed pages"), "n"),
+    ("--lines_overlap", dict(type=int, help="[new] --lines: per cent of the smaller height two boxes must share vertically to be "
+                                                        "neighbours, 1..100 (default 50)"), "n"),
+    ("--lines_tall", dict(type=int, help="[new] --lines: a box taller than this many median heights (a rule, a picture, a drop cap) "
+                                                    "is a line of its own, 1..64 (default 3)"), "n"),
+    ("--lines_gap", dict(type=int, help="[new] --lines: the largest horizontal gap between neighbours of one line, in median "
+                                                   "heights, 1..1024; 0 = no limit (default)"), "n"),
+    ("--text", dict(action="store_true", help="[new] needs --read, implies --lines: also write <stem>.txt, the words the CRNN read, line by "
+                                              "line in reading order"), "n"),
+]
+
 
 def build_parser(which, description):
     import argparse

@@ -1505,3 +1505,30 @@ def word_strips(store, table, boxes, OW, norm, out=None):
     _lib.check(_lib.lib().qea_word_strips(*args, boxes_p, n, OW, norm_p, out_p, _stream()), "qea_word_strips")
     WORD_STRIP_LAUNCHES["strips"] += 1
     return out
+
+
+LINE_MAX_BOXES, LINE_MAX_TALL, LINE_MAX_GAP = 4096, 64, 1024       # QEA_LINE_MAX_* of include/qea_hip.h
+LINE_LAUNCHES = {"group": 0}                 # launches of csrc/lines.hip issued through this module (tests, tools)
+LineGroups = namedtuple("LineGroups", "line pos order line_box n_lines med")
+
+
+def line_group(boxes, box_first, max_boxes, overlap=50, tall=3, gap=0):
+    """include/qea_hip.h: qea_line_group — boxes int32 [N][4] = (x_min, y_min, x_max, y_max), inclusive, page after page, and box_first
+    int32 [pages + 1], both on the device; max_boxes: the largest page, a host value (a page that holds more gets -1 throughout) ->
+    LineGroups(line, pos, order: int32 [N]; line_box: int32 [N][4], a page's L line boxes in its first L rows and -1 in the rest; n_lines:
+    int32 [pages]; med: int64 [pages]), written by ONE launch on the current stream; nothing is read back."""
+    if not torch.is_tensor(boxes) or boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise _lib.QeaError("line_group: boxes must be an int32 [N][4] tensor = (x_min, y_min, x_max, y_max)")
+    if not torch.is_tensor(box_first) or box_first.dim() != 1 or box_first.numel() < 1:
+        raise _lib.QeaError("line_group: box_first must be an int32 [pages + 1] tensor")
+    dev, N, P = boxes.device, boxes.shape[0], box_first.numel() - 1
+    _tensors("line_group", dev, ("boxes", boxes, torch.int32), ("box_first", box_first, torch.int32))
+    line, pos, order = (torch.empty(N, dtype=torch.int32, device=dev) for _ in range(3))
+    line_box = torch.empty(N, 4, dtype=torch.int32, device=dev)
+    n_lines = torch.empty(P, dtype=torch.int32, device=dev)
+    med = torch.empty(P, dtype=torch.int64, device=dev)
+    out = LineGroups(line, pos, order, line_box, n_lines, med)
+    _lib.check(_lib.lib().qea_line_group(*(t.data_ptr() if t.numel() else None for t in (boxes, box_first)), P, N, int(max_boxes), int(overlap),
+                                         int(tall), int(gap), *(t.data_ptr() if t.numel() else None for t in out), _stream()), "qea_line_group")
+    LINE_LAUNCHES["group"] += int(P > 0 and N > 0)
+    return out
