@@ -128,6 +128,24 @@ def conv_igemm_spec(d, x_buf, w, scale, bias, mask_buf, y_prev, perturb=None):
     return y, written
 
 
+def conv_written(d, size):
+    """flat bool [size]: the `written` of conv_igemm_spec(d, ...) from the three row maps alone, without the arithmetic, for a caller
+    that needs the stored region of a launch at sizes the loops above take minutes for (tests/slot_audit.py).  Reads B OH OW N ldy
+    out_mode y_guard y_off; tests/test_slot_audit_cpu.py holds it to conv_igemm_spec's own mask on every case of CONV_CASES."""
+    b, oh, ow = np.meshgrid(np.arange(d.B), np.arange(d.OH), np.arange(d.OW), indexing="ij")
+    if d.out_mode == OUT_CONVT:
+        co_n = d.N // 4
+        a, bb = np.arange(2).reshape(2, 1, 1, 1, 1), np.arange(2).reshape(1, 2, 1, 1, 1)
+        row = ((b * 2 * d.OH + 2 * oh + a) * 2 * d.OW + 2 * ow + bb).reshape(-1)
+        cols = co_n
+    else:
+        row = (ow * d.B + b if d.out_mode == OUT_TBC else (b * d.OH + oh) * d.OW + ow).reshape(-1)
+        cols = d.N
+    written = np.zeros(size, dtype=bool)
+    written[(d.y_guard + d.y_off + row[:, None] * d.ldy + np.arange(cols)[None, :]).reshape(-1)] = True
+    return written
+
+
 def _walked_pixel(m, PH, PW, skip_image_carry):
     """(image, row, column) of pixel m as the gather reaches it: thread m % BKP starts at pixel m % BKP and advances BKP pixels per
     stage as eq images + er rows + dr columns with two carries (WgGather::fetch).  skip_image_carry: the eq term left out."""

@@ -108,23 +108,30 @@ def digest(entry):
     return hashlib.sha256(json.dumps(entry, sort_keys=True, separators=(",", ":")).encode()).hexdigest()[:12]
 
 
-def _run(case, seed):
+def _run(case, seed, *, spec=None, width=128, state=None, inputs=None, out_grad=None, around=None, passes=None):
+    """One forward (+ backward) of a case -> its log.  The keywords are for tests that run the same cases under other instruments
+    (tests/test_slot_audit_gpu.py) and change nothing that is recorded when left alone: spec = a CASES tuple of its own, width = the
+    image width, state / inputs / out_grad = a transform of the seeded state dict / the input images / the output gradient,
+    around(model, log) = the context the passes run in instead of recording(model, log), passes(model, x, forward kwargs) = what runs
+    there instead of one forward and one backward."""
     import torch
     import helpers as H
     from oracle import model_oracle as mo
     from qea import crnn_engine, unet_engine
-    kind, B, train, grad, kwargs, off = CASES[case]
+    kind, B, train, grad, kwargs, off = CASES[case] if spec is None else spec
     engine = unet_engine if kind == "unet" else crnn_engine
-    x = H.synth_images(B, seed).cuda()
+    x = H.synth_images(B, seed, w=width)
+    x = (x if inputs is None else inputs(x)).cuda()
+    state = state or (lambda sd: sd)
     if kind == "unet":
         from models.model_unet import UNet
         net = UNet()
-        net.load_state_dict(mo.seeded_state(mo.unet_state_shapes(), seed + 1))
+        net.load_state_dict(state(mo.seeded_state(mo.unet_state_shapes(), seed + 1)))
         net = net.cuda().train(train)
     else:
         from models.model_crnn import CRNN
         net = CRNN(95, False)
-        net.load_state_dict(mo.seeded_state(mo.crnn_state_shapes(), seed + 1))
+        net.load_state_dict(state(mo.seeded_state(mo.crnn_state_shapes(), seed + 1)))
         net = net.cuda().train()
         net.register_backward_hook(net.backward_hook)
         if not train:
@@ -137,10 +144,11 @@ def _run(case, seed):
     try:
         for name in off:
             setattr(engine, name, False)
-        with recording(net, log), torch.set_grad_enabled(grad):
-            out = net(x, **kwargs)
-            if grad:
-                out.backward(torch.randn(out.shape, generator=torch.Generator().manual_seed(seed + 2)).cuda())
+        with (around or recording)(net, log), torch.set_grad_enabled(grad):
+            out = net(x, **kwargs) if passes is None else passes(net, x, kwargs)
+            if grad and passes is None:
+                g = torch.randn(out.shape, generator=torch.Generator().manual_seed(seed + 2))
+                out.backward((g if out_grad is None else out_grad(g)).cuda())
             torch.cuda.synchronize()
     finally:
         for name, v in before.items():
