@@ -829,6 +829,184 @@ struct Halo9Plan {
 };
 
 constexpr int H9_HP_MAX = 136;   // halo pixels: (2+2) x (32+2) or (4+2) x (16+2) = 108
+static_assert(H9_HP_MAX == 136 && H9_HP_MAX >= 6 * 18, "launch_halo9_ sizes the Q planes of wgrad_halo9_bf3_kernel by this");
+
+// ---------------------------------------------------------------------------------------------
+// The device parts of the nine-tap family.  wgrad_halo9_bf3_kernel and the two producer / consumer kernels are built from this one
+// set, which is what keeps their staging, LDS rows, product order and slab layout the same: a change to one of them is made here.
+// ---------------------------------------------------------------------------------------------
+constexpr int H9_NT = 256;   // threads that gather and stage a tile: the whole workgroup (bf3) or the four producer waves
+
+// the r_blks x c_blks workgroups of one split walk the SAME pixel tiles: the XCD swizzle gives them consecutive slots of one
+// XCD, so the tiles come out of that XCD's L2 instead of being fetched by all eight (PMC: 2.1 GB -> see DESIGN.md per launch)
+struct H9Block { int c_blk, r_blk, split; };
+__device__ __forceinline__ H9Block h9_block(const Halo9Plan& hp) {
+  int bid = qea_xcd_swizzle(blockIdx.x, gridDim.x);
+  H9Block b;
+  b.c_blk = bid % hp.c_blks;
+  bid /= hp.c_blks;
+  b.r_blk = bid % hp.r_blks;
+  b.split = bid / hp.r_blks;
+  return b;
+}
+
+struct H9Tile { int b, x0, y0; };
+template <int SW>
+__device__ __forceinline__ H9Tile h9_tile(const Halo9Plan& hp, int tile) {   // tile index (image-major, then tile row, then column) -> corner
+  const int tx = tile % hp.tiles_x;
+  const int ty = (tile / hp.tiles_x) % hp.tiles_y;
+  return {tile / (hp.tiles_x * hp.tiles_y), tx * SW, ty * (64 / SW)};
+}
+
+// transposing-read geometry of a lane (see tr_frag): pixel (g16 >> 1) * 8 + tq (+ 4 for the second read) of the
+// 16-pixel k-step, channels (g16 & 1) * 16 + tpp * 4 of the wave's 32-channel chunk
+struct H9Lane { int pix, ch; };
+__device__ __forceinline__ H9Lane h9_lane(int lane) {
+  const int g16 = lane >> 4, tq = (lane & 15) >> 2, tpp = lane & 3;
+  return {(g16 >> 1) * 8 + tq, (g16 & 1) * 16 + tpp * 4};
+}
+// byte offset (64-channel rows) of the P fragment of k-step ks below LDS pixel row ks * 16 (ks * 16 is a multiple of 4: the chunk
+// swap only depends on the lane's pixel); wr = the wave's 32-channel half
+__device__ __forceinline__ int h9_p_off(const H9Lane ln, int wr) { return ln.pix * 128 + ((((wr ^ (ln.pix >> 1)) & 1) << 5) + ln.ch) * 2; }
+// Q fragment at halo pixel c + l_pix (c a compile-time tap offset): the chunk swap follows the parity of (c + l_pix) >> 1 -> four
+// loop-invariant bases by (c & 1, (c >> 1) & 1) and an immediate c * 128
+__device__ __forceinline__ void h9_q_offs(const H9Lane ln, int wc, int (&TQ)[2][2]) {
+#pragma unroll
+  for (int par = 0; par < 2; ++par)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int hs = (par ? (ln.pix + 1) >> 1 : ln.pix >> 1) + b;
+      TQ[par][b] = ln.pix * 128 + ((((wc ^ hs) & 1) << 5) + ln.ch) * 2;
+    }
+}
+
+// element offset of float4 chunk c4 of LDS pixel row pix: 64-channel rows swap their two 64-byte chunks by (pix >> 1) & 1;
+// 32-channel rows are one chunk (four pixel rows of a transposing read already fall on four 64-byte bank ranges)
+template <int CHW>
+__device__ __forceinline__ int h9_row_off(int pix, int c4) {
+  return CHW == 64 ? pix * 64 + ((((c4 >> 3) ^ (pix >> 1)) & 1) << 5) + (c4 & 7) * 4 : pix * 32 + c4 * 4;
+}
+
+// The gathers.  The H9_NT threads t of the staging group take the float4 chunks e = t + H9_NT i of a tile, i = 0, 1, ...; these return
+// chunk e.  (Helpers that filled the whole register array through a reference cost wgrad_halo9_bf3_kernel<32, 64, 64, 2> one more
+// spilled register, 44 -> 48 B of scratch; returning one chunk keeps every instance at or below its count.)
+// dY: pixel e / C4 of the 64-pixel, SW-wide tile, chunk e % C4 of the channel block at r0
+template <int SW, int C4>
+__device__ __forceinline__ f32x4 h9_p_chunk(const float* p, int e, const H9Tile tl, int H, int W, int ldp, int r0) {
+  const int c4 = e % C4, pix = e / C4;
+  const int py = pix / SW, px = pix - py * SW;
+  return *reinterpret_cast<const f32x4*>(p + ((size_t)(tl.b * H + tl.y0 + py) * W + tl.x0 + px) * ldp + r0 + c4 * 4);
+}
+// X halo: pixel e / C4 of rows hy0 .. hy0 + rows - 1 of the tile's halo (HWD pixels wide, row 0 / column 0 one pixel outside the tile),
+// chunk e % C4 of the channel block at c0; zeros outside the image and past the last row
+template <int HWD, int C4>
+__device__ __forceinline__ f32x4 h9_halo_chunk(const float* q, int e, const H9Tile tl, int H, int W, int hy0, int rows, int ldq, int c0) {
+  const int c4 = e % C4, hq = e / C4;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (hq < rows * HWD) {
+    const int hr = hq / HWD, hy = hy0 + hr, hx = hq - hr * HWD;
+    const int iy = tl.y0 + hy - 1, ix = tl.x0 + hx - 1;
+    if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = *reinterpret_cast<const f32x4*>(q + ((size_t)(tl.b * H + iy) * W + ix) * ldq + c0 + c4 * 4);
+  }
+  return v;
+}
+
+// split a staged float4 and store it at element o of each plane: NPL = 2 two fp16 planes (h, l) of v * s, NPL = 3 three bf16 planes (h, m, l).
+// The plane's offset is added before o, as the kernels spelled it: with (plane0 + o) + plane the three-plane 64 x 64 instances spill otherwise
+template <int NPL>
+__device__ __forceinline__ void h9_split_store(void* plane0, int plane_elems, int o, const f32x4 v, float s) {
+  if constexpr (NPL == 2) {
+    _Float16* d = reinterpret_cast<_Float16*>(plane0);
+    f16x4 h, l;
+    qea_split2_f16(v, s, h, l);
+    *reinterpret_cast<f16x4*>(d + o) = h;
+    *reinterpret_cast<f16x4*>(d + plane_elems + o) = l;
+  } else {
+    __bf16* d = reinterpret_cast<__bf16*>(plane0);
+    bf16x4 h, m, l;
+    qea_split3(v, h, m, l);
+    *reinterpret_cast<bf16x4*>(d + o) = h;
+    *reinterpret_cast<bf16x4*>(d + plane_elems + o) = m;
+    *reinterpret_cast<bf16x4*>(d + 2 * plane_elems + o) = l;
+  }
+}
+
+// bias gradient (round 4): the column sums of dY ride with the staging — every dY element passes through the staging registers exactly
+// once per channel-block column, so the workgroups of column block 0 add what they stage (fp64, channels t % 16 * 4 ... + 3 of a thread)
+__device__ __forceinline__ void h9_bias_add(double (&bsum)[4], const f32x4 v) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) bsum[k] += (double)v[k];
+}
+// lanes l, l + 16, l + 32, l + 48 of a wave hold the same four channels (pixel rows 4 apart): wave sums, then one partial row per
+// (split, producer wave): [splits * 4][R] doubles, summed in a fixed order by bias_finalize_kernel (fp64 to the end, as qea_colsum:
+// in front of a batch-statistics BatchNorm this gradient is an exact zero made of cancelling terms).  row = this wave's 64 channels
+__device__ __forceinline__ void h9_bias_store(double (&bsum)[4], double* __restrict__ row, int lane) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    double v = bsum[k];
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    bsum[k] = v;
+  }
+  if (lane < 16) {
+    double* dst = row + lane * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dst[k] = bsum[k];
+  }
+}
+
+// the products of one tap, smallest terms first (the ll-class terms are dropped).  Two fp16 planes {h, l}: lh, hl, hh.  Three bf16
+// planes {h, m, l}: lh, hl, mm, mh, hm, hh.  This order is part of the result's bits: every nine-tap kernel takes it from here.
+template <class F>
+__device__ __forceinline__ void h9_tap_mma(f32x16& a9, const F* af, const F* bf) {
+  if constexpr (std::is_same<F, f16x8>::value) {
+    a9 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], bf[0], a9, 0, 0, 0);
+    a9 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[1], a9, 0, 0, 0);
+    a9 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[0], a9, 0, 0, 0);
+  } else {
+    a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2], bf[0], a9, 0, 0, 0);
+    a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[2], a9, 0, 0, 0);
+    a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[1], a9, 0, 0, 0);
+    a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[0], a9, 0, 0, 0);
+    a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[1], a9, 0, 0, 0);
+    a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[0], a9, 0, 0, 0);
+  }
+}
+
+// one 64-pixel tile of the producer / consumer form: four k-steps x nine taps, the fragments of step f + 1 (and the P fragments of
+// the next k-step) read ahead of the MFMAs of step f.  read_p(ks, af[2]) / read_q(f = ks * 9 + tap, bf[2]) fill {h, l}
+template <class ReadP, class ReadQ>
+__device__ __forceinline__ void h9_mma_tile(f32x16 (&acc)[9], ReadP read_p, ReadQ read_q) {
+  f16x8 af[2][2], bq[2][2];
+  read_p(0, af[0]);
+  read_q(0, bq[0]);
+#pragma unroll
+  for (int f = 0; f < 36; ++f) {
+    const int ks = f / 9, tap = f % 9;
+    const f16x8* a = af[ks & 1];
+    const f16x8* b = bq[f & 1];
+    if (f + 1 < 36) read_q(f + 1, bq[(f + 1) & 1]);
+    if (tap == 0 && ks + 1 < 4) read_p(ks + 1, af[(ks + 1) & 1]);
+    h9_tap_mma(acc[tap], a, b);
+    if (f + 1 < 36) {
+      if (tap == 0 && ks + 1 < 4) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+      else __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+    }
+  }
+}
+
+// a wave's 32 x 9 x 32 block at (rbase, cbase) of the partial slab `out` ([R][9][C]), un-scaled by the two powers of two (exact)
+__device__ __forceinline__ void h9_store_slab(float* __restrict__ out, const f32x16 (&acc)[9], int lane, int rbase, int cbase, int C, float inv_p, float inv_q) {
+  const int fr = lane & 31, fh = lane >> 5;
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int rr = rbase + (r & 3) + 8 * (r >> 2) + 4 * fh;
+      out[((size_t)rr * 9 + t) * C + cbase + fr] = (acc[t][r] * inv_p) * inv_q;
+    }
+}
 
 // RB / CB = channel block of dY / X per workgroup (64, or 32 for the 32-channel level): 2x2 waves of 32x32 sub-blocks for
 // 64x64; with fewer sub-blocks the spare waves split the tile's four k-steps (WK = 4 / sub-blocks) and write separate slabs.
@@ -858,14 +1036,8 @@ void wgrad_halo9_bf3_kernel(const float* __restrict__ p, const float* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wk = wave / (WR * WC), wrc = wave % (WR * WC);
   const int wr = wrc / WC, wc = wrc % WC;
-  // the r_blks x c_blks workgroups of one split walk the SAME pixel tiles: the XCD swizzle gives them consecutive slots of one
-  // XCD, so the tiles come out of that XCD's L2 instead of being fetched by all eight (PMC: 2.1 GB -> see DESIGN.md per launch)
-  int bid = qea_xcd_swizzle(blockIdx.x, gridDim.x);
-  const int c_blk = bid % hp.c_blks;
-  bid /= hp.c_blks;
-  const int r_blk = bid % hp.r_blks;
-  const int split = bid / hp.r_blks;
-  const int r0 = r_blk * RB, c0 = c_blk * CB;
+  const H9Block blk = h9_block(hp);
+  const int split = blk.split, r0 = blk.r_blk * RB, c0 = blk.c_blk * CB;
 
   f32x16 acc[9];
 #pragma unroll
@@ -873,103 +1045,35 @@ void wgrad_halo9_bf3_kernel(const float* __restrict__ p, const float* __restrict
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-  // gather: element e = tid + 256 i -> pixel e / (channels / 4), float4 chunk e % (channels / 4)
-  constexpr int NP = 64 * RC4 / 256;                        // 4 (RB 64) / 2 (RB 32)
-  constexpr int NQ = (HP * CC4 + 255) / 256;
+  constexpr int NP = 64 * RC4 / H9_NT;                      // 4 (RB 64) / 2 (RB 32)
+  constexpr int NQ = (HP * CC4 + H9_NT - 1) / H9_NT;
   f32x4 preg[NP], qreg[NQ];
   auto fetch = [&](int tile) {
-    const int tx = tile % hp.tiles_x;
-    const int ty = (tile / hp.tiles_x) % hp.tiles_y;
-    const int b = tile / (hp.tiles_x * hp.tiles_y);
-    const int x0 = tx * SW, y0 = ty * TH;
+    const H9Tile tl = h9_tile<SW>(hp, tile);
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int e = tid + 256 * i;
-      const int c4 = e % RC4, pix = e / RC4;
-      const int py = pix / SW, px = pix - py * SW;
-      preg[i] = *reinterpret_cast<const f32x4*>(p + ((size_t)(b * H + y0 + py) * W + x0 + px) * ldp + r0 + c4 * 4);
-    }
+    for (int i = 0; i < NP; ++i) preg[i] = h9_p_chunk<SW, RC4>(p, tid + H9_NT * i, tl, H, W, ldp, r0);
 #pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      const int e = tid + 256 * i;
-      const int c4 = e % CC4, hq = e / CC4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (hq < HP) {
-        const int hy = hq / HW_, hx = hq - hy * HW_;
-        const int iy = y0 + hy - 1, ix = x0 + hx - 1;
-        if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = *reinterpret_cast<const f32x4*>(q + ((size_t)(b * H + iy) * W + ix) * ldq + c0 + c4 * 4);
-      }
-      qreg[i] = v;
-    }
+    for (int i = 0; i < NQ; ++i) qreg[i] = h9_halo_chunk<HW_, CC4>(q, tid + H9_NT * i, tl, H, W, 0, HH, ldq, c0);
   };
-  // element offset of float4 chunk c4 of LDS pixel row pix: 64-channel rows swap their two 64-byte chunks by (pix >> 1) & 1;
-  // 32-channel rows are one chunk (four pixel rows of a transposing read already fall on four 64-byte bank ranges)
-  auto row_off = [](int pix, int c4, int chw) { return chw == 64 ? pix * 64 + ((((c4 >> 3) ^ (pix >> 1)) & 1) << 5) + (c4 & 7) * 4 : pix * 32 + c4 * 4; };
   auto stage = [&]() {
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      const int e = tid + 256 * i;
-      const int c4 = e % RC4, pix = e / RC4;
-      const int o = row_off(pix, c4, RB);
-      if constexpr (F16) {
-        f16x4 h, l;
-        qea_split2_f16(preg[i], sp, h, l);
-        *reinterpret_cast<f16x4*>(Ps + o) = h;
-        *reinterpret_cast<f16x4*>(Ps + P_PLANE + o) = l;
-      } else {
-        bf16x4 h, m, l;
-        qea_split3(preg[i], h, m, l);
-        *reinterpret_cast<bf16x4*>(Ps + o) = h;
-        *reinterpret_cast<bf16x4*>(Ps + P_PLANE + o) = m;
-        *reinterpret_cast<bf16x4*>(Ps + 2 * P_PLANE + o) = l;
-      }
+      const int e = tid + H9_NT * i;
+      h9_split_store<NPL>(Ps, P_PLANE, h9_row_off<RB>(e / RC4, e % RC4), preg[i], sp);
     }
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
-      const int e = tid + 256 * i;
-      const int c4 = e % CC4, hq = e / CC4;
-      if (hq < HP) {
-        const int o = row_off(hq, c4, CB);
-        if constexpr (F16) {
-          f16x4 h, l;
-          qea_split2_f16(qreg[i], sq, h, l);
-          *reinterpret_cast<f16x4*>(Qs + o) = h;
-          *reinterpret_cast<f16x4*>(Qs + Q_PLANE + o) = l;
-        } else {
-          bf16x4 h, m, l;
-          qea_split3(qreg[i], h, m, l);
-          *reinterpret_cast<bf16x4*>(Qs + o) = h;
-          *reinterpret_cast<bf16x4*>(Qs + Q_PLANE + o) = m;
-          *reinterpret_cast<bf16x4*>(Qs + 2 * Q_PLANE + o) = l;
-        }
-      }
+      const int e = tid + H9_NT * i;
+      if (e / CC4 < HP) h9_split_store<NPL>(Qs, Q_PLANE, h9_row_off<CB>(e / CC4, e % CC4), qreg[i], sq);
     }
   };
-  // transposing-read geometry of this lane (see tr_frag): pixel (g16 >> 1) * 8 + tq (+ 4 for the second read) of the
-  // 16-pixel k-step, channels (g16 & 1) * 16 + tpp * 4 of the wave's 32-channel chunk
-  const int g16 = lane >> 4, tq = (lane & 15) >> 2, tpp = lane & 3;
-  const int l_pix = (g16 >> 1) * 8 + tq;
-  const int l_ch = (g16 & 1) * 16 + tpp * 4;
+  const H9Lane ln = h9_lane(lane);
+  const int l_pix = ln.pix, l_ch = ln.ch;
   auto frag_p = [&](const __bf16* plane, int pix) -> frag_t {   // pix = LDS pixel row of this lane's first 4-pixel block
     return __builtin_bit_cast(frag_t, RB == 64 ? tr_frag(plane + pix * 64 + (((wr ^ (pix >> 1)) & 1) << 5) + l_ch, 64) : tr_frag(plane + pix * 32 + l_ch, 32));
   };
   auto frag_q = [&](const __bf16* plane, int pix) -> frag_t {   // ((pix + 4) >> 1 has the parity of pix >> 1: both reads share the swap)
     return __builtin_bit_cast(frag_t, CB == 64 ? tr_frag(plane + pix * 64 + (((wc ^ (pix >> 1)) & 1) << 5) + l_ch, 64) : tr_frag(plane + pix * 32 + l_ch, 32));
-  };
-  // the products of one tap: smallest terms first (the ll-class terms are dropped)
-  auto mma = [&](f32x16& a9, const frag_t* af, const frag_t* bf) {
-    if constexpr (F16) {
-      a9 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], bf[0], a9, 0, 0, 0);
-      a9 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[1], a9, 0, 0, 0);
-      a9 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[0], a9, 0, 0, 0);
-    } else {
-      a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2], bf[0], a9, 0, 0, 0);
-      a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[2], a9, 0, 0, 0);
-      a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[1], a9, 0, 0, 0);
-      a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[0], a9, 0, 0, 0);
-      a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[1], a9, 0, 0, 0);
-      a9 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[0], a9, 0, 0, 0);
-    }
   };
 
   int tile = split;
@@ -1002,7 +1106,7 @@ void wgrad_halo9_bf3_kernel(const float* __restrict__ p, const float* __restrict
         for (int t = 0; t < 9; ++t) {
           const frag_t* bf = bq2[t & 1];
           if (t + 1 < 9) read_q(t + 1, bq2[(t + 1) & 1]);
-          mma(acc[t], af, bf);
+          h9_tap_mma(acc[t], af, bf);
           if (t + 1 < 9) {
             __builtin_amdgcn_sched_group_barrier(0x100, 2 * NPL, 0);          // the LDS reads of tap t + 1 ...
             __builtin_amdgcn_sched_group_barrier(0x008, F16 ? 3 : 6, 0);      // ... ahead of the MFMAs of tap t
@@ -1017,12 +1121,15 @@ void wgrad_halo9_bf3_kernel(const float* __restrict__ p, const float* __restrict
             frag_t bf[NPL];
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl) bf[pl] = frag_q(Qs + pl * Q_PLANE, hq);
-            mma(acc[kh * 3 + kw], af, bf);
+            h9_tap_mma(acc[kh * 3 + kw], af, bf);
           }
       }
     }
   }
-  // this wave's 32 x 9 x 32 block of the partial slab of (its split, its k-step share): [R][9][C]
+  // this wave's 32 x 9 x 32 block of the partial slab of (its split, its k-step share): [R][9][C].  h9_store_slab's loop, spelled in place:
+  // through the helper the 64 x 64 instances are allocated two SGPRs fewer and lose 8 - 9 scalar instructions, and the three-plane 4 x 32
+  // shapes then measured 5 - 11 us over the parent's 2.8 - 5.4 ms where its own two runs agreed to 1 - 10 us (profiles/wgrad9_parts_ab.json);
+  // in place the four three-plane instances are the parent's code to the byte
   float* out = ws + ((size_t)split * WK + wk) * R * 9 * C;
   const int fr = lane & 31, fh = lane >> 5;
 #pragma unroll
@@ -1039,12 +1146,17 @@ void wgrad_halo9_bf3_kernel(const float* __restrict__ p, const float* __restrict
 // measured it: 299 -> 381 TFLOP/s at 256 x 256 channels, 8 x 32 pixels, B = 2048).  In the kernel above every wave gathers, splits,
 // stores, waits at two barriers and only then multiplies: staging was 46 % of a tile's MFMA time and the matrix pipe 0.41 busy.  Here a
 // workgroup has EIGHT waves: waves 0-3 (one per SIMD) only run MFMAs — each a 32 x 32 sub-block, nine accumulator tiles — and waves
-// 4-7 (their SIMD partners) gather, split and write the NEXT 64-pixel tile into the other of two LDS buffers (50 KB each) while the
-// consumers read this one: ONE barrier per tile, the split's VALU work beside the MFMAs instead of in front of them.  One workgroup
-// per CU (100 KB of LDS), the pixel tiles dealt over 256 / (channel blocks) splits; slabs and their fixed-order reduction as above.
-// Same LDS rows (pixels x 64 channels, 64-byte chunks swapped by (pixel >> 1) & 1), same products in the same order per tile as the
-// kernel above — the slab layout (one per split) and the number of splits differ, so the two forms agree to fp32 rounding, not bit
-// for bit; each is bit-reproducible.
+// 4-7 (their SIMD partners) gather, split and write the NEXT 64-pixel tile into LDS while the consumers read this one: ONE barrier per
+// tile, the split's VALU work beside the MFMAs instead of in front of them.  One workgroup per CU (86 - 100 KB of LDS), the pixel tiles
+// dealt over 256 / (channel blocks) splits; slabs and their fixed-order reduction as above.  Same LDS rows (pixels x 64 channels, 64-byte
+// chunks swapped by (pixel >> 1) & 1), same products in the same order per tile as the kernel above — the slab layout (one per split) and
+// the number of splits differ, so the two forms agree to fp32 rounding, not bit for bit; each is bit-reproducible.
+//
+// There is ONE body, halo9_pc_body, parameterised by how the X halo lives in LDS (a halo policy).  The policy answers: the LDS size and
+// Q plane stride; the workgroup's tile count and the tile -> (b, x0, y0) walk; which halo rows the producers fetch for tile t and at
+// which LDS pixel row each lands; the consumer's per-tile base table and the address of tap fragment (ks, tap).  P staging, bias sums,
+// barriers, pipeline order, consumer loop and epilogue are the body's.  The two policies deal tiles to splits differently (a stride /
+// whole strips), so their kernels agree to fp32 rounding and each is bit-reproducible.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ f16x8 tr_pair128(const char* base) {   // this lane's 4-pixel block and the block 4 pixel rows (512 bytes) further
   typedef __attribute__((address_space(3))) s16x4* lds_ptr;
@@ -1061,298 +1173,137 @@ __global__ void bias_finalize_kernel(const double* __restrict__ ws, int nblk, in
   if ((threadIdx.x & 63) == 0) out[c] = accumulate ? out[c] + (float)a : (float)a;
 }
 
-template <int SW>
-constexpr size_t halo9_spec_lds() { return (size_t)2 * (2 * 64 * 64 * 2 + 2 * ((64 / SW + 2) * (SW + 2)) * 64 * 2); }
+constexpr int H9_P_PLANE_B = 64 * 64 * 2;   // bytes of one fp16 plane of a staged dY tile (64 pixels x 64 channels)
 
-template <int SW>
-__global__ __launch_bounds__(512) void wgrad_halo9_spec_kernel(const float* __restrict__ p, const float* __restrict__ q, float* __restrict__ ws, int B,
-                                                               int H, int W, int R, int C, int ldp, int ldq, Halo9Plan hp,
-                                                               const float* __restrict__ pmax, const float* __restrict__ qmax,
-                                                               double* __restrict__ bias_ws) {
-  constexpr int TH = 64 / SW, HWD = SW + 2, HH = TH + 2, HP = HH * HWD;
-  constexpr int P_PLANE_B = 64 * 64 * 2, Q_PLANE_B = HP * 64 * 2;            // bytes per plane
-  constexpr int BUF_B = 2 * P_PLANE_B + 2 * Q_PLANE_B;                        // one buffer: P h, P l, Q h, Q l
+struct H9HaloRows { int hy0, n, row0; };   // a producer's halo registers hold rows hy0 .. hy0 + n - 1 of a tile's halo, the first bound for LDS row slot row0
+
+// Policy 1: the whole six-row halo of a 4 x 16 tile, double-buffered together with the dY planes (43 KB per buffer).  The workgroup's
+// tiles are split, split + splits, ...  The 16-wide geometry is a constant of this policy: every 32-wide launch goes to the ring.
+struct Halo9Whole16 {
+  static constexpr int SW = 16, HWD = 18, FETCH_ROWS = 6, TAB_ROWS = 1;
+  static constexpr int Q_PLANE_B = 6 * HWD * 64 * 2;
+  static constexpr int BUF_B = 2 * H9_P_PLANE_B + 2 * Q_PLANE_B;                  // one buffer: P h, P l, Q h, Q l
+  static constexpr int P_BUF_B = BUF_B, Q_BASE_B = 2 * H9_P_PLANE_B, Q_BUF_B = BUF_B;
+  static constexpr size_t LDS = (size_t)2 * BUF_B;
+  const Halo9Plan& hp;
+  const int split, ntl;
+  __device__ __forceinline__ Halo9Whole16(const Halo9Plan& hp_, int split_, int)
+      : hp(hp_), split(split_), ntl((hp_.n_tiles - split_ + hp_.splits - 1) / hp_.splits) {}
+  __device__ __forceinline__ H9Tile tile(int t) const { return h9_tile<SW>(hp, split + t * hp.splits); }
+  __device__ __forceinline__ H9HaloRows halo_rows(int) const { return {0, FETCH_ROWS, 0}; }
+  __device__ __forceinline__ static int lds_row(int, int j) { return j; }
+  __device__ __forceinline__ void q_table(int, const int (&TQ)[2][2], int (&tab)[TAB_ROWS][2][2]) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tab[0][i >> 1][i & 1] = TQ[i >> 1][i & 1];
+  }
+  __device__ __forceinline__ static int q_frag(const int (&tab)[TAB_ROWS][2][2], int ks, int tap) {
+    const int py = (ks * 16) / SW, px0 = (ks * 16) % SW;
+    const int c = (py + tap / 3) * HWD + px0 + tap % 3;
+    return tab[0][c & 1][(c >> 1) & 1] + c * 128;
+  }
+};
+
+// Policy 2: the X halo of 2 x 32 tiles in a RING (round 4, tools/micro/wgrad_lab.hip: 380 -> 399 TFLOP/s at 256 x 256 channels and
+// 8 x 32 pixels, 297 -> 335 at 64 x 64 and 16 x 64, 397 -> 404 at 512 x 512 and 4 x 32).  A 2-row tile has a 4-row halo: walking the
+// tiles of one image column top to bottom, two of the four rows are the previous tile's.  A workgroup therefore takes whole column
+// strips (contiguous ranges of (image, column tile) pairs) and keeps the halo in a ring of 8 pixel rows: a tile reads ring rows
+// g .. g + 3, the producers meanwhile write the next tile's NEW rows — g + 4, g + 5 inside a strip, g + 4 .. g + 7 for the first tile
+// of the next strip — so they gather and split 68 instead of 136 halo pixels per tile.  g is even and a ring row holds an even number
+// of pixels, so the chunk-swap parity of a tap only needs the row's index inside the halo: a tap's address is one of 16 per-tile
+// registers (4 rows x the 4 table entries) + an immediate.  The dY planes are double-buffered in front of the ring.
+struct Halo9Ring32 {
+  static constexpr int SW = 32, HWD = 34, RING = 8, FETCH_ROWS = 4, TAB_ROWS = 4;   // FETCH_ROWS: a whole four-row halo at a strip start
+  static constexpr int Q_PLANE_B = RING * HWD * 64 * 2;
+  static constexpr int P_BUF_B = 2 * H9_P_PLANE_B, Q_BASE_B = 2 * P_BUF_B, Q_BUF_B = 0;   // [2 buffers][h, l][64 px][64 ch], then [h, l][8 ring rows][34][64 ch]
+  static constexpr size_t LDS = (size_t)Q_BASE_B + 2 * Q_PLANE_B;
+  const Halo9Plan& hp;
+  int s0, ntl;                                                // first strip; this workgroup's tiles, in (strip, tile row) order
+  __device__ __forceinline__ Halo9Ring32(const Halo9Plan& hp_, int split, int B) : hp(hp_) {
+    const int n_strips = B * hp.tiles_x;                      // (hp.splits <= n_strips)
+    s0 = (int)((long long)n_strips * split / hp.splits);
+    ntl = ((int)((long long)n_strips * (split + 1) / hp.splits) - s0) * hp.tiles_y;
+  }
+  __device__ __forceinline__ int ring_of(int t) const { return ((t + t / hp.tiles_y) * 2) & 7; }   // + 2 per tile inside a strip, + 4 across strips
+  __device__ __forceinline__ H9Tile tile(int t) const {
+    const int st = s0 + t / hp.tiles_y, ty = t % hp.tiles_y;
+    return {st / hp.tiles_x, (st % hp.tiles_x) * SW, ty * 2};
+  }
+  __device__ __forceinline__ H9HaloRows halo_rows(int t) const {
+    const int hy0 = t % hp.tiles_y == 0 ? 0 : 2;              // all four halo rows at a strip start, else the two new ones
+    return {hy0, 4 - hy0, (ring_of(t) + hy0) & 7};
+  }
+  __device__ __forceinline__ static int lds_row(int row0, int j) { return (row0 + j) & 7; }
+  __device__ __forceinline__ void q_table(int t, const int (&TQ)[2][2], int (&tab)[TAB_ROWS][2][2]) const {
+    const int g = ring_of(t);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int rowoff = ((g + k) & 7) * (HWD * 128);
+#pragma unroll
+      for (int par = 0; par < 2; ++par)
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb) tab[k][par][bb] = TQ[par][bb] + rowoff;
+    }
+  }
+  __device__ __forceinline__ static int q_frag(const int (&tab)[TAB_ROWS][2][2], int ks, int tap) {
+    const int py = (ks * 16) / SW, px0 = (ks * 16) % SW;
+    const int k = py + tap / 3, col = px0 + tap % 3;
+    return tab[k][col & 1][((col >> 1) + k) & 1] + col * 128;
+  }
+};
+
+// what launch_halo9 reserves, and the one-workgroup-per-CU claim above, rest on these
+static_assert(Halo9Ring32::LDS == 102400, "ring form: 2 x 16 KB of dY planes + 2 x 34 KB of ring");
+static_assert(Halo9Whole16::LDS == 88064, "16-wide form: 2 x (16 KB of dY planes + 27 KB of halo)");
+
+template <class HaloT>
+__device__ __forceinline__ void halo9_pc_body(const float* __restrict__ p, const float* __restrict__ q, float* __restrict__ ws, int B, int H, int W, int R,
+                                              int C, int ldp, int ldq, const Halo9Plan& hp, const float* __restrict__ pmax,
+                                              const float* __restrict__ qmax, double* __restrict__ bias_ws) {
+  constexpr int HWD = HaloT::HWD;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  char* lds = reinterpret_cast<char*>(smem);
+  char* const lds = reinterpret_cast<char*>(smem);
   float sp, sq, inv_p, inv_q;
   qea_f16_scale(pmax[0], sp, inv_p);
   qea_f16_scale(qmax[0], sq, inv_q);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int bid = qea_xcd_swizzle(blockIdx.x, gridDim.x);
-  const int c_blk = bid % hp.c_blks;
-  bid /= hp.c_blks;
-  const int r_blk = bid % hp.r_blks;
-  const int split = bid / hp.r_blks;
-  const int r0 = r_blk * 64, c0 = c_blk * 64;
-  const int ntl = (hp.n_tiles - split + hp.splits - 1) / hp.splits;          // tiles of this workgroup: split, split + splits, ...
+  const H9Block blk = h9_block(hp);
+  const int split = blk.split, r0 = blk.r_blk * 64, c0 = blk.c_blk * 64;
+  const HaloT halo(hp, split, B);
+  const int ntl = halo.ntl;
 
   if (wave >= 4) {
     // ---------------------------------------------------------------- producers
     const int pt = tid - 256;
-    constexpr int NP = 64 * 16 / 256, NQ = (HP * 16 + 255) / 256;
+    constexpr int NP = 64 * 16 / H9_NT, NQ = (HaloT::FETCH_ROWS * HWD * 16 + H9_NT - 1) / H9_NT;
     f32x4 preg[NP], qreg[NQ];
-    // bias gradient (round 4): the column sums of dY ride with the staging — every dY element passes through these registers exactly once
-    // per channel-block column, so the workgroups of column block 0 add what they stage (fp64, channels pt % 16 * 4 ... + 3 of this thread)
-    const bool do_bias = bias_ws != nullptr && c_blk == 0;
-    double bsum[4] = {0.0, 0.0, 0.0, 0.0};
-    auto fetch = [&](int tile) {
-      const int tx = tile % hp.tiles_x;
-      const int ty = (tile / hp.tiles_x) % hp.tiles_y;
-      const int b = tile / (hp.tiles_x * hp.tiles_y);
-      const int x0 = tx * SW, y0 = ty * TH;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        const int e = pt + 256 * i;
-        const int c4 = e % 16, pix = e / 16;
-        const int py = pix / SW, px = pix - py * SW;
-        preg[i] = *reinterpret_cast<const f32x4*>(p + ((size_t)(b * H + y0 + py) * W + x0 + px) * ldp + r0 + c4 * 4);
-      }
-#pragma unroll
-      for (int i = 0; i < NQ; ++i) {
-        const int e = pt + 256 * i;
-        const int c4 = e % 16, hq = e / 16;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (hq < HP) {
-          const int hy = hq / HWD, hx = hq - hy * HWD;
-          const int iy = y0 + hy - 1, ix = x0 + hx - 1;
-          if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = *reinterpret_cast<const f32x4*>(q + ((size_t)(b * H + iy) * W + ix) * ldq + c0 + c4 * 4);
-        }
-        qreg[i] = v;
-      }
-    };
-    auto row_off = [](int pix, int c4) { return pix * 64 + ((((c4 >> 3) ^ (pix >> 1)) & 1) << 5) + (c4 & 7) * 4; };   // 16-bit elements
-    auto stage = [&](char* buf) {
-      _Float16* Ps = reinterpret_cast<_Float16*>(buf);
-      _Float16* Qs = reinterpret_cast<_Float16*>(buf + 2 * P_PLANE_B);
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        const int e = pt + 256 * i;
-        const int o = row_off(e / 16, e % 16);
-        if (do_bias) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) bsum[k] += (double)preg[i][k];
-        }
-        f16x4 h, l;
-        qea_split2_f16(preg[i], sp, h, l);
-        *reinterpret_cast<f16x4*>(Ps + o) = h;
-        *reinterpret_cast<f16x4*>(Ps + P_PLANE_B / 2 + o) = l;
-      }
-#pragma unroll
-      for (int i = 0; i < NQ; ++i) {
-        const int e = pt + 256 * i;
-        const int hq = e / 16;
-        if (hq < HP) {
-          const int o = row_off(hq, e % 16);
-          f16x4 h, l;
-          qea_split2_f16(qreg[i], sq, h, l);
-          *reinterpret_cast<f16x4*>(Qs + o) = h;
-          *reinterpret_cast<f16x4*>(Qs + Q_PLANE_B / 2 + o) = l;
-        }
-      }
-    };
-    if (ntl > 0) {
-      fetch(split);
-      stage(lds);
-      if (ntl > 1) fetch(split + hp.splits);
-    }
-    __syncthreads();                                         // tile 0 staged
-    for (int t = 0; t < ntl; ++t) {
-      if (t + 1 < ntl) stage(lds + ((t + 1) & 1) * BUF_B);
-      if (t + 2 < ntl) fetch(split + (t + 2) * hp.splits);
-      __syncthreads();                                       // consumers done with buffer t & 1, buffer (t + 1) & 1 complete
-    }
-    if (do_bias) {
-      // lanes l, l + 16, l + 32, l + 48 of a wave hold the same four channels (pixel rows 4 apart): wave sums, then one partial row per
-      // (split, producer wave): [splits * 4][R] doubles, summed in a fixed order by bias_finalize_kernel (fp64 to the end, as qea_colsum:
-      // in front of a batch-statistics BatchNorm this gradient is an exact zero made of cancelling terms)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        double v = bsum[k];
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        bsum[k] = v;
-      }
-      if (lane < 16) {
-        double* dst = bias_ws + (size_t)(split * 4 + (wave - 4)) * R + r0 + lane * 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k] = bsum[k];
-      }
-    }
-    return;
-  }
-
-  // ------------------------------------------------------------------ consumers
-  const int wr = wave >> 1, wc = wave & 1;
-  f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  // transposing-read geometry: pixel (g16 >> 1) * 8 + tq (+ 4 for the second read) of a 16-pixel k-step, channels (g16 & 1) * 16 + tpp * 4
-  const int g16 = lane >> 4, tq = (lane & 15) >> 2, tpp = lane & 3;
-  const int l_pix = (g16 >> 1) * 8 + tq;
-  const int l_ch = (g16 & 1) * 16 + tpp * 4;
-  // P fragment of k-step ks: LDS pixel row ks * 16 + l_pix (ks * 16 is a multiple of 4: the chunk swap only depends on l_pix)
-  const int p_off = l_pix * 128 + ((((wr ^ (l_pix >> 1)) & 1) << 5) + l_ch) * 2;
-  // Q fragment at halo pixel c + l_pix (c a compile-time tap offset): the chunk swap follows the parity of (c + l_pix) >> 1 -> four
-  // loop-invariant bases by (c & 1, (c >> 1) & 1) and an immediate c * 128
-  int TQ[2][2];
-#pragma unroll
-  for (int par = 0; par < 2; ++par)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int hs = (par ? (l_pix + 1) >> 1 : l_pix >> 1) + b;
-      TQ[par][b] = l_pix * 128 + ((((wc ^ hs) & 1) << 5) + l_ch) * 2;
-    }
-  __syncthreads();                                           // tile 0 staged
-  for (int t = 0; t < ntl; ++t) {
-    const char* buf = lds + (t & 1) * BUF_B;
-    const char* Pb = buf + p_off;
-    const char* Qb = buf + 2 * P_PLANE_B;
-    auto read_p = [&](int ks, f16x8* af) {
-      af[0] = tr_pair128(Pb + ks * 16 * 128);
-      af[1] = tr_pair128(Pb + P_PLANE_B + ks * 16 * 128);
-    };
-    auto read_q = [&](int f, f16x8* bf) {                   // f = ks * 9 + tap
-      const int ks = f / 9, tap = f % 9;
-      const int py = (ks * 16) / SW, px0 = (ks * 16) % SW;
-      const int c = (py + tap / 3) * HWD + px0 + tap % 3;
-      const char* src = Qb + TQ[c & 1][(c >> 1) & 1] + c * 128;
-      bf[0] = tr_pair128(src);
-      bf[1] = tr_pair128(src + Q_PLANE_B);
-    };
-    f16x8 af[2][2], bq[2][2];
-    read_p(0, af[0]);
-    read_q(0, bq[0]);
-#pragma unroll
-    for (int f = 0; f < 36; ++f) {
-      const int ks = f / 9, tap = f % 9;
-      const f16x8* a = af[ks & 1];
-      const f16x8* b = bq[f & 1];
-      if (f + 1 < 36) read_q(f + 1, bq[(f + 1) & 1]);
-      if (tap == 0 && ks + 1 < 4) read_p(ks + 1, af[(ks + 1) & 1]);
-      // smallest terms first (ll is dropped): lh, hl, hh
-      acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], acc[tap], 0, 0, 0);
-      acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], acc[tap], 0, 0, 0);
-      acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], acc[tap], 0, 0, 0);
-      if (f + 1 < 36) {
-        if (tap == 0 && ks + 1 < 4) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-        else __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-      }
-    }
-    __syncthreads();
-  }
-  float* out = ws + (size_t)split * R * 9 * C;
-  const int fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int rr = r0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-      out[((size_t)rr * 9 + t) * C + c0 + wc * 32 + fr] = (acc[t][r] * inv_p) * inv_q;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The producer / consumer form for 32-pixel-wide tiles with the X halo in a RING (round 4, tools/micro/wgrad_lab.hip: 380 -> 399 TFLOP/s at
-// 256 x 256 channels and 8 x 32 pixels, 297 -> 335 at 64 x 64 and 16 x 64, 397 -> 404 at 512 x 512 and 4 x 32).  A 2-row tile has a 4-row
-// halo: walking the tiles of one image column top to bottom, two of the four rows are the previous tile's.  A workgroup therefore takes
-// whole column strips (contiguous ranges of (image, column tile) pairs) and keeps the halo in a ring of 8 pixel rows: a tile reads ring
-// rows g .. g + 3, the producers meanwhile write the next tile's NEW rows — g + 4, g + 5 inside a strip, g + 4 .. g + 7 for the first tile
-// of the next strip — so they gather and split 68 instead of 136 halo pixels per tile.  g is even and a ring row holds an even number of
-// pixels, so the chunk-swap parity of a tap only needs the row's index inside the halo: a tap's address is one of 16 per-tile registers
-// (4 rows x the 4 table entries) + an immediate.  Everything else as wgrad_halo9_spec_kernel; the tile -> split assignment differs (strips,
-// not a stride), so the two agree to fp32 rounding and each is bit-reproducible.
-// ---------------------------------------------------------------------------------------------
-constexpr int H9R_ROWS = 8, H9R_HWD = 34;
-constexpr size_t halo9_ring_lds() { return (size_t)2 * (2 * 64 * 64 * 2) + (size_t)2 * H9R_ROWS * H9R_HWD * 64 * 2; }
-
-__global__ __launch_bounds__(512) void wgrad_halo9_ring_kernel(const float* __restrict__ p, const float* __restrict__ q, float* __restrict__ ws, int B, int H,
-                                                               int W, int R, int C, int ldp, int ldq, Halo9Plan hp, const float* __restrict__ pmax,
-                                                               const float* __restrict__ qmax, double* __restrict__ bias_ws) {
-  constexpr int SW = 32, TH = 2, HWD = H9R_HWD;
-  constexpr int P_PLANE_B = 64 * 64 * 2, QR_PLANE_B = H9R_ROWS * HWD * 64 * 2;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  char* const Pbase = reinterpret_cast<char*>(smem);                          // [2 buffers][h, l][64 px][64 ch]
-  char* const Qbase = Pbase + 2 * (2 * P_PLANE_B);                            // [h, l][8 ring rows][34][64 ch]
-  float sp, sq, inv_p, inv_q;
-  qea_f16_scale(pmax[0], sp, inv_p);
-  qea_f16_scale(qmax[0], sq, inv_q);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int bid = qea_xcd_swizzle(blockIdx.x, gridDim.x);
-  const int c_blk = bid % hp.c_blks;
-  bid /= hp.c_blks;
-  const int r_blk = bid % hp.r_blks;
-  const int split = bid / hp.r_blks;
-  const int r0 = r_blk * 64, c0 = c_blk * 64;
-  const int n_strips = B * hp.tiles_x;                                        // (hp.splits <= n_strips)
-  const int s0 = (int)((long long)n_strips * split / hp.splits), s1 = (int)((long long)n_strips * (split + 1) / hp.splits);
-  const int ntl = (s1 - s0) * hp.tiles_y;                                     // this workgroup's tiles, in (strip, tile row) order
-  auto ring_of = [&](int t) { return ((t + t / hp.tiles_y) * 2) & 7; };      // + 2 per tile inside a strip, + 4 across strips
-
-  if (wave >= 4) {
-    // ---------------------------------------------------------------- producers
-    const int pt = tid - 256;
-    constexpr int NP = 64 * 16 / 256, NQ = (4 * HWD * 16 + 255) / 256;        // 4, 9 (a whole four-row halo at a strip start)
-    f32x4 preg[NP], qreg[NQ];
-    int q_rows = 0, q_ring0 = 0;                                              // what qreg holds: halo rows and their first ring row
-    const bool do_bias = bias_ws != nullptr && c_blk == 0;
+    H9HaloRows qrows = {0, 0, 0};                             // what qreg holds
+    const bool do_bias = bias_ws != nullptr && blk.c_blk == 0;
     double bsum[4] = {0.0, 0.0, 0.0, 0.0};
     auto fetch = [&](int t) {
-      const int st = s0 + t / hp.tiles_y, ty = t % hp.tiles_y;
-      const int b = st / hp.tiles_x, x0 = (st % hp.tiles_x) * SW, y0 = ty * TH;
+      const H9Tile tl = halo.tile(t);
 #pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        const int e = pt + 256 * i;
-        const int c4 = e % 16, pix = e / 16;
-        const int py = pix / SW, px = pix - py * SW;
-        preg[i] = *reinterpret_cast<const f32x4*>(p + ((size_t)(b * H + y0 + py) * W + x0 + px) * ldp + r0 + c4 * 4);
-      }
-      const int hy0 = ty == 0 ? 0 : 2;                                        // all four halo rows at a strip start, else the two new ones
-      q_rows = 4 - hy0;
-      q_ring0 = (ring_of(t) + hy0) & 7;
+      for (int i = 0; i < NP; ++i) preg[i] = h9_p_chunk<HaloT::SW, 16>(p, pt + H9_NT * i, tl, H, W, ldp, r0);
+      qrows = halo.halo_rows(t);
 #pragma unroll
-      for (int i = 0; i < NQ; ++i) {
-        const int e = pt + 256 * i;
-        const int c4 = e % 16, hq = e / 16;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (hq < q_rows * HWD) {
-          const int hy = hy0 + hq / HWD, hx = hq % HWD;
-          const int iy = y0 + hy - 1, ix = x0 + hx - 1;
-          if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = *reinterpret_cast<const f32x4*>(q + ((size_t)(b * H + iy) * W + ix) * ldq + c0 + c4 * 4);
-        }
-        qreg[i] = v;
-      }
+      for (int i = 0; i < NQ; ++i) qreg[i] = h9_halo_chunk<HWD, 16>(q, pt + H9_NT * i, tl, H, W, qrows.hy0, qrows.n, ldq, c0);
     };
-    auto row_off = [](int pix, int c4) { return pix * 64 + ((((c4 >> 3) ^ (pix >> 1)) & 1) << 5) + (c4 & 7) * 4; };   // 16-bit elements
-    auto stage = [&](int pbuf) {
-      _Float16* Ps = reinterpret_cast<_Float16*>(Pbase + pbuf * (2 * P_PLANE_B));
-      _Float16* Qs = reinterpret_cast<_Float16*>(Qbase);
+    auto stage = [&](int buf) {
+      char* Ps = lds + buf * HaloT::P_BUF_B;
+      char* Qs = lds + HaloT::Q_BASE_B + buf * HaloT::Q_BUF_B;
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
-        const int e = pt + 256 * i;
-        const int o = row_off(e / 16, e % 16);
-        if (do_bias) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) bsum[k] += (double)preg[i][k];
-        }
-        f16x4 h, l;
-        qea_split2_f16(preg[i], sp, h, l);
-        *reinterpret_cast<f16x4*>(Ps + o) = h;
-        *reinterpret_cast<f16x4*>(Ps + P_PLANE_B / 2 + o) = l;
+        const int e = pt + H9_NT * i;
+        if (do_bias) h9_bias_add(bsum, preg[i]);
+        h9_split_store<2>(Ps, H9_P_PLANE_B / 2, h9_row_off<64>(e / 16, e % 16), preg[i], sp);
       }
 #pragma unroll
       for (int i = 0; i < NQ; ++i) {
-        const int e = pt + 256 * i;
+        const int e = pt + H9_NT * i;
         const int hq = e / 16;
-        if (hq < q_rows * HWD) {
-          const int rr = (q_ring0 + hq / HWD) & 7;
-          const int o = row_off(rr * HWD + hq % HWD, e % 16);
-          f16x4 h, l;
-          qea_split2_f16(qreg[i], sq, h, l);
-          *reinterpret_cast<f16x4*>(Qs + o) = h;
-          *reinterpret_cast<f16x4*>(Qs + QR_PLANE_B / 2 + o) = l;
+        if (hq < qrows.n * HWD) {
+          const int hr = hq / HWD;
+          const int pix = HaloT::lds_row(qrows.row0, hr) * HWD + hq - hr * HWD;
+          h9_split_store<2>(Qs, HaloT::Q_PLANE_B / 2, h9_row_off<64>(pix, e % 16), qreg[i], sq);
         }
       }
     };
@@ -1367,20 +1318,7 @@ __global__ __launch_bounds__(512) void wgrad_halo9_ring_kernel(const float* __re
       if (t + 2 < ntl) fetch(t + 2);
       __syncthreads();                                       // consumers done with tile t, tile t + 1 complete
     }
-    if (do_bias) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        double v = bsum[k];
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        bsum[k] = v;
-      }
-      if (lane < 16) {
-        double* dst = bias_ws + (size_t)(split * 4 + (wave - 4)) * R + r0 + lane * 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k] = bsum[k];
-      }
-    }
+    if (do_bias) h9_bias_store(bsum, bias_ws + (size_t)(split * 4 + (wave - 4)) * R + r0, lane);
     return;
   }
 
@@ -1391,73 +1329,42 @@ __global__ __launch_bounds__(512) void wgrad_halo9_ring_kernel(const float* __re
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  const int g16 = lane >> 4, tq = (lane & 15) >> 2, tpp = lane & 3;
-  const int l_pix = (g16 >> 1) * 8 + tq;
-  const int l_ch = (g16 & 1) * 16 + tpp * 4;
-  const int p_off = l_pix * 128 + ((((wr ^ (l_pix >> 1)) & 1) << 5) + l_ch) * 2;
+  const H9Lane ln = h9_lane(lane);
+  const int p_off = h9_p_off(ln, wr);
   int TQ[2][2];
-#pragma unroll
-  for (int par = 0; par < 2; ++par)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int hs = (par ? (l_pix + 1) >> 1 : l_pix >> 1) + b;
-      TQ[par][b] = l_pix * 128 + ((((wc ^ hs) & 1) << 5) + l_ch) * 2;
-    }
+  h9_q_offs(ln, wc, TQ);
   __syncthreads();                                           // tile 0 staged
   for (int t = 0; t < ntl; ++t) {
-    const char* Pb = Pbase + (t & 1) * (2 * P_PLANE_B) + p_off;
-    const int g = ring_of(t);
-    int QB[4][2][2];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int rowoff = ((g + k) & 7) * (HWD * 128);
-#pragma unroll
-      for (int par = 0; par < 2; ++par)
-#pragma unroll
-        for (int bb = 0; bb < 2; ++bb) QB[k][par][bb] = TQ[par][bb] + rowoff;
-    }
+    const char* Pb = lds + (t & 1) * HaloT::P_BUF_B + p_off;
+    const char* Qb = lds + HaloT::Q_BASE_B + (t & 1) * HaloT::Q_BUF_B;
+    int tab[HaloT::TAB_ROWS][2][2];
+    halo.q_table(t, TQ, tab);
     auto read_p = [&](int ks, f16x8* af) {
       af[0] = tr_pair128(Pb + ks * 16 * 128);
-      af[1] = tr_pair128(Pb + P_PLANE_B + ks * 16 * 128);
+      af[1] = tr_pair128(Pb + H9_P_PLANE_B + ks * 16 * 128);
     };
     auto read_q = [&](int f, f16x8* bf) {                   // f = ks * 9 + tap
-      const int ks = f / 9, tap = f % 9;
-      const int py = (ks * 16) / SW, px0 = (ks * 16) % SW;
-      const int k = py + tap / 3, col = px0 + tap % 3;
-      const char* src = Qbase + QB[k][col & 1][((col >> 1) + k) & 1] + col * 128;
+      const char* src = Qb + HaloT::q_frag(tab, f / 9, f % 9);
       bf[0] = tr_pair128(src);
-      bf[1] = tr_pair128(src + QR_PLANE_B);
+      bf[1] = tr_pair128(src + HaloT::Q_PLANE_B);
     };
-    f16x8 af[2][2], bq[2][2];
-    read_p(0, af[0]);
-    read_q(0, bq[0]);
-#pragma unroll
-    for (int f = 0; f < 36; ++f) {
-      const int ks = f / 9, tap = f % 9;
-      const f16x8* a = af[ks & 1];
-      const f16x8* b = bq[f & 1];
-      if (f + 1 < 36) read_q(f + 1, bq[(f + 1) & 1]);
-      if (tap == 0 && ks + 1 < 4) read_p(ks + 1, af[(ks + 1) & 1]);
-      acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], acc[tap], 0, 0, 0);
-      acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], acc[tap], 0, 0, 0);
-      acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], acc[tap], 0, 0, 0);
-      if (f + 1 < 36) {
-        if (tap == 0 && ks + 1 < 4) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-        else __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-      }
-    }
+    h9_mma_tile(acc, read_p, read_q);
     __syncthreads();
   }
-  float* out = ws + (size_t)split * R * 9 * C;
-  const int fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int rr = r0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-      out[((size_t)rr * 9 + t) * C + c0 + wc * 32 + fr] = (acc[t][r] * inv_p) * inv_q;
-    }
+  h9_store_slab(ws + (size_t)split * R * 9 * C, acc, lane, r0 + wr * 32, c0 + wc * 32, C, inv_p, inv_q);
+}
+
+// the two entry points keep their names: traces, tools/pmc_traffic.py and tools/design_numbers.py read them
+__global__ __launch_bounds__(512) void wgrad_halo9_spec_kernel(const float* __restrict__ p, const float* __restrict__ q, float* __restrict__ ws, int B, int H,
+                                                               int W, int R, int C, int ldp, int ldq, Halo9Plan hp, const float* __restrict__ pmax,
+                                                               const float* __restrict__ qmax, double* __restrict__ bias_ws) {
+  halo9_pc_body<Halo9Whole16>(p, q, ws, B, H, W, R, C, ldp, ldq, hp, pmax, qmax, bias_ws);
+}
+
+__global__ __launch_bounds__(512) void wgrad_halo9_ring_kernel(const float* __restrict__ p, const float* __restrict__ q, float* __restrict__ ws, int B, int H,
+                                                               int W, int R, int C, int ldp, int ldq, Halo9Plan hp, const float* __restrict__ pmax,
+                                                               const float* __restrict__ qmax, double* __restrict__ bias_ws) {
+  halo9_pc_body<Halo9Ring32>(p, q, ws, B, H, W, R, C, ldp, ldq, hp, pmax, qmax, bias_ws);
 }
 
 Halo9Plan halo9_plan(const qea_wgrad_desc* d) {
@@ -1509,7 +1416,7 @@ int launch_halo9_any(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s)
   return (d->p_absmax && d->q_absmax) ? launch_halo9_<SW, RB, CB, 2>(d, h, s) : launch_halo9_<SW, RB, CB, 3>(d, h, s);
 }
 
-// the producer / consumer forms: the ring kernel for 32-pixel-wide tiles, wgrad_halo9_spec_kernel<16> for the 16-wide ones
+// the producer / consumer forms: the ring kernel for 32-pixel-wide tiles, wgrad_halo9_spec_kernel for the 16-wide ones
 template <auto Kernel, size_t LDS>
 int launch_halo9_pc(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s, double* bias_ws) {
   const int rc = reserve_lds<Kernel>("qea_conv_wgrad", LDS);
@@ -1521,8 +1428,8 @@ int launch_halo9_pc(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s, 
 
 int launch_halo9(const qea_wgrad_desc* d, const Halo9Plan& h, hipStream_t s, double* bias_ws) {
   if (h.spec)
-    return h.sw == 32 ? launch_halo9_pc<wgrad_halo9_ring_kernel, halo9_ring_lds()>(d, h, s, bias_ws)
-                      : launch_halo9_pc<wgrad_halo9_spec_kernel<16>, halo9_spec_lds<16>()>(d, h, s, bias_ws);
+    return h.sw == 32 ? launch_halo9_pc<wgrad_halo9_ring_kernel, Halo9Ring32::LDS>(d, h, s, bias_ws)
+                      : launch_halo9_pc<wgrad_halo9_spec_kernel, Halo9Whole16::LDS>(d, h, s, bias_ws);
   if (h.sw == 32) return h.rb == 64 ? launch_halo9_any<32, 64, 64>(d, h, s) : launch_halo9_any<32, 32, 32>(d, h, s);
   return h.rb == 64 ? launch_halo9_any<16, 64, 64>(d, h, s) : launch_halo9_any<16, 32, 32>(d, h, s);
 }
